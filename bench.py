@@ -12,7 +12,12 @@ matrices (independent units, no data-path collective): weak scaling.  Rank 0 pri
 line: value = matrices/s over all ranks = N * batch * K / T, T = max over ranks of the time of
 exactly K steps bracketed by barrier + torch.cuda.synchronize().
 
-Extra objects on the same line:
+A plain run does only that: set up, warm up, time the K steps, print the line (metric, value, unit,
+ms_per_step, higher_is_better, dtype and the configuration).  ``--dump-outputs DIR`` also writes what the
+timed path returned in its last step (see dump_outputs), for comparing two builds output for output.
+
+With ``--full`` the line also carries the correctness check of the timed result (residual_inf, status_max)
+and these extra objects; the --no-* switches skip single legs of a --full run:
   roofline      -- the kernel that carries the algorithmic flops (or bytes): per-launch
                    durations from HIP events recorded on the launch stream (inside the library,
                    mi32_set_profiling) over a second, instrumented pass of the same K steps, so the
@@ -54,6 +59,11 @@ PUBLISHED_MATRICES_PER_S_N4096 = 1.0 / 2.92434
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense fp32 MFMA = fp32 vector peak
 PEAK_HBM_GBPS = 8000.0          # HBM3E spec
 PMC_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "round3", "pmc_traffic.json")
+# --dump-outputs: the inverses are written whole while they fit DUMP_INVERSE_BYTES, else as a fixed seeded sample of
+# DUMP_SAMPLE entries with their flat indices (float32 values + float64 indices = 25 MB); both stay under 64 MB in all
+DUMP_INVERSE_BYTES = 48 * 10 ** 6
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 20240601
 
 
 def gate_matrix(n, seed):
@@ -202,6 +212,27 @@ def pmc_traffic(algo_name, n, batch, bw):
                                                      "write_bytes": e.get("write_bytes")}
 
 
+def dump_outputs(path, out, status, world=1, rank=0):
+    """Write what a caller of the timed path received from its last step as .npy files under `path`:
+    inverse.npy (batch x n x n float32) -- or, above DUMP_INVERSE_BYTES, inverse_sample.npy (float32) with the flat
+    indices into the batch it was taken at, inverse_sample_index.npy (float64; sorted, drawn with DUMP_SEED, so the
+    same for every run of the same shape) -- and status.npy (the status words as float32).  With several ranks every
+    rank writes its own files, prefixed rank<r>_, and the budget is shared among them."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    flat = out.reshape(-1)
+    if flat.numel() * 4 <= DUMP_INVERSE_BYTES // world:
+        np.save(os.path.join(path, prefix + "inverse.npy"), out.cpu().numpy().astype(np.float32))
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE // world))
+        vals = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, prefix + "inverse_sample.npy"), vals)
+        np.save(os.path.join(path, prefix + "inverse_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, prefix + "status.npy"), status.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -221,7 +252,15 @@ def main():
     ap.add_argument("--distribute", dest="distribute", action="store_true", default=True,
                     help="N > 1 (default on): also time the batch scattered from / gathered to rank 0 over RCCL (xGMI)")
     ap.add_argument("--no-distribute", dest="distribute", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the residual check, the instrumented pass (roofline, kernel breakdown), "
+                         "the resident batch, the distribution leg, e2e, the CPU baselines and the reference distributions "
+                         "(the --no-* switches skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as .npy files under DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.algo != "auto":  # the host-pointer entry point (e2e leg) runs on the default context: same algorithm
         os.environ["MI32_ALGO"] = {"sweep": "1", "blocked": "2"}[args.algo]
@@ -274,19 +313,23 @@ def main():
         elapsed = float(t.item())
     torch.cuda.synchronize()
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, status, world, rank)
+
     # correctness of what was just timed (outside the timed region)
-    res = inv.residual(a, out)
-    torch.cuda.synchronize()
-    res_right = float(res[:, 0].max())
-    res_left = float(res[:, 1].max())
-    res_frob = float(res[:, 2].abs().max())
-    st_max = int(status.max())
+    if args.full:
+        res = inv.residual(a, out)
+        torch.cuda.synchronize()
+        res_right = float(res[:, 0].max())
+        res_left = float(res[:, 1].max())
+        res_frob = float(res[:, 2].abs().max())
+        st_max = int(status.max())
 
     # What the GPU does with this order when it is not waiting on one matrix's chain of pivot steps: the headline
     # configuration keeps 1 CU of 256 busy for most of its time (roofline.time_dominant), a resident batch of the same
     # matrices fills the rest.  Extra key, not the headline (BASELINE.json's metric is matrices/s).
     resident = None
-    if rank == 0 and batch == 1 and n <= 4096 and not args.no_resident_batch:
+    if args.full and rank == 0 and batch == 1 and n <= 4096 and not args.no_resident_batch:
         resident = {}
         for nb in (4, 8):
             ab = a.expand(nb, n, n).contiguous()
@@ -306,7 +349,7 @@ def main():
 
     # with distribution: the whole batch starts on rank 0, travels over RCCL point-to-point sends
     distribution = None
-    if args.distribute and world > 1:
+    if args.full and args.distribute and world > 1:
         try:
             full = None
             if rank == 0:
@@ -345,7 +388,7 @@ def main():
     # instrumented pass: HIP events around every launch, on the launch stream
     roof = None
     breakdown = None
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         inv.set_lookahead(False)  # one clean full-size launch of the rank-bw kernel per block
         inv.set_profiling(True)
         inv.get_profile()
@@ -399,7 +442,7 @@ def main():
 
     # T_e2e through the host-pointer drop-in (rank 0 only; pageable host memory both ways)
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if args.full and rank == 0 and not args.no_e2e:
         reps = 5 if n <= 4096 else 2
         times, computes = [], []
         flat = host.reshape(batch, -1)
@@ -446,19 +489,22 @@ def main():
             "parallelism": "independent matrices sharded over ranks, no data-path collective",
             "vs_baseline_denominator": "0.342 matrices/s: reference kernel loop, N=4096, RX 5700 (BASELINE.md)",
         },
-        "residual_inf": res_right,
-        "residual_inf_left": res_left,
-        "frobenius_metric_abs": res_frob,
-        "status_max": st_max,
-        "roofline": roof,
-        "kernel_breakdown": breakdown,
-        "e2e": e2e,
     }
+    if args.full:
+        line.update({
+            "residual_inf": res_right,
+            "residual_inf_left": res_left,
+            "frobenius_metric_abs": res_frob,
+            "status_max": st_max,
+            "roofline": roof,
+            "kernel_breakdown": breakdown,
+            "e2e": e2e,
+        })
     if distribution is not None:
         line["distribution"] = distribution
     if resident is not None:
         line["resident_batch_throughput"] = resident
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cb = cpu_baseline(host[0])
         line["cpu_baseline"] = cb
         line["cpu_baseline_oracle_port"] = oracle_port_baseline()

@@ -1028,11 +1028,11 @@ def test_no_pivot_blocked_4096_bit_identical_and_timed(oracle):
 
 def test_bench_py_contract_line():
     """bench.py prints ONE JSON line with the driver's contract keys, the roofline and cpu_baseline objects and the
-    round-2 additions (e2e through matrix_inv_32, time-dominant kernel class, reference distributions), on a small run."""
+    round-2 additions (e2e through matrix_inv_32, time-dominant kernel class, reference distributions), on a small --full run."""
     import json
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "640", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "640", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1051,6 +1051,31 @@ def test_bench_py_contract_line():
     assert d["e2e"]["e2e_ms"] >= d["e2e"]["compute_ms_inside"] > 0 and d["speedup_vs_numpy_e2e"] > 0
     assert d["residual_inf"] < 1e-3 and d["status_max"] == 0
     assert set(d["residuals_reference_distributions"]) == {"D_ref100", "D_rand"}
+
+
+def test_bench_py_plain_run_and_dumped_outputs(oracle, tmp_path):
+    """A plain bench.py run (no --full): the headline line only, exactly --steps timed steps, and --dump-outputs writes
+    what the timed path returned in its last step -- the reference-order oracle's bits on bench.py's input."""
+    import json
+
+    n, dump = 300, tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--batch", "2", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "kernel_breakdown", "e2e", "cpu_baseline", "residual_inf", "resident_batch_throughput"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "matrices/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 * 2 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert sorted(os.listdir(dump)) == ["inverse.npy", "status.npy"]
+    x, st = np.load(dump / "inverse.npy"), np.load(dump / "status.npy")
+    assert x.dtype == np.float32 and x.shape == (2, n, n) and st.dtype == np.float32 and np.array_equal(st, [0, 0])
+    for b in range(2):  # bench.py's input: gate_matrix(n, 1000 + rank * batch + b)
+        assert np.array_equal(x[b].reshape(-1), oracle_inverse(oracle, gate_matrix(n, 1000 + b), n)), b
 
 
 def test_experiment_header_twins(oracle, tmp_path):

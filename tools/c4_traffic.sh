@@ -1,6 +1,6 @@
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof; mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-python3 bench.py --n 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-resident-batch > $OUT/bench_c4.json 2> $OUT/bench_c4.log || { tail -5 $OUT/bench_c4.log; exit 1; }
+python3 bench.py --full --n 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-resident-batch > $OUT/bench_c4.json 2> $OUT/bench_c4.log || { tail -5 $OUT/bench_c4.log; exit 1; }
 python3 tools/show_bench.py $OUT/bench_c4.json 2>/dev/null | head -12
 export MI32_LOOKAHEAD=0
 for ctr in FETCH_SIZE WRITE_SIZE; do

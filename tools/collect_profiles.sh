@@ -25,7 +25,7 @@ fail() {  # name, log
 }
 run_stats() {  # name, bench args...
     local name=$1; shift
-    rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o "$name" --output-format csv -- python3 bench.py "$@" --no-resident-batch \
+    rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o "$name" --output-format csv -- python3 bench.py --full "$@" --no-resident-batch \
         --no-cpu-baseline --no-e2e > "$OUT/${name}_bench_under_rocprof.json" 2> "$OUT/${name}.log" || fail "stats $name" "$OUT/${name}.log"
     echo "stats $name done"
 }
@@ -58,11 +58,11 @@ if want sq; then
     pmc "$SQ" c2 "gj_rank_bw2|gj_subpanel|gj_inblock|gj_block_strip" --n 2048 --batch 64 --steps 2 --warmup 1
 fi
 unset MI32_LOOKAHEAD
-if want bench; then  # plain bench lines (what the driver runs)
-    python3 bench.py > "$OUT/bench_c1_default.json" 2> "$OUT/bench_c1_default.log" || fail "bench c1" "$OUT/bench_c1_default.log"; echo "bench c1 done"
-    python3 bench.py --n 2048 --batch 64 --steps 5 --warmup 2 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.log" || fail "bench c2" "$OUT/bench_c2.log"; echo "bench c2 done"
-    python3 bench.py --n 16384 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.log" || fail "bench c4" "$OUT/bench_c4.log"; echo "bench c4 done"
-    python3 bench.py --algo sweep --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_c1_sweep.json" 2> "$OUT/bench_c1_sweep.log" || fail "bench sweep" "$OUT/bench_c1_sweep.log"; echo "bench sweep done"
+if want bench; then  # full bench lines (the driver's headline plus every --full leg)
+    python3 bench.py --full > "$OUT/bench_c1_default.json" 2> "$OUT/bench_c1_default.log" || fail "bench c1" "$OUT/bench_c1_default.log"; echo "bench c1 done"
+    python3 bench.py --full --n 2048 --batch 64 --steps 5 --warmup 2 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.log" || fail "bench c2" "$OUT/bench_c2.log"; echo "bench c2 done"
+    python3 bench.py --full --n 16384 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.log" || fail "bench c4" "$OUT/bench_c4.log"; echo "bench c4 done"
+    python3 bench.py --full --algo sweep --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_c1_sweep.json" 2> "$OUT/bench_c1_sweep.log" || fail "bench sweep" "$OUT/bench_c1_sweep.log"; echo "bench sweep done"
 fi
 python3 tools/pmc_traffic.py "$OUT" "$OUT/pmc_traffic.json" > "$OUT/pmc_traffic.log" 2>&1 || fail "pmc_traffic.py" "$OUT/pmc_traffic.log"
 python3 tools/pmc_sq_summary.py "$OUT" "$OUT/pmc_sq_summary.json" > "$OUT/pmc_sq_summary.log" 2>&1 || fail "pmc_sq_summary.py" "$OUT/pmc_sq_summary.log"

@@ -12,13 +12,22 @@
 //                     pivot steps on them: column arg-max (DPP + one LDS atomic), row
 //                     swap (= exchange of two position labels), IEEE-division
 //                     normalise, eliminate.  Result: G_s = the W transformed columns
-//                     (the inverse columns of these pivots).
-//       update(s)  -- every other column j of the block (fp32 MFMA, K = W):
-//                     M[i][j] = (i in Ks ? 0 : M[src(i)][j]) + sum_k G_s[i][k] * M[src(c0+k)][j]
-//     rank-bw update (K = kb, mi32_rank_bw.h) -- every column outside the block, same
-//                     formula with the block's composite G and row map.
+//                     (the inverse columns of these pivots) and the multipliers f_m[i] of
+//                     its steps (the entry row i had in the pivot column when step m ran).
+//       update(s)  -- every other column j of the block, 64-column tiles: the tile's W pivot
+//                     rows run the W steps alone (the strip: u_m[j] = pivot row of step m over
+//                     its pivot, W dependent IEEE divisions), then every other row takes
+//                     M[i][j] = fmaf(-f_m[i], u_m[j], M[i][j]), m ascending, as ONE chain from
+//                     its old value (v_mfma_f32_32x32x2_f32 with the old value as C operand):
+//                     the reference's own operation order.
+//       strip(s)   -- the columns outside the block: only their W pivot rows, which first
+//                     take the block's earlier steps; u_m is kept (ub) for the rank-bw update.
+//     rank-bw update (K = kb, mi32_rank_bw.h) -- every column outside the block: the same
+//                     chain from the old value over all kb steps, A = the block's multipliers,
+//                     B = u.
 //
-// panel(s) and update(s-1) are ONE launch (gj_subpanel_kernel: workgroup 0 of a
+// strip(s-1) rides in the launch of panel(s).  In blocks of at most kFusedRows rows,
+// panel(s) and update(s-1) are ONE launch too (gj_subpanel_kernel: workgroup 0 of a
 // matrix is the panel, the others are update tiles): update(s-1) no longer sits
 // between two panels on the critical path of the N pivot steps.  What panel(s)
 // needs from update(s-1) -- its own W columns -- it computes itself in a prologue
@@ -53,6 +62,8 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <set>
+#include <type_traits>
 #include <utility>
 
 #include "mi32_internal.h"
@@ -62,17 +73,9 @@ namespace mi32 {
 
 typedef float float16v __attribute__((ext_vector_type(16)));
 
-// k-tile depth and waves/SIMD of the rank-bw update (mi32_rank_bw.h; tunable at build time)
-#ifndef MI32_BW_BK
-#define MI32_BW_BK 16
-#endif
-#ifndef MI32_BW_PF
-#define MI32_BW_PF 0   // (round 2 fetched the old values of a tile under its last k-tiles; the accumulation from the old
-                       // value, round 3, needs them in front of the k-loop)
-#endif
-#ifndef MI32_BW_WPS
-#define MI32_BW_WPS (MI32_BW_PF ? 2 : 3)   // the prefetch keeps 64 more registers live: two workgroups per CU
-#endif
+// k-tile depth and waves/SIMD of the rank-bw update (mi32_rank_bw.h)
+static constexpr int kBwBK = 16;
+static constexpr int kBwWPS = 3;
 static constexpr int kMaxBW = 512;  // widest outer block (rows of the transposed panel Gk)
 
 static constexpr int kMaxW = 32;  // widest sub-panel (columns kept in registers)
@@ -113,10 +116,6 @@ BlockedPlan make_blocked_plan(int n, int w, int bw, int batch)
     // Row stride: np + 64 floats (256 B): keeps rows 256-B aligned and avoids a power-of-two stride.
     p.ld = p.np + 64;
     int nt = (p.np >= 2048) ? 1024 : 512;
-    if (const char *e = std::getenv("MI32_PANEL_THREADS")) {
-        const int v = std::atoi(e);
-        if (v == 512 || v == 1024) nt = v;
-    }
     int rpt = 1;
     while (rpt * nt < p.np) rpt *= 2;
     if (rpt > 8 && nt == 512) {  // no 512-thread instance holds more than 8 rows per lane: use 1024
@@ -544,9 +543,6 @@ struct PanelGroup {
 template <int V, typename T>
 __device__ __forceinline__ void mt_store(float *sbase, unsigned voff, T v)
 {
-#ifdef MI32_TIMING_NO_MT_STORE  // timing-only builds (wrong results): what do the multiplier stores cost the panel?
-    return;
-#endif
     if constexpr (V == 1) asm volatile("global_store_dword %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase));
     else if constexpr (V == 2) asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase));
     else asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase));
@@ -986,10 +982,10 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
         }
         __syncthreads();
         const float *mtp = A.mt_prev + (size_t)b * A.mtstride;
-#ifndef MI32_PRO_REGS
-#define MI32_PRO_REGS 16  // (32: hipcc hoists every LDS read of the round and spills them -- 892 B of scratch per lane in the 1024 x 2 instance)
-#endif
-        constexpr int KC = (MI32_PRO_REGS / RPT) < 1 ? 1 : ((MI32_PRO_REGS / RPT) > W ? W : (MI32_PRO_REGS / RPT));  // k's per round of loads
+        // registers of multipliers per round (32: hipcc hoists every LDS read of the round and spills them -- 892 B
+        // of scratch per lane in the 1024 x 2 instance)
+        constexpr int kProRegs = 16;
+        constexpr int KC = (kProRegs / RPT) < 1 ? 1 : ((kProRegs / RPT) > W ? W : (kProRegs / RPT));  // k's per round of loads
         // a ROLLED loop over the rounds: unrolled, hipcc hoists every round's loads to the top and the whole of
         // Mt_{s-1} (RPT * W registers) is live beside the slab
 #pragma unroll 1
@@ -2023,24 +2019,55 @@ extern "C" int mi32_debug_drop_panel_group(int enable)
     return 0;
 }
 
+// Raises a kernel's dynamic-LDS limit to `bytes`, once per device (function attributes are per device; any thread may
+// be the first to launch).
+static hipError_t raise_lds_limit(const void *kernel, size_t bytes)
+{
+    static std::mutex mu;
+    static std::set<std::pair<const void *, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count({kernel, dev})) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) done.insert({kernel, dev});
+    return e;
+}
+
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v: a run-time value as a template argument
+template <int... Vs, class F>
+static hipError_t with_constant(int v, F &&f)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return e;
+}
+
+// Fused launches exist for the panel geometries of at most kFusedRows rows (see "Fused mode" in blocked_invert).
+static constexpr int kFusedRows = 2048;
+// The instances of gj_subpanel_kernel: every panel geometry make_blocked_plan can give a block -- one row per lane at
+// 256 threads; at 512 threads at most 8 rows per lane and 128 floats of slab, at 1024 threads at most 64 floats.
+constexpr bool subpanel_instance(int nt, int rpt, int w, bool fused)
+{
+    const bool fits = nt == 256 ? rpt == 1 : nt == 512 ? (rpt <= 8 && rpt * w <= 128) : rpt * w <= 64;
+    return fits && (!fused || nt * rpt <= kFusedRows);
+}
+
 template <int NT, int RPT, int W, bool FUSED>
 static hipError_t launch_subpanel(const SubpanelArgs &A, int nwgs, hipStream_t stream)
 {
-    constexpr size_t lds = subpanel_lds_bytes<NT, RPT, W, FUSED>();
-    if (lds > 48 * 1024) {  // more dynamic LDS than the default limit: raise it once per device (any thread may be first)
-        static std::once_flag once[64];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        hipError_t e = hipSuccess;
-        std::call_once(once[dev & 63], [&] {
-            e = hipFuncSetAttribute((const void *)gj_subpanel_kernel<NT, RPT, W, FUSED>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        });
-        if (e != hipSuccess) return e;
+    if constexpr (!subpanel_instance(NT, RPT, W, FUSED)) {
+        return hipErrorInvalidValue;
+    } else {
+        constexpr size_t lds = subpanel_lds_bytes<NT, RPT, W, FUSED>();
+        if (lds > 48 * 1024) {  // more dynamic LDS than the default limit
+            const hipError_t e = raise_lds_limit((const void *)gj_subpanel_kernel<NT, RPT, W, FUSED>, lds);
+            if (e != hipSuccess) return e;
+        }
+        const size_t lds_now = subpanel_lds_bytes<NT, RPT, W, FUSED>(A.os_on != 0);
+        hipLaunchKernelGGL((gj_subpanel_kernel<NT, RPT, W, FUSED>), dim3(nwgs), dim3(NT), lds_now, stream, A);
+        return hipSuccess;
     }
-    const size_t lds_now = subpanel_lds_bytes<NT, RPT, W, FUSED>(A.os_on != 0);
-    hipLaunchKernelGGL((gj_subpanel_kernel<NT, RPT, W, FUSED>), dim3(nwgs), dim3(NT), lds_now, stream, A);
-    return hipSuccess;
 }
 
 // One launch of the sub-panel pipeline:
@@ -2056,12 +2083,10 @@ static hipError_t dispatch_subpanel(const BlockedPlan &p, int w, const SubpanelA
     const int os_tiles = A.os_on ? A.batch * A.os_ntiles : 0;  // strip tiles of columns outside the block
     if (!A.panel_on) {
         A.upd_wgs = A.batch * tiles;
-        const dim3 grid(A.upd_wgs + os_tiles);
-        if (w == 32) hipLaunchKernelGGL((gj_inblock_update_kernel<32>), grid, dim3(256), 0, stream, A);
-        else if (w == 16) hipLaunchKernelGGL((gj_inblock_update_kernel<16>), grid, dim3(256), 0, stream, A);
-        else if (w == 8) hipLaunchKernelGGL((gj_inblock_update_kernel<8>), grid, dim3(256), 0, stream, A);
-        else hipLaunchKernelGGL((gj_inblock_update_kernel<4>), grid, dim3(256), 0, stream, A);
-        return hipSuccess;
+        return with_constant<4, 8, 16, 32>(w, [&](auto W) {
+            hipLaunchKernelGGL((gj_inblock_update_kernel<W>), dim3(A.upd_wgs + os_tiles), dim3(256), 0, stream, A);
+            return hipSuccess;
+        });
     }
     if (A.ngroups > 1) {  // multi-workgroup panel: never fused, W = 16 (what the plan gives every block then)
         if (A.upd_on || w != 16) return hipErrorInvalidValue;
@@ -2074,96 +2099,54 @@ static hipError_t dispatch_subpanel(const BlockedPlan &p, int w, const SubpanelA
                            dim3(1024), lds_now, stream, A);
         return hipSuccess;
     }
-    const bool fused = A.upd_on != 0;
     int nt, rpt;
     panel_geometry(p, p.np - A.row_lo, nt, rpt);
     A.upd_wgs = A.batch * (tiles / (nt / 256));
     const int nwgs = A.batch + A.upd_wgs + (os_tiles + nt / 256 - 1) / (nt / 256);
-#define MI32_SUBPANEL_CASE(T, R, WW)                                                                   \
-    if (nt == T && rpt == R && w == WW && !fused) return launch_subpanel<T, R, WW, false>(A, nwgs, stream);
-#define MI32_SUBPANEL_FUSED(T, R, WW)                                                                  \
-    if (nt == T && rpt == R && w == WW && fused) return launch_subpanel<T, R, WW, true>(A, nwgs, stream);
-#ifdef MI32_EXPERIMENT_MIN  // compile-time experiments (tools/build_check.sh): the two instances C1 runs most
-    MI32_SUBPANEL_CASE(1024, 4, 16) MI32_SUBPANEL_FUSED(1024, 2, 16)
-#else
-    MI32_SUBPANEL_CASE(256, 1, 32) MI32_SUBPANEL_CASE(256, 1, 16) MI32_SUBPANEL_CASE(256, 1, 8) MI32_SUBPANEL_CASE(256, 1, 4)
-    MI32_SUBPANEL_CASE(512, 1, 32) MI32_SUBPANEL_CASE(512, 2, 32) MI32_SUBPANEL_CASE(512, 4, 32)
-    MI32_SUBPANEL_CASE(1024, 1, 32) MI32_SUBPANEL_CASE(1024, 2, 32)
-    MI32_SUBPANEL_CASE(512, 1, 16) MI32_SUBPANEL_CASE(512, 2, 16) MI32_SUBPANEL_CASE(512, 4, 16) MI32_SUBPANEL_CASE(512, 8, 16)
-    MI32_SUBPANEL_CASE(512, 1, 8) MI32_SUBPANEL_CASE(512, 2, 8) MI32_SUBPANEL_CASE(512, 4, 8) MI32_SUBPANEL_CASE(512, 8, 8)
-    MI32_SUBPANEL_CASE(512, 1, 4) MI32_SUBPANEL_CASE(512, 2, 4) MI32_SUBPANEL_CASE(512, 4, 4) MI32_SUBPANEL_CASE(512, 8, 4)
-    MI32_SUBPANEL_CASE(1024, 1, 16) MI32_SUBPANEL_CASE(1024, 2, 16) MI32_SUBPANEL_CASE(1024, 4, 16)
-    MI32_SUBPANEL_CASE(1024, 1, 8) MI32_SUBPANEL_CASE(1024, 2, 8) MI32_SUBPANEL_CASE(1024, 4, 8) MI32_SUBPANEL_CASE(1024, 8, 8)
-    MI32_SUBPANEL_CASE(1024, 1, 4) MI32_SUBPANEL_CASE(1024, 2, 4) MI32_SUBPANEL_CASE(1024, 4, 4) MI32_SUBPANEL_CASE(1024, 8, 4)
-    MI32_SUBPANEL_CASE(1024, 16, 4)
-    // fused launches exist for the geometries of at most kFusedRows rows (blocked_invert)
-    MI32_SUBPANEL_FUSED(256, 1, 32) MI32_SUBPANEL_FUSED(256, 1, 16) MI32_SUBPANEL_FUSED(256, 1, 8) MI32_SUBPANEL_FUSED(256, 1, 4)
-    MI32_SUBPANEL_FUSED(512, 1, 32) MI32_SUBPANEL_FUSED(512, 2, 32) MI32_SUBPANEL_FUSED(512, 4, 32)
-    MI32_SUBPANEL_FUSED(1024, 1, 32) MI32_SUBPANEL_FUSED(1024, 2, 32)
-    MI32_SUBPANEL_FUSED(512, 1, 16) MI32_SUBPANEL_FUSED(512, 2, 16) MI32_SUBPANEL_FUSED(512, 4, 16)
-    MI32_SUBPANEL_FUSED(1024, 1, 16) MI32_SUBPANEL_FUSED(1024, 2, 16)
-    MI32_SUBPANEL_FUSED(512, 1, 8) MI32_SUBPANEL_FUSED(512, 2, 8) MI32_SUBPANEL_FUSED(512, 4, 8)
-    MI32_SUBPANEL_FUSED(1024, 1, 8) MI32_SUBPANEL_FUSED(1024, 2, 8)
-    MI32_SUBPANEL_FUSED(512, 1, 4) MI32_SUBPANEL_FUSED(512, 2, 4) MI32_SUBPANEL_FUSED(512, 4, 4)
-    MI32_SUBPANEL_FUSED(1024, 1, 4) MI32_SUBPANEL_FUSED(1024, 2, 4)
-#endif
-#undef MI32_SUBPANEL_CASE
-#undef MI32_SUBPANEL_FUSED
-    return hipErrorInvalidValue;
+    return with_constant<256, 512, 1024>(nt, [&](auto NT) {
+        return with_constant<1, 2, 4, 8, 16>(rpt, [&](auto RPT) {
+            return with_constant<4, 8, 16, 32>(w, [&](auto W) {
+                return with_constant<0, 1>(A.upd_on, [&](auto FUSED) {
+                    return launch_subpanel<NT, RPT, W, FUSED != 0>(A, nwgs, stream);
+                });
+            });
+        });
+    });
 }
 
+// gj_block_strip_kernel's parameters (the block's strips, sub-panels [g_lo, g_hi), for the columns outside the block
+// that lie in [col_lo, col_hi) (inside) / that do not)
+struct BlockStripArgs {
+    const float *src; size_t mstride; int np, ld;
+    const float *mf; size_t mfstride; int mf_ld;
+    float *ub, *xs, *xst; size_t ubstride;
+    int C0, kb;
+    const int *map;
+    int col_lo, col_hi, inside, g_lo, g_hi;
+    const int *guard;
+};
 template <int CT, int G, int SNT>
-static hipError_t launch_block_strip_t(dim3 grid, size_t lds, hipStream_t st, const float *src, size_t mstride, int np, int ld,
-                                       const float *mf, size_t mfstride, int mf_ld, float *ub, float *xs, float *xst,
-                                       size_t ubstride, int C0, int kb, const int *map, int col_lo, int col_hi, int inside,
-                                       int g_lo, int g_hi, const int *guard)
+static hipError_t launch_block_strip_t(const BlockStripArgs &a, int batch, hipStream_t st)
 {
-    static std::once_flag once[64];  // function attributes are per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipError_t e = hipSuccess;
-    std::call_once(once[dev & 63], [&] {
-        e = hipFuncSetAttribute((const void *)gj_block_strip_kernel<CT, G, SNT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)block_strip_lds_bytes<CT, G>(CT == 128 ? 128 : CT == 64 ? 256 : kMaxBW));
-    });
+    const hipError_t e = raise_lds_limit((const void *)gj_block_strip_kernel<CT, G, SNT>,
+                                         block_strip_lds_bytes<CT, G>(CT == 128 ? 128 : CT == 64 ? 256 : kMaxBW));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gj_block_strip_kernel<CT, G, SNT>), grid, dim3(SNT), lds, st, src, mstride, np, ld, mf, mfstride,
-                       mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, col_hi, inside, g_lo, g_hi, guard);
+    const size_t lds = block_strip_lds_bytes<CT, G>(a.kb);
+    hipLaunchKernelGGL((gj_block_strip_kernel<CT, G, SNT>), dim3(a.np / CT, batch), dim3(SNT), lds, st, a.src, a.mstride,
+                       a.np, a.ld, a.mf, a.mfstride, a.mf_ld, a.ub, a.xs, a.xst, a.ubstride, a.C0, a.kb, a.map, a.col_lo,
+                       a.col_hi, a.inside, a.g_lo, a.g_hi, a.guard);
     return hipSuccess;
 }
-// the block's strips, sub-panels [g_lo, g_hi), for the columns outside the block that lie in [col_lo, col_hi) (inside) /
-// that do not
-static hipError_t launch_block_strip(int w, int batch, hipStream_t st, const float *src, size_t mstride, int np, int ld,
-                                     const float *mf, size_t mfstride, int mf_ld, float *ub, float *xs, float *xst,
-                                     size_t ubstride, int C0, int kb, const int *map, int col_lo, int col_hi, int inside,
-                                     int g_lo, int g_hi, const int *guard)
+static hipError_t launch_block_strip(int w, int batch, hipStream_t st, const BlockStripArgs &a)
 {
-#define MI32_STRIP_CASE(GG)                                                                                               \
-    if (w == GG && batch * (np / 64) > 512) {  /* GPU-filling: small workgroups */                                        \
-        if (kb <= 128 && C0 % 128 == 0 && np % 128 == 0)  /* 128 columns: the strip uses all 512 threads */               \
-            return launch_block_strip_t<128, GG, 512>(dim3(np / 128, batch), block_strip_lds_bytes<128, GG>(kb), st, src, mstride, \
-                                                      np, ld, mf, mfstride, mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, \
-                                                      col_hi, inside, g_lo, g_hi, guard);                                 \
-        if (kb <= 256)                                                                                                    \
-            return launch_block_strip_t<64, GG, 512>(dim3(np / 64, batch), block_strip_lds_bytes<64, GG>(kb), st, src, mstride, \
-                                                     np, ld, mf, mfstride, mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, \
-                                                     col_hi, inside, g_lo, g_hi, guard);                                  \
-        return launch_block_strip_t<32, GG, 512>(dim3(np / 32, batch), block_strip_lds_bytes<32, GG>(kb), st, src, mstride, np, \
-                                                 ld, mf, mfstride, mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, col_hi, \
-                                                 inside, g_lo, g_hi, guard);                                              \
-    }                                                                                                                     \
-    if (w == GG) {                                                                                                        \
-        if (kb <= 256)                                                                                                    \
-            return launch_block_strip_t<64, GG, 1024>(dim3(np / 64, batch), block_strip_lds_bytes<64, GG>(kb), st, src, mstride, np, \
-                                                ld, mf, mfstride, mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, col_hi, \
-                                                inside, g_lo, g_hi, guard);                                               \
-        return launch_block_strip_t<32, GG, 1024>(dim3(np / 32, batch), block_strip_lds_bytes<32, GG>(kb), st, src, mstride, np, ld, \
-                                            mf, mfstride, mf_ld, ub, xs, xst, ubstride, C0, kb, map, col_lo, col_hi, inside, \
-                                            g_lo, g_hi, guard);                                                           \
-    }
-    MI32_STRIP_CASE(16) MI32_STRIP_CASE(8) MI32_STRIP_CASE(4) MI32_STRIP_CASE(32)
-#undef MI32_STRIP_CASE
-    return hipErrorInvalidValue;
+    return with_constant<4, 8, 16, 32>(w, [&](auto G) {
+        if (batch * (a.np / 64) > 512) {  // GPU-filling: small workgroups
+            if (a.kb <= 128 && a.C0 % 128 == 0 && a.np % 128 == 0)  // 128 columns: the strip uses all 512 threads
+                return launch_block_strip_t<128, G, 512>(a, batch, st);
+            return a.kb <= 256 ? launch_block_strip_t<64, G, 512>(a, batch, st) : launch_block_strip_t<32, G, 512>(a, batch, st);
+        }
+        return a.kb <= 256 ? launch_block_strip_t<64, G, 1024>(a, batch, st) : launch_block_strip_t<32, G, 1024>(a, batch, st);
+    });
 }
 
 // Look-ahead: the rank-bw update of block b is split into (A) the columns of block b+1, which the next
@@ -2188,8 +2171,6 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
     if (const char *ev = std::getenv("MI32_LOOKAHEAD_MIN")) la_min = std::atoi(ev) > 2048 ? std::atoi(ev) : 2048;
     const bool lookahead = ex.aux != nullptr && ex.n_events >= 4 && ex.aux_workgroups > 0 && batch == 1 && np >= la_min;
     hipError_t e;
-    int fused_rows = 2048;  // see "Fused mode" below; fused instances exist for at most 2048 rows
-    if (const char *ev = std::getenv("MI32_FUSED_ROWS")) fused_rows = std::atoi(ev) < 2048 ? std::atoi(ev) : 2048;
     const PanelExport no_export = {ws.pt[0], ws.pt_bstride, -(1 << 30), 1, 0};
     if (d_status) {  // MI32_OK; the init kernel flags non-finite input, the panels bad pivots and lost partners
         if ((e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream)) != hipSuccess) return e;
@@ -2199,7 +2180,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         // update at all, the second gets the first one's update in its panel's prologue
         ProfScope ps(prof, KC_INIT, stream);
         const PanelExport ex0 = {ws.pt[0], ws.pt_bstride, 0, ex.pivoting ? (int)p.wblk[0] : 16,
-                                 (ex.pivoting && np <= fused_rows) ? 2 : 1};
+                                 (ex.pivoting && np <= kFusedRows) ? 2 : 1};
         hipLaunchKernelGGL(blocked_init_kernel, dim3((np + 255) / 256, (np + 15) / 16, batch), dim3(256), 0, stream,
                            d_a, p.n, np, p.ld, ws.mstride, ws.m0, ex0, ws.tstride, ws.orig, d_status);
     }
@@ -2215,32 +2196,34 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
     // look-ahead half keeps busy although whole CUs are idle (in-block update 12.2 instead of 6.4 us while the half
     // runs).  Where the half is short against the panel phase (up to ~8192 rows) it gets fewer CUs, all to itself.
     const size_t lds_persistent = (ex.aux_exclusive ? 156 : 84) * 1024;
-    {
-        static std::once_flag once[64];  // function attributes are per device; any thread may be the first
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::call_once(once[dev & 63], [] {
-            (void)hipFuncSetAttribute((const void *)gj_rank_bw2_kernel<MI32_BW_BK, MI32_BW_WPS, 128, (MI32_BW_PF != 0)>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)rank_bw2_lds_bytes<MI32_BW_BK>(kMaxBW));
-            (void)hipFuncSetAttribute((const void *)gj_rank_bw2_persistent_kernel<MI32_BW_BK>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-            (void)hipFuncSetAttribute((const void *)gj_panel_multi_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)subpanel_lds_bytes<1024, 4, 16, false>());
-        });
-    }
-    // plans with shared panels: every launch skips a matrix whose panel lost a partner (SubpanelArgs::guard)
-    const int *guard = (p.multi_panel && ex.pivoting) ? d_status : nullptr;
+    if ((e = raise_lds_limit((const void *)gj_rank_bw2_kernel<kBwBK, kBwWPS>, rank_bw2_lds_bytes<kBwBK>(kMaxBW))) != hipSuccess ||
+        (e = raise_lds_limit((const void *)gj_rank_bw2_persistent_kernel<kBwBK>, 156 * 1024)) != hipSuccess ||
+        (e = raise_lds_limit((const void *)gj_panel_multi_kernel<16>, subpanel_lds_bytes<1024, 4, 16, false>())) != hipSuccess)
+        return e;
+    // plans with shared panels (multi-workgroup panels, pivoting only): every launch skips a matrix whose panel lost
+    // a partner (SubpanelArgs::guard)
+    const bool shared_panels = p.multi_panel && ex.pivoting;
+    const int *guard = shared_panels ? d_status : nullptr;
     unsigned panel_launches = 0;  // tags of the multi-workgroup panels' exchange granules: unique per launch
-    if (p.multi_panel) {  // no stale tag of an earlier call may match
+    if (shared_panels) {  // no stale tag of an earlier call may match
         if ((e = hipMemsetAsync(ws.xch, 0, (size_t)kXchGranules * sizeof(unsigned long long) * batch, stream)) != hipSuccess)
             return e;
     }
-    // MI32_STRIP_ONE_LAUNCH=1 (diagnostic): every block's strips in one launch at its end, no strip(t) tiles
-    const char *sol = std::getenv("MI32_STRIP_ONE_LAUNCH");
-    // GPU-filling batches: the strip(t) tiles (256-thread groups, one global round trip per 32 earlier steps) cost
-    // more than the one launch per block (measured 64 x 2048^2: 23.0 vs 21.7 ms)
-    const bool one_launch_strips = !lookahead && ((sol && std::atoi(sol) != 0) || batch * ((np + 63) / 64) > 256);
+    // The strip(t) tiles follow each block sub-panel by sub-panel in the columns outside it -- unless the look-ahead
+    // is on: those columns are then still being written by the previous block's second-stream update while the
+    // block's panels run (the next block's columns too: half (A) of the previous block covered THIS block's), and
+    // the block's strips run in one launch at its end (gj_block_strip_kernel).  So do GPU-filling batches: there the
+    // strip(t) tiles (256-thread groups, one global round trip per 32 earlier steps) cost more than the one launch
+    // per block (measured 64 x 2048^2: 23.0 vs 21.7 ms).
+    const bool strips_at_end = lookahead || batch * ((np + 63) / 64) > 256;
+    // what every sub-panel launch shares
+    SubpanelArgs base = {};
+    base.np = np; base.n = p.n; base.ld = p.ld; base.batch = batch;
+    base.mstride = ws.mstride; base.tstride = ws.tstride;
+    base.mtstride = ws.mtstride; base.mtld = ws.mtld;
+    base.mfstride = ws.mfstride; base.mf_ld = p.bw;
+    base.u_exp = no_export;
+    base.guard = guard;
     float *cur = ws.m0, *oth = ws.m1;
     bool pending_b = false;  // a (B) half is in flight on the second stream
     int blk = 0, ev = 0;
@@ -2257,106 +2240,102 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         // prologue.  It pays while the panel workgroup holds at most 2 rows per lane (measured: 2048^2 3.23 ->
         // 3.06 ms, 1024^2 1.40 -> 1.27 ms); with more rows the prologue (rows x W x W fmaf on ONE CU) costs what
         // the update launch did (4096^2: 8.9 -> 9.5 ms), so those blocks keep panel(s) and update(s) apart.
-        const bool fused = ex.pivoting && (np - C0) <= fused_rows;
-        // The strip(t) tiles follow the block sub-panel by sub-panel in the columns outside it -- unless the look-ahead
-        // is on: those columns are then still being written by the previous block's second-stream update while this
-        // block's panels run (the next block's columns too: half (A) of the previous block covered THIS block's), and
-        // the block's strips run in one launch at its end (gj_block_strip_kernel).
-        const int os_first = 0;
-        const int os_ntiles = (one_launch_strips || lookahead) ? 0 : (np - kb) / 64;
-        const bool strips_at_end = one_launch_strips || lookahead;
+        const bool fused = ex.pivoting && (np - C0) <= kFusedRows;
+        const int os_ntiles = strips_at_end ? 0 : (np - kb) / 64;
         float *x = cur, *y = oth;  // the block's panel columns alternate between the two copies
+        // Each builder fills its own fields of a launch's arguments.  panel(s): sub-panel s's pivot steps.
+        auto panel = [&](SubpanelArgs &A, int s) {
+            A.panel_on = 1;
+            A.c0 = C0 + s * w;
+            A.has_prev = fused && (s > 0);
+            A.c0_prev = A.c0 - w;
+            A.row_lo = A.has_prev ? A.c0_prev : A.c0;  // fused: the W pivot rows of s-1 are needed once more
+            A.first_in_block = (s == 0);
+            A.pt_in = ws.pt[s % 3];
+            A.mt_prev = ws.mt[(s + 1) & 1];
+            A.gt_out = ws.gt[s & 1];
+            A.mt_out = ws.mt[s & 1];
+            A.submap_prev = ws.submap[(s + 1) & 1];
+            A.invsub_prev = ws.invsub[(s + 1) & 1];
+            A.submap_out = ws.submap[s & 1];
+            A.invsub_out = ws.invsub[s & 1];
+            A.rowsrc_in = rsb[fused ? (s + 1) & 1 : 0];
+            A.rowsrc_out = rsb[fused ? s & 1 : 0];
+            A.rowsrc_alt = (fused && s == 0) ? rsb[1] : nullptr;
+            A.orig = ws.orig;
+            A.aux_out = ws.aux[s & 1];
+            A.status = d_status;
+            const int prow = np - A.row_lo;  // rows the panel holds
+            A.ngroups = (shared_panels && prow > kPanelGroupRows) ? (prow + kPanelGroupRows - 1) / kPanelGroupRows : 1;
+            A.xch = ws.xch;
+            A.tag_base = ++panel_launches;
+        };
+        // what the update and the strip tiles of sub-panel t both read
+        auto tile_inputs = [&](SubpanelArgs &A, int t) {
+            A.u_c0 = C0 + t * w;
+            A.C0 = C0; A.kb = kb;
+            A.u_mt = ws.mt[t & 1];
+            A.u_rowsrc = ex.pivoting ? rsb[fused ? t & 1 : 0] : ws.orig;  // no pivoting: no row ever moves
+            A.u_submap = ex.pivoting ? ws.submap[t & 1] : ws.orig;
+            A.u_mf = mf;
+        };
+        // update(t): the columns of the block that are not sub-panel t's own
+        auto update = [&](SubpanelArgs &A, int t) {
+            tile_inputs(A, t);
+            A.upd_on = 1;
+            A.u_has_prev = fused && (t > 0);
+            A.u_above_hi = A.u_has_prev ? A.u_c0 - w : A.u_c0;  // = the first row panel(t) held
+            A.u_panel_hi = ex.pivoting ? np : A.u_c0 + w;
+            A.x = x; A.y = y;
+            A.u_gt = ws.gt[t & 1];
+            A.u_pt_in = ws.pt[t % 3];
+            A.u_aux = ws.aux[t & 1];
+            // fused: sub-panel t+2's columns (t+1's are brought up to date by its own panel);
+            // otherwise sub-panel t+1's, fully up to date
+            const int tx = fused ? t + 2 : t + 1;
+            if (tx < S) A.u_exp = PanelExport{ws.pt[tx % 3], ws.pt_bstride, C0 + tx * w, w, 1};
+        };
+        // strip(t): the columns outside the block; needs panel(t)'s output and the strips before it
+        auto strip = [&](SubpanelArgs &A, int t) {
+            tile_inputs(A, t);
+            A.os_on = 1;
+            A.os_first = 0;
+            A.os_ntiles = os_ntiles;
+            A.os_cur = cur;
+            A.os_ub = ub; A.os_xs = xs; A.ubstride = ws.gkstride;
+        };
         for (int s = 0; s <= S; ++s) {
-            SubpanelArgs P = {};   // the panel half
-            P.np = np; P.n = p.n; P.ld = p.ld; P.batch = batch;
-            P.mstride = ws.mstride; P.tstride = ws.tstride;
-            P.mtstride = ws.mtstride; P.mtld = ws.mtld;
-            P.mfstride = ws.mfstride; P.mf_ld = p.bw;
-            P.u_exp = no_export;
-            P.guard = guard;
-            SubpanelArgs U = P;    // the update half
-            if (s < S) {
-                P.panel_on = 1;
-                P.c0 = C0 + s * w;
-                P.has_prev = fused && (s > 0);
-                P.c0_prev = P.c0 - w;
-                P.row_lo = P.has_prev ? P.c0_prev : P.c0;  // fused: the W pivot rows of s-1 are needed once more
-                P.first_in_block = (s == 0);
-                P.pt_in = ws.pt[s % 3];
-                P.mt_prev = ws.mt[(s + 1) & 1];
-                P.gt_out = ws.gt[s & 1];
-                P.mt_out = ws.mt[s & 1];
-                P.submap_prev = ws.submap[(s + 1) & 1];
-                P.invsub_prev = ws.invsub[(s + 1) & 1];
-                P.submap_out = ws.submap[s & 1];
-                P.invsub_out = ws.invsub[s & 1];
-                if (!ex.pivoting) P.ngroups = 1;
-                P.rowsrc_in = rsb[fused ? (s + 1) & 1 : 0];
-                P.rowsrc_out = rsb[fused ? s & 1 : 0];
-                P.rowsrc_alt = (fused && s == 0) ? rsb[1] : nullptr;
-                P.orig = ws.orig;
-                P.aux_out = ws.aux[s & 1];
-                P.status = d_status;
-                const int prow = np - P.row_lo;  // rows the panel holds
-                P.ngroups = (p.multi_panel && prow > kPanelGroupRows) ? (prow + kPanelGroupRows - 1) / kPanelGroupRows : 1;
-                P.xch = ws.xch;
-                P.tag_base = ++panel_launches;
-            }
-            if (s > 0) {
-                const int t = s - 1;
-                U.upd_on = 1;
-                U.u_c0 = C0 + t * w;
-                U.u_has_prev = fused && (t > 0);
-                U.u_above_hi = U.u_has_prev ? U.u_c0 - w : U.u_c0;  // = the first row panel(t) held
-                U.u_panel_hi = ex.pivoting ? np : U.u_c0 + w;
-                U.C0 = C0; U.kb = kb;
-                U.x = x; U.y = y;
-                U.u_gt = ws.gt[t & 1];
-                U.u_mt = ws.mt[t & 1];
-                U.u_rowsrc = ex.pivoting ? rsb[fused ? t & 1 : 0] : ws.orig;  // no pivoting: no row ever moves
-                U.u_mf = mf;
-                U.u_submap = ex.pivoting ? ws.submap[t & 1] : ws.orig;
-                U.u_pt_in = ws.pt[t % 3];
-                U.u_aux = ws.aux[t & 1];
-                // fused: sub-panel t+2's columns (t+1's are brought up to date by its own panel);
-                // otherwise sub-panel t+1's, fully up to date
-                const int tx = fused ? t + 2 : t + 1;
-                if (tx < S) U.u_exp = PanelExport{ws.pt[tx % 3], ws.pt_bstride, C0 + tx * w, w, 1};
-            }
-            if (s > 0 && os_ntiles > 0) {
-                // strip(s-1) of the columns outside the block: rides in the launch of panel(s) (in the block's last
-                // in-block update for the last sub-panel); it needs panel(s-1)'s output and the strips before it
-                SubpanelArgs &O = (fused || s < S) ? P : U;
-                O.os_on = 1;
-                O.os_first = os_first; O.os_ntiles = os_ntiles;
-                O.os_cur = cur;
-                O.os_ub = ub; O.os_xs = xs; O.ubstride = ws.gkstride;
-                O.u_c0 = U.u_c0; O.C0 = C0; O.kb = kb;
-                O.u_mt = U.u_mt; O.u_submap = U.u_submap; O.u_rowsrc = U.u_rowsrc; O.u_mf = U.u_mf;
-            }
-            if (fused) {
-                SubpanelArgs A = P;  // one launch: panel(s) || update(s-1) || strip(s-1)
-                A.upd_on = U.upd_on; A.u_c0 = U.u_c0; A.u_has_prev = U.u_has_prev; A.u_above_hi = U.u_above_hi;
-                A.u_panel_hi = U.u_panel_hi;
-                A.C0 = U.C0; A.kb = U.kb; A.x = U.x; A.y = U.y; A.u_gt = U.u_gt; A.u_submap = U.u_submap;
-                A.u_mt = U.u_mt; A.u_rowsrc = U.u_rowsrc; A.u_mf = U.u_mf;
-                A.u_pt_in = U.u_pt_in; A.u_aux = U.u_aux; A.u_exp = U.u_exp;
+            const int t = s - 1;
+            // strip(s-1) rides in the launch of panel(s), in the block's last in-block update for the last sub-panel
+            const bool with_strip = s > 0 && os_ntiles > 0;
+            if (fused) {  // one launch: panel(s) || update(s-1) || strip(s-1)
+                SubpanelArgs A = base;
+                if (s < S) panel(A, s);
+                if (s > 0) update(A, t);
+                if (with_strip) strip(A, t);
                 // a fused launch is accounted to the panel while there is one (it is the critical path)
                 ProfScope ps(prof, A.panel_on ? KC_PANEL : KC_UPDATE_IN, stream);
                 if ((e = dispatch_subpanel(p, w, A, stream)) != hipSuccess) return e;
             } else {
-                if (U.upd_on) {  // update(s-1) first: panel(s) reads the columns it exports
+                if (s > 0) {  // update(s-1) first: panel(s) reads the columns it exports
+                    SubpanelArgs U = base;
+                    update(U, t);
+                    if (with_strip && s == S) strip(U, t);
                     ProfScope ps(prof, KC_UPDATE_IN, stream);
                     if ((e = dispatch_subpanel(p, w, U, stream)) != hipSuccess) return e;
                 }
-                if (P.panel_on && !ex.pivoting) {
-                    // the no-pivot variant: the W x W diagonal block alone (+ the strip tiles that ride with a panel)
+                if (s < S) {
+                    SubpanelArgs P = base;
+                    panel(P, s);
+                    if (with_strip) strip(P, t);
                     ProfScope ps(prof, KC_PANEL, stream);
-                    const int os_tiles = P.os_on ? batch * P.os_ntiles : 0;
-                    hipLaunchKernelGGL((gj_diag_panel_kernel<16>), dim3(batch + os_tiles), dim3(256), 0, stream, P);
-                } else if (P.panel_on) {
-                    ProfScope ps(prof, KC_PANEL, stream);
-                    if ((e = dispatch_subpanel(p, w, P, stream)) != hipSuccess) return e;
+                    if (!ex.pivoting) {
+                        // the no-pivot variant: the W x W diagonal block alone (+ the strip tiles that ride with a panel)
+                        const int os_tiles = P.os_on ? batch * P.os_ntiles : 0;
+                        hipLaunchKernelGGL((gj_diag_panel_kernel<16>), dim3(batch + os_tiles), dim3(256), 0, stream, P);
+                    } else if ((e = dispatch_subpanel(p, w, P, stream)) != hipSuccess) {
+                        return e;
+                    }
                 }
             }
             if (s > 0) { float *t2 = x; x = y; y = t2; }
@@ -2370,7 +2349,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
             const int *rowsrc = ex.pivoting ? rsb[fused ? (S - 1) & 1 : 0] : ws.orig;
             // the next block's first two sub-panels, fully updated, for its first two panels
             const PanelExport exn =
-                has_next ? PanelExport{ws.pt[0], ws.pt_bstride, next, w_next, (ex.pivoting && (np - next) <= fused_rows) ? 2 : 1}
+                has_next ? PanelExport{ws.pt[0], ws.pt_bstride, next, w_next, (ex.pivoting && (np - next) <= kFusedRows) ? 2 : 1}
                          : no_export;
             const int copy = (x != oth) ? 1 : 0;
             if (pending_b) {  // this update reads all of `cur` and overwrites `oth`: the previous (B) must be done
@@ -2383,15 +2362,16 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                 hipLaunchKernelGGL(gj_mult_transpose_kernel, dim3(np / 64, kb / 64, batch), dim3(256), 0, st, mf,
                                    ws.mfstride, p.bw, np, rowsrc, ws.gk, ws.gkstride, C0, kb, w, guard);
             };
+            // the block's strips in one launch, for the columns outside it in [col_lo, col_hi) (inside) / not in it
+            auto launch_strips = [&](hipStream_t st, int col_lo, int col_hi, int inside) {
+                ProfScope ps(prof, KC_TRANSPOSE, st);
+                const BlockStripArgs a = {cur, ws.mstride, np, p.ld, mf, ws.mfstride, p.bw, ub, xs, ws.xst, ws.gkstride,
+                                          C0, kb, rowsrc, col_lo, col_hi, inside, 0, S, guard};
+                return launch_block_strip(w, batch, st, a);
+            };
             if (split_update) {
                 {   // (A): the next block's columns, on the main stream; exports the next sub-panels
-                    {
-                        ProfScope ps(prof, KC_TRANSPOSE, stream);
-                        if ((e = launch_block_strip(w, batch, stream, cur, ws.mstride, np, p.ld, mf, ws.mfstride, p.bw, ub, xs,
-                                                    ws.xst, ws.gkstride, C0, kb, rowsrc, next, next + kb_next, 1, 0, S,
-                                                    guard)) != hipSuccess)
-                            return e;
-                    }
+                    if ((e = launch_strips(stream, next, next + kb_next, 1)) != hipSuccess) return e;
                     ProfScope ps(prof, KC_UPDATE_OUT, stream);
                     // small tiles: only kb_next columns, so 64x64 gives 4x the workgroups of 128x128
                     hipLaunchKernelGGL((gj_rank_update_kernel<32>), dim3(kb_next / 64, np / 64, batch), dim3(256), 0,
@@ -2403,19 +2383,14 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                 hipEvent_t e_panel = ex.events[ex.n_events / 2 + ev];
                 if ((e = hipEventRecord(e_panel, stream)) != hipSuccess) return e;
                 if ((e = hipStreamWaitEvent(ex.aux, e_panel, 0)) != hipSuccess) return e;
-                {   // the strips of every column the strip(t) tiles could not follow
-                    ProfScope ps(prof, KC_TRANSPOSE, ex.aux);
-                    if ((e = launch_block_strip(w, batch, ex.aux, cur, ws.mstride, np, p.ld, mf, ws.mfstride, p.bw, ub, xs,
-                                                ws.xst, ws.gkstride, C0, kb, rowsrc, next, next + kb_next, 0, 0, S,
-                                                guard)) != hipSuccess)
-                        return e;
-                }
+                // the strips of every column the strip(t) tiles could not follow
+                if ((e = launch_strips(ex.aux, next, next + kb_next, 0)) != hipSuccess) return e;
                 launch_transpose(ex.aux);  // only half (B) reads the transposed multipliers: off the main stream
                 {
                     ProfScope ps(prof, KC_UPDATE_OUT, ex.aux);
                     // persistent flavour: aux_workgroups (< number of CUs) workgroups, with so much dynamic LDS
                     // that one CU holds at most one of them -> the remaining CUs stay free for the main stream
-                    hipLaunchKernelGGL((gj_rank_bw2_persistent_kernel<MI32_BW_BK>), dim3(ex.aux_workgroups, batch),
+                    hipLaunchKernelGGL((gj_rank_bw2_persistent_kernel<kBwBK>), dim3(ex.aux_workgroups, batch),
                                        dim3(256), lds_persistent, ex.aux, cur, oth, x, ws.mstride, ws.gk, ws.gkstride, ub, xs, np,
                                        p.ld, ws.mstride, C0, kb, rowsrc, copy, no_export, ws.tstride, next,
                                        next + kb_next, guard);
@@ -2424,15 +2399,12 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                 pending_b = true;
             } else {
                 if (strips_at_end) {  // no strip(t) tiles ran
-                    ProfScope ps(prof, KC_TRANSPOSE, stream);
-                    if ((e = launch_block_strip(w, batch, stream, cur, ws.mstride, np, p.ld, mf, ws.mfstride, p.bw, ub, xs,
-                                                ws.xst, ws.gkstride, C0, kb, rowsrc, 0, 0, 0, 0, S, guard)) != hipSuccess)
-                        return e;
+                    if ((e = launch_strips(stream, 0, 0, 0)) != hipSuccess) return e;
                 }
                 launch_transpose(stream);
                 ProfScope ps(prof, KC_UPDATE_OUT, stream);
-                hipLaunchKernelGGL((gj_rank_bw2_kernel<MI32_BW_BK, MI32_BW_WPS, 128, (MI32_BW_PF != 0)>), dim3((np / 128) * (np / 128), batch),
-                                   dim3(256), rank_bw2_lds_bytes<MI32_BW_BK>(kb), stream, cur, oth, x, ws.mstride, ws.gk,
+                hipLaunchKernelGGL((gj_rank_bw2_kernel<kBwBK, kBwWPS>), dim3((np / 128) * (np / 128), batch),
+                                   dim3(256), rank_bw2_lds_bytes<kBwBK>(kb), stream, cur, oth, x, ws.mstride, ws.gk,
                                    ws.gkstride, ub, xs, np, p.ld, ws.mstride, C0, kb, rowsrc, copy, exn, ws.tstride, 0, 0, guard);
             }
             float *t = cur; cur = oth; oth = t;

@@ -21,8 +21,6 @@
 // Working matrix: the N x N in-place form padded with an identity block to a multiple of 64 (no bounds checks in the
 // tiles: inv(diag(A, I)) = diag(inv(A), I); a real column never takes its pivot from the padding, whose entries
 // in real columns are exact zeros).
-#include <cstdlib>
-
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -48,10 +46,6 @@ Blocked64Plan make_blocked64_plan(int n, int bw)
     p.np = ((n + bw - 1) / bw) * bw;
     p.ld = p.np;
     p.tr = (p.np <= 4096) ? 8 : 32;
-    if (const char *e = std::getenv("MI32_B64_TR")) {  // experiments
-        const int v = std::atoi(e);
-        if (v == 8 || v == 16 || v == 32) p.tr = v;
-    }
     p.row_tiles = (p.np + p.tr - 1) / p.tr;
     return p;
 }

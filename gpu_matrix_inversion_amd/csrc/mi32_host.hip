@@ -283,7 +283,6 @@ static int env_int(const char *name, int dflt)
 //   (two or three look-ahead workgroups per CU, 76 / 50 KB each: 8192 37.7, 12288 77.8, 16384 143-145: the shared panels starve)
 // Up to ~7168 rows the half is short against the panel phase: it gets few CUs, all to itself, and the panel chain
 // keeps the rest undisturbed; above, every block waits for the half: it gets all but 32 / 16 CUs and shares them.
-// MI32_RESERVED_CUS / MI32_LA_EXCLUSIVE override.
 static void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive)
 {
     int reserve;
@@ -292,12 +291,8 @@ static void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive)
     else if (n <= 7168) { reserve = cus / 4; excl = true; }
     else if (n <= 14336) { reserve = cus / 8; excl = false; }
     else { reserve = cus / 32; excl = false; }
-    const int r_env = env_int("MI32_RESERVED_CUS", 0);
-    if (r_env > 0) reserve = r_env;
     if (reserve < 1) reserve = 1;
     if (reserve > cus - 1) reserve = cus - 1;
-    const int x_env = env_int("MI32_LA_EXCLUSIVE", -1);
-    if (x_env >= 0) excl = x_env != 0;
     *workgroups = cus - reserve;
     *exclusive = excl;
 }
@@ -416,7 +411,7 @@ int mi32_create(mi32_handle_t *out, int device)
     if (env_int("MI32_LOOKAHEAD", 1)) {
         // Look-ahead (see blocked_invert): the half of each rank-bw update that is not on the critical
         // path runs on a second stream as a persistent kernel with one workgroup per CU on all but
-        // MI32_RESERVED_CUS compute units, which stay free for the panel / in-block kernels.
+        // the compute units lookahead_geometry reserves, which stay free for the panel / in-block kernels.
         // (Tried and rejected on MI355X: a plain second stream -- its workgroups fill every CU's register
         // file and the critical-path kernels queue behind them; hipExtStreamCreateWithCUMask -- it
         // serialises the two queues, 17 ms instead of 11.5.)
@@ -559,7 +554,7 @@ int mi32_reserve(mi32_handle_t h, int n, int batch)
 // result does not depend on the split; mi32_set_lookahead(h, 0) turns the second stream off altogether.
 static bool split_batch(const mi32_context *h, int algo, int n, int batch)
 {
-    return algo == MI32_ALGO_BLOCKED && h->lookahead && h->split_stream != nullptr && batch >= env_int("MI32_BATCH_SPLIT_MIN", 4) &&
+    return algo == MI32_ALGO_BLOCKED && h->lookahead && h->split_stream != nullptr && batch >= 4 &&
            (double)batch * n * n >= 64.0 * 1024.0 * 1024.0 && env_int("MI32_BATCH_SPLIT", 1) != 0;
 }
 

@@ -119,9 +119,8 @@ __device__ unsigned long long *g_rb_stamps;  // [workgroup][8]
 // rb_smem: rank_bw2_lds_bytes<BK, BN>(kdim) bytes of LDS.
 // The accumulators START from the old values C (row-mapped), so that every element goes through one fmaf chain from
 // its old value, k ascending -- the reference's own operation order (mat_inv_32.cpp:28-38).  The old values are
-// requested before the first operand stage, so both travel together.  (PF is kept as a template parameter for the
-// call sites; round 2 fetched the old values under the last k-tiles, which the order from the old value rules out.)
-template <int BK, int BN = 128, bool PF = false>
+// requested before the first operand stage, so both travel together.
+template <int BK, int BN = 128>
 __device__ __forceinline__ void rank_bw2_tile(
     const float *__restrict__ src_all, float *__restrict__ dst_all, const float *__restrict__ g_all, size_t gstride,
     const float *__restrict__ gk_all, size_t gkstride, const float *__restrict__ ub_all, const float *__restrict__ xs_all,
@@ -298,7 +297,7 @@ __device__ __forceinline__ void rank_bw2_tile(
 #endif
 }
 
-template <int BK, int WPS, int BN = 128, bool PF = false>
+template <int BK, int WPS, int BN = 128>
 __global__ __launch_bounds__(256, WPS) void gj_rank_bw2_kernel(
     const float *__restrict__ src_all, float *__restrict__ dst_all, const float *__restrict__ g_all, size_t gstride,
     const float *__restrict__ gk_all, size_t gkstride, const float *__restrict__ ub_all, const float *__restrict__ xs_all,
@@ -309,8 +308,8 @@ __global__ __launch_bounds__(256, WPS) void gj_rank_bw2_kernel(
     if (guard != nullptr && __builtin_amdgcn_readfirstlane(guard[blockIdx.y]) == MI32_RUNTIME_ERROR) return;  // given up
     int rt, ct;
     rb_tile_of(blockIdx.x, np / 128, np / BN, rb_strip_width(kdim, BN), rt, ct);
-    rank_bw2_tile<BK, BN, PF>(src_all, dst_all, g_all, gstride, gk_all, gkstride, ub_all, xs_all, np, ld, mstride, c0, kdim,
-                              map_all, copy_panel, ex, tstride, skip_lo, skip_hi, blockIdx.y, rt, ct, rb_smem);
+    rank_bw2_tile<BK, BN>(src_all, dst_all, g_all, gstride, gk_all, gkstride, ub_all, xs_all, np, ld, mstride, c0, kdim,
+                          map_all, copy_panel, ex, tstride, skip_lo, skip_hi, blockIdx.y, rt, ct, rb_smem);
 }
 
 // Persistent, residency-limited flavour for the look-ahead half (see blocked_invert): gridDim.x workgroups
@@ -318,7 +317,7 @@ __global__ __launch_bounds__(256, WPS) void gj_rank_bw2_kernel(
 // fewer workgroups than CUs, so a known number of CUs stays entirely free for the critical-path kernels
 // of the main stream (the panel kernel needs a whole CU); stream priorities cannot give that guarantee
 // and a CU mask serialises the queues.
-template <int BK, bool PF = false>
+template <int BK>
 __global__ __launch_bounds__(256, 1) void gj_rank_bw2_persistent_kernel(
     const float *__restrict__ src_all, float *__restrict__ dst_all, const float *__restrict__ g_all, size_t gstride,
     const float *__restrict__ gk_all, size_t gkstride, const float *__restrict__ ub_all, const float *__restrict__ xs_all,
@@ -331,8 +330,8 @@ __global__ __launch_bounds__(256, 1) void gj_rank_bw2_persistent_kernel(
     for (int id = blockIdx.x; id < T * T; id += gridDim.x) {
         int rt, ct;
         rb_tile_of(id, T, T, rb_strip_width(kdim, 128), rt, ct);
-        rank_bw2_tile<BK, 128, PF>(src_all, dst_all, g_all, gstride, gk_all, gkstride, ub_all, xs_all, np, ld, mstride, c0,
-                                   kdim, map_all, copy_panel, ex, tstride, skip_lo, skip_hi, blockIdx.y, rt, ct, rb_smem);
+        rank_bw2_tile<BK, 128>(src_all, dst_all, g_all, gstride, gk_all, gkstride, ub_all, xs_all, np, ld, mstride, c0,
+                               kdim, map_all, copy_panel, ex, tstride, skip_lo, skip_hi, blockIdx.y, rt, ct, rb_smem);
         __syncthreads();  // the next tile re-uses the LDS buffers and maps
     }
 }

@@ -992,10 +992,11 @@ def test_no_pivot_variant_bit_identical_to_oracle(oracle, n):
     assert g.matrix_inversion_no_pivots(a64.reshape(-1), n + 1).size == 0   # the shape guards
 
 
-def test_no_pivot_blocked_4096_bit_identical_and_timed(oracle):
-    """The no-pivot variant (matrix_inversion_no_pivots.cpp:10) in fp32 at N = 4096 through the blocked path -- with the
-    look-ahead and without -- against the oracle's step-by-step no-pivot restatement, and how long it takes next to
-    the sweep kernels (one launch per pivot step)."""
+def test_no_pivot_blocked_4096_bit_identical_and_timed(oracle, monkeypatch):
+    """The no-pivot variant (matrix_inversion_no_pivots.cpp:10) in fp32 at N = 4096 through the blocked path -- the
+    look-ahead schedule (forced on: MI32_LOOKAHEAD_MIN, its default starts above 4096 rows) against the oracle's
+    step-by-step no-pivot restatement, the single-stream schedule bit for bit the same -- and how long the look-ahead
+    schedule takes next to the sweep kernels (one launch per pivot step)."""
     import time
 
     n = 4096
@@ -1003,6 +1004,7 @@ def test_no_pivot_blocked_4096_bit_identical_and_timed(oracle):
     want = oracle.matrix_inversion_no_pivots(a, n)
     ta = torch.from_numpy(a).cuda()
     times = {}
+    monkeypatch.setenv("MI32_LOOKAHEAD_MIN", "2048")   # read per call; the sweep kernels ignore it
     for algo in ("blocked", "sweep"):
         inv = g.Inverter(algo=algo, pivoting=False)
         try:
@@ -1024,6 +1026,40 @@ def test_no_pivot_blocked_4096_bit_identical_and_timed(oracle):
             inv.close()
     print(f"no-pivot fp32 N=4096: blocked {times['blocked']:.2f} ms, sweep {times['sweep']:.2f} ms")
     assert times["blocked"] < times["sweep"]
+
+
+def test_no_pivot_blocked_4300_lookahead_and_shared_panel_plan_bit_identical_to_oracle(oracle):
+    """The fp32 no-pivot blocked path above 4096 padded rows (4300 -> 4352): the default plan there has the look-ahead
+    on and the multi-workgroup-panel flag set (which the no-pivot variant, without a panel search, must ignore) --
+    bit-identical to the oracle's no-pivot restatement."""
+    n = 4300
+    a = _dominant(n, 4300, np.float32)
+    inv = g.Inverter(algo="auto", pivoting=False)
+    try:
+        assert inv.resolved_algo(n, 1) == g.ALGO_BLOCKED
+        x, st = inv.inv(torch.from_numpy(a).cuda())
+        torch.cuda.synchronize()
+    finally:
+        inv.close()
+    assert int(st[0]) == 0
+    assert np.array_equal(x.cpu().numpy().reshape(-1), oracle.matrix_inversion_no_pivots(a, n))
+
+
+def test_no_pivot_blocked_batch_bit_identical_to_oracle(oracle):
+    """A small fp32 no-pivot batch (3 x 1000) through the blocked path: every member bit-identical to the oracle's
+    no-pivot restatement of it alone."""
+    n, B = 1000, 3
+    mats = np.stack([_dominant(n, 9000 + b, np.float32) for b in range(B)])
+    inv = g.Inverter(algo="auto", pivoting=False)
+    try:
+        assert inv.resolved_algo(n, B) == g.ALGO_BLOCKED
+        x, st = inv.inv(torch.from_numpy(mats).cuda())
+        torch.cuda.synchronize()
+    finally:
+        inv.close()
+    assert st.tolist() == [0] * B
+    for b in range(B):
+        assert np.array_equal(x[b].cpu().numpy().reshape(-1), oracle.matrix_inversion_no_pivots(mats[b], n)), b
 
 
 def test_bench_py_contract_line():

@@ -1,6 +1,6 @@
 """Where does the blocked HIP path differ from the reference-order oracle?  (debug aid, GPU box)
 
-    python tools/exact_debug.py [n ...]      env: MI32_FUSED_ROWS=0 (no fused launches), LOOKAHEAD=0
+    python tools/exact_debug.py [n ...]      env: LOOKAHEAD=0 (no second stream), MI32_PANEL_W / MI32_BLOCK_W
 Prints, per size and distribution, the number of differing entries and the bounding box / first rows and
 columns of the differences, which localises a bug to a block, a sub-panel or a row class.
 """

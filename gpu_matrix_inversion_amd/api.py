@@ -31,6 +31,32 @@ def _algo_id(algo) -> int:
     return int(algo)
 
 
+def _call_flat(sym: str, matrix_vector, matrix_order: int, dtype, *extra):
+    """``(rc, flat output)`` of the C entry point ``sym(vec, len, N, out, *extra)`` on a flat row-major ``dtype``
+    copy of the input; None for a bad shape: ``N <= 0`` or ``int(len/N) != N`` (mat_inv_32.cpp:206-215)."""
+    lib = _lib.load()
+    n = int(matrix_order)
+    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=dtype).reshape(-1))
+    if n <= 0 or int(v.size // n) != n:
+        return None
+    out = np.empty(n * n, dtype=dtype)
+    ptr = ctypes.POINTER(np.ctypeslib.as_ctypes_type(dtype))
+    rc = getattr(lib, sym)(v.ctypes.data_as(ptr), v.size, n, out.ctypes.data_as(ptr), *extra)
+    if rc == _lib.MI32_RUNTIME_ERROR:
+        raise Mi32Error(lib.mi32_last_error().decode())
+    return rc, out
+
+
+def _invert_flat(sym: str, matrix_vector, matrix_order: int, dtype) -> np.ndarray:
+    """The flat inverse, or an empty array where the reference returns an empty vector: a bad shape, or a singular
+    input (README.md:54; ``MI32_SINGULAR_KEEP=1`` returns the shipped library's inf/NaN result instead)."""
+    r = _call_flat(sym, matrix_vector, matrix_order, dtype)
+    keep = os.environ.get("MI32_SINGULAR_KEEP", "0") not in ("", "0")
+    if r is not None and (r[0] == MI32_OK or (r[0] == MI32_SINGULAR and keep)):
+        return r[1]
+    return np.empty(0, dtype=dtype)
+
+
 def matrix_inv_32(matrix_vector, matrix_order: int) -> np.ndarray:
     """Drop-in for ``matrix_inv_32(std::vector<float>, int)``.
 
@@ -39,62 +65,20 @@ def matrix_inv_32(matrix_vector, matrix_order: int) -> np.ndarray:
     ``int(len/N) != N`` (mat_inv_32.cpp:206-215), or a singular input (README.md:54;
     set ``MI32_SINGULAR_KEEP=1`` to get the shipped library's inf/NaN result instead).
     """
-    lib = _lib.load()
-    n = int(matrix_order)
-    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=np.float32).reshape(-1))
-    if n <= 0 or int(v.size // n) != n:
-        return np.empty(0, dtype=np.float32)
-    out = np.empty(n * n, dtype=np.float32)
-    fp = ctypes.POINTER(ctypes.c_float)
-    rc = lib.mi32_matrix_inv_32(v.ctypes.data_as(fp), v.size, n, out.ctypes.data_as(fp))
-    if rc == MI32_OK:
-        return out
-    if rc == MI32_SINGULAR:
-        return out if os.environ.get("MI32_SINGULAR_KEEP", "0") not in ("", "0") else np.empty(0, dtype=np.float32)
-    if rc == _lib.MI32_RUNTIME_ERROR:
-        raise Mi32Error(lib.mi32_last_error().decode())
-    return np.empty(0, dtype=np.float32)
+    return _invert_flat("mi32_matrix_inv_32", matrix_vector, matrix_order, np.float32)
 
 
 def matrix_inv_64(matrix_vector, matrix_order: int) -> np.ndarray:
     """Drop-in for the reference's ``matrix_inversion_FP64(std::vector<double>, int)`` (headers.h:9): flat
     row-major float64 in, flat inverse out, empty array for a bad shape or a singular input."""
-    lib = _lib.load()
-    n = int(matrix_order)
-    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=np.float64).reshape(-1))
-    if n <= 0 or int(v.size // n) != n:
-        return np.empty(0, dtype=np.float64)
-    out = np.empty(n * n, dtype=np.float64)
-    dp = ctypes.POINTER(ctypes.c_double)
-    rc = lib.mi32_matrix_inv_64(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp))
-    if rc == MI32_OK:
-        return out
-    if rc == MI32_SINGULAR:
-        return out if os.environ.get("MI32_SINGULAR_KEEP", "0") not in ("", "0") else np.empty(0, dtype=np.float64)
-    if rc == _lib.MI32_RUNTIME_ERROR:
-        raise Mi32Error(lib.mi32_last_error().decode())
-    return np.empty(0, dtype=np.float64)
+    return _invert_flat("mi32_matrix_inv_64", matrix_vector, matrix_order, np.float64)
 
 
 def matrix_inversion_no_pivots(matrix_vector, matrix_order: int) -> np.ndarray:
     """Drop-in for the reference's ``matrix_inversion_no_pivots(std::vector<double>, int)`` (headers.h:11,
     matrix_inversion_no_pivots.cpp:10): Gauss-Jordan in double with the diagonal entry as every step's pivot --
     for diagonally dominant inputs.  Empty array for a bad shape or when a zero diagonal entry is met."""
-    lib = _lib.load()
-    n = int(matrix_order)
-    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=np.float64).reshape(-1))
-    if n <= 0 or int(v.size // n) != n:
-        return np.empty(0, dtype=np.float64)
-    out = np.empty(n * n, dtype=np.float64)
-    dp = ctypes.POINTER(ctypes.c_double)
-    rc = lib.mi32_matrix_inversion_no_pivots(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp))
-    if rc == MI32_OK:
-        return out
-    if rc == MI32_SINGULAR:
-        return out if os.environ.get("MI32_SINGULAR_KEEP", "0") not in ("", "0") else np.empty(0, dtype=np.float64)
-    if rc == _lib.MI32_RUNTIME_ERROR:
-        raise Mi32Error(lib.mi32_last_error().decode())
-    return np.empty(0, dtype=np.float64)
+    return _invert_flat("mi32_matrix_inversion_no_pivots", matrix_vector, matrix_order, np.float64)
 
 
 def matrix_inv_32_batched(a: np.ndarray, ngpus: int = 1):
@@ -122,43 +106,26 @@ def matrix_inv_32_batched(a: np.ndarray, ngpus: int = 1):
     return out, st
 
 
+def _bench(sym: str, matrix_vector, matrix_order: int, dtype, *extra):
+    """``(inverse, times)``; ``(empty, {})`` where the reference returns an empty Res."""
+    times = (ctypes.c_double * 10)()
+    r = _call_flat(sym, matrix_vector, matrix_order, dtype, times, *extra)
+    if r is None or r[0] != MI32_OK:
+        return np.empty(0, dtype=dtype), {}
+    return r[1], dict(zip(_lib.TIMES10_SLOTS, (float(t) for t in times)))
+
+
 def fp32_bench(matrix_vector, matrix_order: int):
     """The reference's ``Res FP32_bench(vector<float>, int)`` (FP32_bench.cpp:11): returns ``(inverse, times)``
     with ``times`` the ten durations of FP32_bench.cpp:256-443 in seconds, keyed by ``_lib.TIMES10_SLOTS``
     (queue, buffers, build, makeAug, pivot, row, column, compute, getInverted, total); ``(empty, {})`` where the
     reference returns an empty Res."""
-    lib = _lib.load()
-    n = int(matrix_order)
-    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=np.float32).reshape(-1))
-    if n <= 0 or int(v.size // n) != n:
-        return np.empty(0, dtype=np.float32), {}
-    out = np.empty(n * n, dtype=np.float32)
-    times = (ctypes.c_double * 10)()
-    fp = ctypes.POINTER(ctypes.c_float)
-    rc = lib.mi32_bench_32(v.ctypes.data_as(fp), v.size, n, out.ctypes.data_as(fp), times)
-    if rc == _lib.MI32_RUNTIME_ERROR:
-        raise Mi32Error(lib.mi32_last_error().decode())
-    if rc != MI32_OK:
-        return np.empty(0, dtype=np.float32), {}
-    return out, dict(zip(_lib.TIMES10_SLOTS, (float(t) for t in times)))
+    return _bench("mi32_bench_32", matrix_vector, matrix_order, np.float32)
 
 
 def fp64_bench(matrix_vector, matrix_order: int, pivoting: bool = True):
     """``Res FP64_bench`` / ``Res no_pivots_bench`` of the reference (headers.h:14,16): ``(inverse float64, times)``."""
-    lib = _lib.load()
-    n = int(matrix_order)
-    v = np.ascontiguousarray(np.asarray(matrix_vector, dtype=np.float64).reshape(-1))
-    if n <= 0 or int(v.size // n) != n:
-        return np.empty(0, dtype=np.float64), {}
-    out = np.empty(n * n, dtype=np.float64)
-    times = (ctypes.c_double * 10)()
-    dp = ctypes.POINTER(ctypes.c_double)
-    rc = lib.mi32_bench_64(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp), times, 1 if pivoting else 0)
-    if rc == _lib.MI32_RUNTIME_ERROR:
-        raise Mi32Error(lib.mi32_last_error().decode())
-    if rc != MI32_OK:
-        return np.empty(0, dtype=np.float64), {}
-    return out, dict(zip(_lib.TIMES10_SLOTS, (float(t) for t in times)))
+    return _bench("mi32_bench_64", matrix_vector, matrix_order, np.float64, 1 if pivoting else 0)
 
 
 def matrix_multiply(matrice_a, matrice_b) -> float:

@@ -153,7 +153,6 @@ BlockedPlan make_blocked_plan(int n, int w, int bw, int batch)
 static_assert(16384ull * (16384 + 64) * sizeof(float) < (1ull << 32), "a working copy must stay below 4 GiB");
 bool blocked_supported(int n) { return n > 0 && ((n + 127) & ~127) <= 16384; }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct BlockedWs {
     float *m0, *m1;     // the two working copies, np x ld each
     float *pt[3];       // compact transposed panel inputs, kMaxW x np each: sub-panel s of a block uses pt[s % 3]
@@ -183,7 +182,7 @@ struct BlockedWs {
     size_t pt_bstride;  // floats between pt[i] and pt[i + 1]
 };
 static constexpr int kAuxFloats = 2 * kMaxW * kMaxW;
-static size_t blocked_carve(const BlockedPlan &p, int batch, void *base, BlockedWs *o)
+static size_t blocked_carve(const BlockedPlan &p, int batch, void *base, BlockedWs &o)
 {
     const size_t mbytes = align256((size_t)p.np * p.ld * sizeof(float));
     const size_t tbytes = align256((size_t)kMaxW * p.np * sizeof(float));
@@ -191,71 +190,38 @@ static size_t blocked_carve(const BlockedPlan &p, int batch, void *base, Blocked
     const size_t abytes = align256((size_t)kAuxFloats * sizeof(float) * batch);
     const int mtld = 2 * p.np + 256;  // row_lo + NT * RPT <= 2 np + 256 for every panel geometry
     const size_t mtbytes = align256((size_t)kMaxW * mtld * sizeof(float));
-    char *c = (char *)base;
-    size_t off = 0;
-    if (o) {
-        o->m0 = (float *)(c + off);
-        o->mstride = mbytes / sizeof(float);
-        o->tstride = tbytes / sizeof(float);
-        o->pt_bstride = tbytes * batch / sizeof(float);
-        o->mtstride = mtbytes / sizeof(float);
-        o->mtld = mtld;
-    }
-    off += mbytes * batch;
-    if (o) o->m1 = (float *)(c + off);
-    off += mbytes * batch;
-    for (int i = 0; i < 3; ++i) {
-        if (o) o->pt[i] = (float *)(c + off);
-        off += tbytes * batch;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (o) o->gt[i] = (float *)(c + off);
-        off += tbytes * batch;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (o) o->mt[i] = (float *)(c + off);
-        off += mtbytes * batch;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (o) o->aux[i] = (float *)(c + off);
-        off += abytes;
-    }
-    if (o) o->xch = (unsigned long long *)(c + off);
-    off += align256((size_t)kXchGranules * sizeof(unsigned long long) * batch);
     const size_t gkbytes = align256((size_t)(p.bw < kMaxBW ? p.bw : kMaxBW) * p.np * sizeof(float));
-    if (o) { o->gk = (float *)(c + off); o->gkstride = gkbytes / sizeof(float); }
-    off += gkbytes * batch;
-    for (int i = 0; i < 2; ++i) {
-        if (o) o->ub[i] = (float *)(c + off);
-        off += gkbytes * batch;
-        if (o) o->xs[i] = (float *)(c + off);
-        off += gkbytes * batch;
-    }
-    if (o) o->xst = (float *)(c + off);
-    off += gkbytes * batch;
     const size_t mfbytes = align256((size_t)p.np * p.bw * sizeof(float));
-    if (o) o->mfstride = mfbytes / sizeof(float);
+    o.mstride = mbytes / sizeof(float);
+    o.tstride = tbytes / sizeof(float);
+    o.pt_bstride = tbytes * batch / sizeof(float);
+    o.mtstride = mtbytes / sizeof(float);
+    o.mtld = mtld;
+    o.gkstride = gkbytes / sizeof(float);
+    o.mfstride = mfbytes / sizeof(float);
+    WsCarver c(base);
+    o.m0 = c.take<float>(mbytes * batch);
+    o.m1 = c.take<float>(mbytes * batch);
+    for (auto &r : o.pt) r = c.take<float>(tbytes * batch);
+    for (auto &r : o.gt) r = c.take<float>(tbytes * batch);
+    for (auto &r : o.mt) r = c.take<float>(mtbytes * batch);
+    for (auto &r : o.aux) r = c.take<float>(abytes);
+    o.xch = c.take<unsigned long long>(align256((size_t)kXchGranules * sizeof(unsigned long long) * batch));
+    o.gk = c.take<float>(gkbytes * batch);
     for (int i = 0; i < 2; ++i) {
-        if (o) o->mf[i] = (float *)(c + off);
-        off += mfbytes * batch;
+        o.ub[i] = c.take<float>(gkbytes * batch);
+        o.xs[i] = c.take<float>(gkbytes * batch);
     }
-    int **maps[10] = {o ? &o->submap[0] : nullptr, o ? &o->submap[1] : nullptr, o ? &o->invsub[0] : nullptr,
-                      o ? &o->invsub[1] : nullptr, o ? &o->rowsrc[0] : nullptr, o ? &o->rowsrc[1] : nullptr,
-                      o ? &o->rowsrc[2] : nullptr, o ? &o->rowsrc[3] : nullptr,
-                      o ? &o->orig : nullptr,      o ? &o->invp : nullptr};
-    for (int i = 0; i < 10; ++i) {
-        if (o) *maps[i] = (int *)(c + off);
-        off += ibytes;
-    }
-    return off;
+    o.xst = c.take<float>(gkbytes * batch);
+    for (auto &r : o.mf) r = c.take<float>(mfbytes * batch);
+    for (auto &r : o.submap) r = c.take<int>(ibytes);
+    for (auto &r : o.invsub) r = c.take<int>(ibytes);
+    for (auto &r : o.rowsrc) r = c.take<int>(ibytes);
+    o.orig = c.take<int>(ibytes);
+    o.invp = c.take<int>(ibytes);
+    return c.off;
 }
-size_t blocked_workspace_bytes(const BlockedPlan &p, int batch) { return blocked_carve(p, batch, nullptr, nullptr); }
-
-// Shared panels only: true when matrix b was given up (see SubpanelArgs::guard).  Wave-uniform.
-__device__ __forceinline__ bool matrix_given_up(const int *guard, int b)
-{
-    return guard != nullptr && __builtin_amdgcn_readfirstlane(guard[b]) == MI32_RUNTIME_ERROR;
-}
+size_t blocked_workspace_bytes(const BlockedPlan &p, int batch) { BlockedWs ws; return blocked_carve(p, batch, nullptr, ws); }
 
 // ---- init: A -> diag(A, I) in the first working copy (makeAugmentedMatrix counterpart,
 //      mat_inv_32.cpp:177-192) + the compact copies of the first two sub-panels' columns ------
@@ -1969,14 +1935,6 @@ __global__ __launch_bounds__(256) void gj_rank_update_kernel(const float *__rest
 }
 
 // ---- getInvertedMatrix counterpart: undo the column permutation ----------------
-__global__ void invert_perm_ld_kernel(const int *__restrict__ orig, int *__restrict__ invp, int n, int istride,
-                                      const int *__restrict__ guard)
-{
-    const int b = blockIdx.y;
-    if (matrix_given_up(guard, b)) return;
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < n) invp[(size_t)b * istride + orig[(size_t)b * istride + c]] = c;
-}
 // Whole rows go through LDS: the global read (all np columns of R rows) and the global write (n columns)
 // are both coalesced; the column gather happens inside LDS.  (A direct gather from global memory read
 // 4 scattered bytes per lane: 1.35 ms for 64 x 2048^2, i.e. 1.5 TB/s.)
@@ -2157,7 +2115,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                           const BlockedExec &ex)
 {
     BlockedWs ws;
-    blocked_carve(p, batch, wsp, &ws);
+    blocked_carve(p, batch, wsp, ws);
     const int np = p.np;
     hipStream_t stream = ex.stream;
     Profiler *prof = ex.prof;
@@ -2417,8 +2375,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
     }
     ProfScope ps(prof, KC_FINISH, stream);
     // over ALL np entries: orig is a permutation of [0, np), so every invp[j] is defined and in range
-    hipLaunchKernelGGL(invert_perm_ld_kernel, dim3((np + 255) / 256, batch), dim3(256), 0, stream, ws.orig, ws.invp,
-                       np, np, guard);
+    launch_invert_perm(ws.orig, ws.invp, np, batch, guard, stream);
     {
         int rpb = (64 * 1024) / (np * (int)sizeof(float));  // rows per workgroup: at most 64 KiB of LDS
         if (rpb < 1) rpb = 1;

@@ -50,37 +50,29 @@ Blocked64Plan make_blocked64_plan(int n, int bw)
     return p;
 }
 
-static inline size_t b64_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct B64Ws {
     double *w0, *w1;
     PivotRec<double> *k0, *k1;
     int *orig, *invp, *rowmap;
     size_t wstride;
 };
-static size_t b64_carve(const Blocked64Plan &p, int batch, void *base, B64Ws *o)
+static size_t b64_carve(const Blocked64Plan &p, int batch, void *base, B64Ws &o)
 {
-    const size_t wbytes = b64_align256((size_t)p.np * p.ld * sizeof(double));
-    const size_t kbytes = b64_align256((size_t)p.row_tiles * sizeof(PivotRec<double>) * batch);
-    const size_t ibytes = b64_align256((size_t)p.np * sizeof(int) * batch);
-    char *c = (char *)base;
-    size_t off = 0;
-    if (o) { o->w0 = (double *)(c + off); o->wstride = wbytes / sizeof(double); }
-    off += wbytes * batch;
-    if (o) o->w1 = (double *)(c + off);
-    off += wbytes * batch;
-    if (o) o->k0 = (PivotRec<double> *)(c + off);
-    off += kbytes;
-    if (o) o->k1 = (PivotRec<double> *)(c + off);
-    off += kbytes;
-    if (o) o->orig = (int *)(c + off);
-    off += ibytes;
-    if (o) o->invp = (int *)(c + off);
-    off += ibytes;
-    if (o) o->rowmap = (int *)(c + off);
-    off += ibytes;
-    return off;
+    const size_t wbytes = align256((size_t)p.np * p.ld * sizeof(double));
+    const size_t kbytes = align256((size_t)p.row_tiles * sizeof(PivotRec<double>) * batch);
+    const size_t ibytes = align256((size_t)p.np * sizeof(int) * batch);
+    WsCarver c(base);
+    o.wstride = wbytes / sizeof(double);
+    o.w0 = c.take<double>(wbytes * batch);
+    o.w1 = c.take<double>(wbytes * batch);
+    o.k0 = c.take<PivotRec<double>>(kbytes);
+    o.k1 = c.take<PivotRec<double>>(kbytes);
+    o.orig = c.take<int>(ibytes);
+    o.invp = c.take<int>(ibytes);
+    o.rowmap = c.take<int>(ibytes);
+    return c.off;
 }
-size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch) { return b64_carve(p, batch, nullptr, nullptr); }
+size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch) { B64Ws ws; return b64_carve(p, batch, nullptr, ws); }
 
 // ---- makeAugmented counterpart: A -> diag(A, I) in the first working copy --------------------
 __global__ __launch_bounds__(256) void b64_init_kernel(const double *__restrict__ in, int n, int np, int ld, size_t wstride,
@@ -351,39 +343,12 @@ __global__ __launch_bounds__(256) void b64_rank_update_kernel(const double *__re
             }
 }
 
-// ---- getInvertedMatrix counterpart --------------------------------------------------------------
-__global__ void b64_invert_perm_kernel(const int *__restrict__ orig, int *__restrict__ invp, int np)
-{
-    const int b = blockIdx.y;
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < np) invp[(size_t)b * np + orig[(size_t)b * np + c]] = c;
-}
-__global__ __launch_bounds__(256) void b64_unpermute_kernel(const double *__restrict__ w_all, int ld, int np, size_t wstride,
-                                                             const int *__restrict__ invp, int n, double *__restrict__ out)
-{
-    const int b = blockIdx.z;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const double *w = w_all + (size_t)b * wstride;
-    double *o = out + (size_t)b * n * n;
-    const int c = invp[(size_t)b * np + j];
-    const int i0 = blockIdx.y * 16;
-#pragma unroll 4
-    for (int u = 0; u < 16; ++u) {
-        const int i = i0 + u;
-        if (i < n) o[(size_t)i * n + j] = w[(size_t)i * ld + c];
-    }
-}
-
 template <int TX>
 static void b64_launch_step(const dim3 &grid, hipStream_t stream, const double *x, double *y, const Blocked64Plan &p,
                             size_t wstride, int r, int col_lo, const PivotRec<double> *kin, PivotRec<double> *kout, int *orig,
                             int *rowmap, int *status)
 {
-    if (p.tr == 16)
-        hipLaunchKernelGGL((b64_panel_step_kernel<TX, 16>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r,
-                           col_lo, kin, kout, p.row_tiles, orig, rowmap, status);
-    else if (p.tr == 8)
+    if (p.tr == 8)
         hipLaunchKernelGGL((b64_panel_step_kernel<TX, 8>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r,
                            col_lo, kin, kout, p.row_tiles, orig, rowmap, status);
     else
@@ -395,7 +360,7 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
                             hipStream_t stream, Profiler *prof)
 {
     B64Ws ws;
-    b64_carve(p, batch, wsp, &ws);
+    b64_carve(p, batch, wsp, ws);
     const int np = p.np;
     hipError_t e;
     if (d_status) {
@@ -438,9 +403,7 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
         }
     }
     ProfScope ps(prof, KC_FINISH, stream);
-    hipLaunchKernelGGL(b64_invert_perm_kernel, dim3((np + 255) / 256, batch), dim3(256), 0, stream, ws.orig, ws.invp, np);
-    hipLaunchKernelGGL(b64_unpermute_kernel, dim3((p.n + 255) / 256, (p.n + 15) / 16, batch), dim3(256), 0, stream, cur,
-                       p.ld, np, ws.wstride, ws.invp, p.n, d_inv);
+    launch_unpermute(cur, p.ld, ws.wstride, ws.orig, ws.invp, np, p.n, batch, d_inv, stream);
     return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <sys/mman.h>
@@ -635,22 +636,15 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
     if (!h || !d_a || !d_inv || n <= 0 || batch <= 0 || d_a == d_inv) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
-    if (resolve_algo_f64(h, n) == MI32_ALGO_BLOCKED) {
-        const Blocked64Plan bp = plan_blocked64(h, n);
-        int rc = ensure_ws(h, blocked64_workspace_bytes(bp, batch));
-        if (rc != MI32_OK) return rc;
-        rc = status_buffer(h, d_status, batch, &d_status);
-        if (rc != MI32_OK) return rc;
-        hipError_t eb = blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof);
-        if (eb != hipSuccess) return fail(eb, "kernel launch");
-        return MI32_OK;
-    }
-    const SweepPlan p = make_sweep_plan(n);
-    int rc = ensure_ws(h, sweep_workspace_bytes(p, batch, sizeof(double)));
+    const bool blocked = resolve_algo_f64(h, n) == MI32_ALGO_BLOCKED;
+    const Blocked64Plan bp = plan_blocked64(h, n);
+    const SweepPlan sp = make_sweep_plan(n);
+    int rc = ensure_ws(h, blocked ? blocked64_workspace_bytes(bp, batch) : sweep_workspace_bytes(sp, batch, sizeof(double)));
     if (rc != MI32_OK) return rc;
     rc = status_buffer(h, d_status, batch, &d_status);
     if (rc != MI32_OK) return rc;
-    hipError_t e = sweep_invert_f64(p, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
+    const hipError_t e = blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof)
+                                 : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     if (e != hipSuccess) return fail(e, "kernel launch");
     return MI32_OK;
 }
@@ -691,6 +685,8 @@ int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, in
     if (e != hipSuccess) return fail(e, "residual launch");
     return MI32_OK;
 }
+
+}  // extern "C"
 
 // ---- host-pointer entry points on the default context ---------------------------
 static mi32_context *g_default = nullptr;
@@ -823,46 +819,66 @@ struct ProfilingGuard {
     ~ProfilingGuard() { if (h) (void)mi32_set_profiling(h, 0); }
 };
 
+// the device entry point per element type
+static int inv_device(mi32_context *h, const float *d_a, int n, int batch, float *d_inv, int *d_status)
+{
+    return mi32_inv_device(h, d_a, n, batch, d_inv, d_status);
+}
+static int inv_device(mi32_context *h, const double *d_a, int n, int batch, double *d_inv, int *d_status)
+{
+    return mi32_inv_device_f64(h, d_a, n, batch, d_inv, d_status);
+}
+
 // `late_out`: where the result goes is only asked for once the kernels are queued -- the std::vector entry points
 // allocate and first-touch their 4 N^2 result bytes (64 MiB of page faults at N = 4096, ~8 ms) while the device works
 typedef void *(*LateOut)(void *ctx);
 // One host-pointer inversion on context h; the caller holds the lock that guards h's staging buffers.
+// pivoting: the variant of this one call (the context's own setting is restored afterwards).
 // total_s / compute_s: the reference's two numbers ("Tempo Totale Impiegato" / "Tempo Computazione", mat_inv_32.cpp:385-386).
-static int host_invert_32_on(mi32_context *h, std::chrono::steady_clock::time_point tq0, const float *a, int n, int batch,
-                             float *inv, int *status, double *times10, LateOut late_out, void *late_ctx, double *total_s,
-                             double *compute_s)
+template <typename T>
+static int host_invert_on(mi32_context *h, std::chrono::steady_clock::time_point tq0, const T *a, int n, int batch,
+                          T *inv, int *status, double *times10, bool pivoting, LateOut late_out, void *late_ctx,
+                          double *total_s, double *compute_s)
 {
     const auto t0 = std::chrono::steady_clock::now();
     MI32_HIP(hipSetDevice(h->device));
-    const size_t floats = (size_t)batch * n * n;
-    int rc = ensure_io(h, floats, (size_t)batch);
+    const size_t elems = (size_t)batch * n * n;
+    int rc = ensure_io(h, elems * (sizeof(T) / sizeof(float)), (size_t)batch);  // staging capacity in 4-byte units
     if (rc != MI32_OK) return rc;
     ProfilingGuard prof_guard;  // profiling is switched off again on every way out
     if (times10) {
-        rc = mi32_reserve(h, n, batch);  // workspace allocation belongs to the "buffers" slot
-        if (rc != MI32_OK) return rc;
+        if (std::is_same<T, float>::value) {
+            rc = mi32_reserve(h, n, batch);  // fp32: workspace allocation belongs to the "buffers" slot
+            if (rc != MI32_OK) return rc;
+        }
         rc = mi32_set_profiling(h, 1);
         if (rc != MI32_OK) return rc;
         prof_guard.h = h;
         double ms[KC_COUNT]; long long cnt[KC_COUNT];
         (void)mi32_get_profile(h, ms, cnt, KC_COUNT);  // drop what an earlier call left
     }
-    rc = host_copy(h, h->d_in, const_cast<float *>(a), floats * sizeof(float), true);
+    T *d_in = reinterpret_cast<T *>(h->d_in), *d_out = reinterpret_cast<T *>(h->d_out);
+    rc = host_copy(h, d_in, const_cast<T *>(a), elems * sizeof(T), true);
     if (rc != MI32_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = mi32_inv_device(h, h->d_in, n, batch, h->d_out, h->d_status);
+    {
+        const bool saved = h->pivoting;  // host-pointer contexts are only used under their caller's lock
+        h->pivoting = pivoting;
+        rc = inv_device(h, d_in, n, batch, d_out, h->d_status);
+        h->pivoting = saved;
+    }
     if (rc != MI32_OK) return rc;
     if (late_out) {
-        inv = static_cast<float *>(late_out(late_ctx));
+        inv = static_cast<T *>(late_out(late_ctx));
         if (!inv) { (void)hipStreamSynchronize(h->stream); return MI32_RUNTIME_ERROR; }
     } else {
-        parallel_populate(inv, floats * sizeof(float), true);  // the device is busy for the next milliseconds
+        parallel_populate(inv, elems * sizeof(T), true);  // the device is busy for the next milliseconds
     }
     MI32_HIP(hipStreamSynchronize(h->stream));
     const auto t2 = std::chrono::steady_clock::now();
     std::vector<int> st((size_t)batch);
     MI32_HIP(hipMemcpyAsync(st.data(), h->d_status, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    rc = host_copy(h, h->d_out, inv, floats * sizeof(float), false);
+    rc = host_copy(h, d_out, inv, elems * sizeof(T), false);
     if (rc != MI32_OK) return rc;
     MI32_HIP(hipStreamSynchronize(h->stream));
     const auto t3 = std::chrono::steady_clock::now();
@@ -879,7 +895,7 @@ static int host_invert_32_on(mi32_context *h, std::chrono::steady_clock::time_po
         if (status) status[b] = st[(size_t)b];
         if (st[(size_t)b] > worst) worst = st[(size_t)b];
     }
-    if (worst == MI32_RUNTIME_ERROR)  // the only status-borne runtime error (mi32_blocked.hip, shared panels)
+    if (worst == MI32_RUNTIME_ERROR)  // the only status-borne runtime error (mi32_blocked.hip, fp32 shared panels)
         g_last_error = "a workgroup of a shared panel timed out waiting for its partners (the device was not ours "
                        "alone); the affected inverse is NaN-filled -- retry, or set MI32_MULTI_PANEL=0";
     return worst;
@@ -895,8 +911,10 @@ static void print_reference_timing_lines()
     }
 }
 
-static int host_invert_32(const float *a, int n, int batch, float *inv, int *status, double *times10,
-                          LateOut late_out = nullptr, void *late_ctx = nullptr)
+// One host-pointer inversion on the default context.  The fp32 calls print the reference's timing lines.
+template <typename T>
+static int host_invert(const T *a, int n, int batch, T *inv, int *status, double *times10, bool pivoting = true,
+                       LateOut late_out = nullptr, void *late_ctx = nullptr)
 {
     if (!a || (!inv && !late_out) || n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
     const auto tq0 = std::chrono::steady_clock::now();
@@ -904,10 +922,18 @@ static int host_invert_32(const float *a, int n, int batch, float *inv, int *sta
     int rc = default_context(&h);  // the reference's platform / device / context / queue bring-up (cached here)
     if (rc != MI32_OK) return rc;
     std::lock_guard<std::mutex> lk(g_host_call_mu);  // one host-pointer call at a time: the staging buffers are shared
-    rc = host_invert_32_on(h, tq0, a, n, batch, inv, status, times10, late_out, late_ctx, &g_last_total, &g_last_compute);
-    if (rc == MI32_OK || rc == MI32_SINGULAR || rc == MI32_RUNTIME_ERROR) print_reference_timing_lines();
+    rc = host_invert_on(h, tq0, a, n, batch, inv, status, times10, pivoting, late_out, late_ctx, &g_last_total,
+                        &g_last_compute);
+    if (std::is_same<T, float>::value && (rc == MI32_OK || rc == MI32_SINGULAR || rc == MI32_RUNTIME_ERROR))
+        print_reference_timing_lines();
     return rc;
 }
+
+// the reference's shape guards, mat_inv_32.cpp:206-215 (integer division included); matrix_inversion_FP64.cpp
+// has the same two
+static bool bad_order(size_t a_len, int n) { return n <= 0 || (int)(a_len / (size_t)n) != n; }
+
+extern "C" {
 
 // ---- the batch over several GPUs (what replaces the reference's platforms[0] / devices[0],
 //      mat_inv_32.cpp:239-244) -------------------------------------------------------------------------
@@ -979,8 +1005,9 @@ extern "C" int mi32_matrix_inv_32_batched_multi(const float *a, int n, int batch
             if (rc == MI32_OK) sl->h = nh;
         }
         if (rc == MI32_OK)
-            rc = host_invert_32_on(sl->h, tq0, a + (size_t)lo * mat, n, hi - lo, inv + (size_t)lo * mat,
-                                   status ? status + lo : nullptr, nullptr, nullptr, nullptr, &tot[(size_t)g], &cmp[(size_t)g]);
+            rc = host_invert_on(sl->h, tq0, a + (size_t)lo * mat, n, hi - lo, inv + (size_t)lo * mat,
+                                status ? status + lo : nullptr, nullptr, true, nullptr, nullptr, &tot[(size_t)g],
+                                &cmp[(size_t)g]);
         rcs[(size_t)g] = rc;
         if (rc != MI32_OK) errs[(size_t)g] = g_last_error;  // thread-local: carried to the caller's thread below
     };
@@ -1010,102 +1037,37 @@ extern "C" int mi32_matrix_inv_32_batched_multi(const float *a, int n, int batch
 
 int mi32_matrix_inv_32_batched(const float *a, int n, int batch, float *inv, int *status)
 {
-    return host_invert_32(a, n, batch, inv, status, nullptr);
+    return host_invert(a, n, batch, inv, status, nullptr);
 }
 
 int mi32_bench_32(const float *a_rowmajor, size_t a_len, int n, float *inv_rowmajor, double *times10)
 {
-    if (n <= 0 || !times10) return MI32_BAD_SHAPE;
-    if ((int)(a_len / (size_t)n) != n) return MI32_BAD_SHAPE;
-    return host_invert_32(a_rowmajor, n, 1, inv_rowmajor, nullptr, times10);
+    if (!times10 || bad_order(a_len, n)) return MI32_BAD_SHAPE;
+    return host_invert(a_rowmajor, n, 1, inv_rowmajor, nullptr, times10);
 }
 
 int mi32_matrix_inv_32(const float *a_rowmajor, size_t a_len, int n, float *inv_rowmajor)
 {
-    // the reference's guards, mat_inv_32.cpp:206-215 (integer division included)
-    if (n <= 0) return MI32_BAD_SHAPE;
-    if ((int)(a_len / (size_t)n) != n) return MI32_BAD_SHAPE;
-    return mi32_matrix_inv_32_batched(a_rowmajor, n, 1, inv_rowmajor, nullptr);
+    if (bad_order(a_len, n)) return MI32_BAD_SHAPE;
+    return host_invert(a_rowmajor, n, 1, inv_rowmajor, nullptr, nullptr);
 }
-
-static int host_invert_64(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor, bool pivoting,
-                          double *times10, LateOut late_out = nullptr, void *late_ctx = nullptr);
 
 int mi32_matrix_inv_64(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor)
 {
-    return host_invert_64(a_rowmajor, a_len, n, inv_rowmajor, true, nullptr);
+    if (bad_order(a_len, n)) return MI32_BAD_SHAPE;
+    return host_invert(a_rowmajor, n, 1, inv_rowmajor, nullptr, nullptr);
 }
 
 int mi32_matrix_inversion_no_pivots(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor)
 {
-    return host_invert_64(a_rowmajor, a_len, n, inv_rowmajor, false, nullptr);
+    if (bad_order(a_len, n)) return MI32_BAD_SHAPE;
+    return host_invert(a_rowmajor, n, 1, inv_rowmajor, nullptr, nullptr, false);
 }
 
 int mi32_bench_64(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor, double *times10, int pivoting)
 {
-    if (!times10) return MI32_BAD_SHAPE;
-    return host_invert_64(a_rowmajor, a_len, n, inv_rowmajor, pivoting != 0, times10);
-}
-
-static int host_invert_64(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor, bool pivoting,
-                          double *times10, LateOut late_out, void *late_ctx)
-{
-    // the guards of the fp32 library (mat_inv_32.cpp:206-215); matrix_inversion_FP64.cpp has the same two
-    if (n <= 0) return MI32_BAD_SHAPE;
-    if ((int)(a_len / (size_t)n) != n) return MI32_BAD_SHAPE;
-    if (!a_rowmajor || (!inv_rowmajor && !late_out)) return MI32_BAD_SHAPE;
-    const auto tq0 = std::chrono::steady_clock::now();
-    mi32_context *h = nullptr;
-    int rc = default_context(&h);
-    if (rc != MI32_OK) return rc;
-    std::lock_guard<std::mutex> lk(g_host_call_mu);  // the staging buffers are shared with the fp32 host-pointer calls
-    const auto t0 = std::chrono::steady_clock::now();
-    MI32_HIP(hipSetDevice(h->device));
-    const size_t elems = (size_t)n * n;
-    rc = ensure_io(h, 2 * elems, 1);  // doubles: two 4-byte units each
-    if (rc != MI32_OK) return rc;
-    ProfilingGuard prof_guard;  // profiling is switched off again on every way out
-    if (times10) {
-        rc = mi32_set_profiling(h, 1);
-        if (rc != MI32_OK) return rc;
-        prof_guard.h = h;
-        double ms0[KC_COUNT]; long long cnt0[KC_COUNT];
-        (void)mi32_get_profile(h, ms0, cnt0, KC_COUNT);  // drop what an earlier call left
-    }
-    double *din = reinterpret_cast<double *>(h->d_in), *dout = reinterpret_cast<double *>(h->d_out);
-    rc = host_copy(h, din, const_cast<double *>(a_rowmajor), elems * sizeof(double), true);
-    if (rc != MI32_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    {
-        const bool saved = h->pivoting;  // the default context is only ever used under g_host_call_mu
-        h->pivoting = pivoting;
-        rc = mi32_inv_device_f64(h, din, n, 1, dout, h->d_status);
-        h->pivoting = saved;
-    }
-    if (rc != MI32_OK) return rc;
-    if (late_out) {
-        inv_rowmajor = static_cast<double *>(late_out(late_ctx));
-        if (!inv_rowmajor) { (void)hipStreamSynchronize(h->stream); return MI32_RUNTIME_ERROR; }
-    } else {
-        parallel_populate(inv_rowmajor, elems * sizeof(double), true);
-    }
-    MI32_HIP(hipStreamSynchronize(h->stream));
-    const auto t2 = std::chrono::steady_clock::now();
-    int st = MI32_OK;
-    MI32_HIP(hipMemcpyAsync(&st, h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    rc = host_copy(h, dout, inv_rowmajor, elems * sizeof(double), false);
-    if (rc != MI32_OK) return rc;
-    MI32_HIP(hipStreamSynchronize(h->stream));
-    const auto t3 = std::chrono::steady_clock::now();
-    g_last_total = std::chrono::duration<double>(t3 - t0).count();
-    g_last_compute = std::chrono::duration<double>(t2 - t1).count();
-    if (times10) {
-        double ms[KC_COUNT]; long long cnt[KC_COUNT];
-        rc = mi32_get_profile(h, ms, cnt, KC_COUNT);
-        if (rc != MI32_OK) return rc;
-        fill_times10(times10, ms, tq0, t0, t1, t2, t3);
-    }
-    return st;
+    if (!times10 || bad_order(a_len, n)) return MI32_BAD_SHAPE;
+    return host_invert(a_rowmajor, n, 1, inv_rowmajor, nullptr, times10, pivoting != 0);
 }
 
 // matrix_multiply of the reference (matrix_multiply.cpp:15-212): C = A * B in double on the device, returns
@@ -1150,91 +1112,89 @@ int mi32_last_timing(double *total_seconds, double *compute_seconds)
 
 }  // extern "C"
 
-// ---- the reference's entry point, unchanged signature (Matlab/mat_inv_32.h:4) ----
-std::vector<float> matrix_inv_32(std::vector<float> matrix_vector, int matrix_order)
+// ---- the reference's C++ entry points, unchanged signatures ------------------------------------------------
+
+// The std::vector drop-ins: {} for a bad shape (mat_inv_32.cpp:206-215) and for a failure.  README.md:54 "In case of
+// invalid matrix an empty vector is returned", and the experiment twins do so for a singular input (their
+// exact-identity checks, matrix_inversion_FP32.cpp:814-835, matrix_inversion_FP64.cpp:846-867,
+// matrix_inversion_no_pivots.cpp:670).  MI32_SINGULAR_KEEP=1 returns the inf/NaN result instead, as the shipped
+// library does.
+template <typename T>
+static std::vector<T> invert_to_vector(const std::vector<T> &matrix_vector, int matrix_order, bool pivoting,
+                                       const char *name)
 {
-    if (matrix_order <= 0) return {};                                        // mat_inv_32.cpp:206-208
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return {};  // :211-214
+    if (bad_order(matrix_vector.size(), matrix_order)) return {};
     // the result vector comes into being (value-initialised, every page touched) while the device works
-    std::vector<float> result;
-    struct Ctx { std::vector<float> *v; size_t n; } ctx = {&result, (size_t)matrix_order * matrix_order};
-    const int rc = host_invert_32(matrix_vector.data(), matrix_order, 1, nullptr, nullptr, nullptr,
+    std::vector<T> result;
+    struct Ctx { std::vector<T> *v; size_t n; } ctx = {&result, (size_t)matrix_order * matrix_order};
+    const int rc = host_invert<T>(matrix_vector.data(), matrix_order, 1, nullptr, nullptr, nullptr, pivoting,
                                   [](void *c) -> void * {
                                       Ctx *x = static_cast<Ctx *>(c);
                                       try {
                                           x->v->reserve(x->n);  // pages first (several threads), then the value-initialisation
-                                          parallel_populate(x->v->data(), x->n * sizeof(float));
+                                          parallel_populate(x->v->data(), x->n * sizeof(T));
                                           x->v->resize(x->n);
                                       } catch (...) { return nullptr; }
                                       return x->v->data();
                                   }, &ctx);
     if (rc == MI32_OK) return result;
-    // README.md:54 "In case of invalid matrix an empty vector is returned"; the experiment twin
-    // does so for a singular input (matrix_inversion_FP32.cpp:814-835).  MI32_SINGULAR_KEEP=1
-    // returns the inf/NaN result instead, as the shipped library does.
     if (rc == MI32_SINGULAR && env_int("MI32_SINGULAR_KEEP", 0)) return result;
-    if (rc == MI32_RUNTIME_ERROR) std::fprintf(stderr, "matrix_inv_32: %s\n", mi32_last_error());
+    if (rc == MI32_RUNTIME_ERROR) std::fprintf(stderr, "%s: %s\n", name, mi32_last_error());
     return {};
 }
 
-// ---- the reference's no-pivot variant, unchanged signature (matrix_inversion/headers.h:11) ----
-std::vector<double> matrix_inversion_no_pivots(std::vector<double> matrix_vector, int matrix_order)
-{
-    if (matrix_order <= 0) return {};
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return {};
-    std::vector<double> result((size_t)matrix_order * matrix_order, 0.0);
-    const int rc = mi32_matrix_inversion_no_pivots(matrix_vector.data(), matrix_vector.size(), matrix_order, result.data());
-    if (rc == MI32_OK) return result;
-    // a zero diagonal entry on the way: {} like the reference (exact-identity check, matrix_inversion_no_pivots.cpp:670)
-    if (rc == MI32_SINGULAR && env_int("MI32_SINGULAR_KEEP", 0)) return result;
-    if (rc == MI32_RUNTIME_ERROR) std::fprintf(stderr, "matrix_inversion_no_pivots: %s\n", mi32_last_error());
-    return {};
-}
-
-// ---- the reference's benchmark twin, unchanged signature (matrix_inversion/headers.h:15, FP32_bench.cpp:11) ----
-Res FP32_bench(std::vector<float> matrix_vector, int matrix_order)
+// The benchmark twins (FP32_bench.cpp:11): the inverse and the ten timing slots, an empty Res where the reference
+// returns one (bad shape, :212-217; error paths, :456).
+template <typename T>
+static Res bench_to_res(const std::vector<T> &matrix_vector, int matrix_order, bool pivoting, std::vector<T> Res::*inverse)
 {
     Res res;
-    if (matrix_order <= 0) return res;                                                       // FP32_bench.cpp:212
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return res;      // :217
-    std::vector<float> inv((size_t)matrix_order * matrix_order, 0.0f);
+    if (bad_order(matrix_vector.size(), matrix_order)) return res;
+    std::vector<T> inv((size_t)matrix_order * matrix_order, T(0));
     std::vector<double> times(10, 0.0);
-    const int rc = mi32_bench_32(matrix_vector.data(), matrix_vector.size(), matrix_order, inv.data(), times.data());
-    if (rc != MI32_OK) return res;   // {} like the reference's error paths (:456)
-    res.inversa32 = std::move(inv);
+    if (host_invert(matrix_vector.data(), matrix_order, 1, inv.data(), nullptr, times.data(), pivoting) != MI32_OK)
+        return res;
+    res.*inverse = std::move(inv);
     res.times = std::move(times);
     return res;
 }
 
-Res FP64_bench(std::vector<double> matrix_vector, int matrix_order)
+// Matlab/mat_inv_32.h:4
+std::vector<float> matrix_inv_32(std::vector<float> matrix_vector, int matrix_order)
 {
-    Res res;
-    if (matrix_order <= 0) return res;
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return res;
-    std::vector<double> inv((size_t)matrix_order * matrix_order, 0.0), times(10, 0.0);
-    if (mi32_bench_64(matrix_vector.data(), matrix_vector.size(), matrix_order, inv.data(), times.data(), 1) != MI32_OK) return res;
-    res.inversa64 = std::move(inv);
-    res.times = std::move(times);
-    return res;
+    return invert_to_vector(matrix_vector, matrix_order, true, "matrix_inv_32");
 }
 
-Res no_pivots_bench(std::vector<double> matrix_vector, int matrix_order)
-{
-    Res res;
-    if (matrix_order <= 0) return res;
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return res;
-    std::vector<double> inv((size_t)matrix_order * matrix_order, 0.0), times(10, 0.0);
-    if (mi32_bench_64(matrix_vector.data(), matrix_vector.size(), matrix_order, inv.data(), times.data(), 0) != MI32_OK) return res;
-    res.inversa64 = std::move(inv);
-    res.times = std::move(times);
-    return res;
-}
-
-// the experiment twin of matrix_inv_32 (headers.h:7, matrix_inversion_FP32.cpp:11): same call shape; {} for an
-// invalid matrix (its exact-identity check of the reduced left half, :814-835)
+// the experiment twin of matrix_inv_32 (headers.h:7, matrix_inversion_FP32.cpp:11): same call shape
 std::vector<float> matrix_inversion_FP32(std::vector<float> matrix_vector, int matrix_order)
 {
     return matrix_inv_32(static_cast<std::vector<float> &&>(matrix_vector), matrix_order);
+}
+
+// matrix_inversion/headers.h:9
+std::vector<double> matrix_inversion_FP64(std::vector<double> matrix_vector, int matrix_order)
+{
+    return invert_to_vector(matrix_vector, matrix_order, true, "matrix_inversion_FP64");
+}
+
+// matrix_inversion/headers.h:11: the diagonal entry is every step's pivot
+std::vector<double> matrix_inversion_no_pivots(std::vector<double> matrix_vector, int matrix_order)
+{
+    return invert_to_vector(matrix_vector, matrix_order, false, "matrix_inversion_no_pivots");
+}
+
+// matrix_inversion/headers.h:13-16
+Res FP32_bench(std::vector<float> matrix_vector, int matrix_order)
+{
+    return bench_to_res(matrix_vector, matrix_order, true, &Res::inversa32);
+}
+Res FP64_bench(std::vector<double> matrix_vector, int matrix_order)
+{
+    return bench_to_res(matrix_vector, matrix_order, true, &Res::inversa64);
+}
+Res no_pivots_bench(std::vector<double> matrix_vector, int matrix_order)
+{
+    return bench_to_res(matrix_vector, matrix_order, false, &Res::inversa64);
 }
 
 // headers.h:5, matrix_multiply.cpp:15: sqrt(N) - ||A * B||_F, N = sqrt(size)
@@ -1245,28 +1205,4 @@ double matrix_multiply(std::vector<double> matriceA, std::vector<double> matrice
     const int rc = mi32_matrix_multiply_64(matriceA.data(), matriceB.data(), matriceA.size(), &errore);
     if (rc == MI32_RUNTIME_ERROR) std::fprintf(stderr, "matrix_multiply: %s\n", mi32_last_error());
     return errore;
-}
-
-// ---- the reference's fp64 entry point, unchanged signature (matrix_inversion/headers.h:9) ----
-std::vector<double> matrix_inversion_FP64(std::vector<double> matrix_vector, int matrix_order)
-{
-    if (matrix_order <= 0) return {};
-    if ((int)(matrix_vector.size() / (size_t)matrix_order) != matrix_order) return {};
-    std::vector<double> result;  // allocated and first touched while the device works (see matrix_inv_32)
-    struct Ctx { std::vector<double> *v; size_t n; } ctx = {&result, (size_t)matrix_order * matrix_order};
-    const int rc = host_invert_64(matrix_vector.data(), matrix_vector.size(), matrix_order, nullptr, true, nullptr,
-                                  [](void *c) -> void * {
-                                      Ctx *x = static_cast<Ctx *>(c);
-                                      try {
-                                          x->v->reserve(x->n);
-                                          parallel_populate(x->v->data(), x->n * sizeof(double));
-                                          x->v->resize(x->n);
-                                      } catch (...) { return nullptr; }
-                                      return x->v->data();
-                                  }, &ctx);
-    if (rc == MI32_OK) return result;
-    // a singular input: {} like the reference (its exact-identity check, matrix_inversion_FP64.cpp:846-867)
-    if (rc == MI32_SINGULAR && env_int("MI32_SINGULAR_KEEP", 0)) return result;
-    if (rc == MI32_RUNTIME_ERROR) std::fprintf(stderr, "matrix_inversion_FP64: %s\n", mi32_last_error());
-    return {};
 }

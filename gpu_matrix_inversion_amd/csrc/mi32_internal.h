@@ -34,6 +34,13 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
     return k;
 }
 
+// Blocked fp32 plans with shared panels only: true when matrix b was given up (see SubpanelArgs::guard in
+// mi32_blocked.hip; guard may be null).  Wave-uniform.
+__device__ __forceinline__ bool matrix_given_up(const int *guard, int b)
+{
+    return guard != nullptr && __builtin_amdgcn_readfirstlane(guard[b]) == MI32_RUNTIME_ERROR;
+}
+
 // ---- optional per-kernel-class timing (HIP events on the launch stream) -------------
 // Off by default.  When a context enables it, every launch is bracketed by two
 // events recorded on the stream the kernel is launched on; the classes mirror the
@@ -58,6 +65,24 @@ struct ProfScope {
     Profiler *p; int k; hipStream_t s;
     ProfScope(Profiler *p_, int k_, hipStream_t s_) : p(p_), k(k_), s(s_) { if (p) p->begin(k, s); }
     ~ProfScope() { if (p) p->end(k, s); }
+};
+
+// ---- workspace carving ----------------------------------------------------------
+// Every workspace region starts on a 256-byte boundary.
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// Bump allocator over one workspace.  Without a base pointer it only adds up the region sizes (the
+// *_workspace_bytes functions); with one it also hands out each region's address.
+struct WsCarver {
+    char *base;
+    size_t off = 0;
+    explicit WsCarver(void *b) : base((char *)b) {}
+    template <typename P>
+    P *take(size_t bytes)
+    {
+        P *p = base ? (P *)(base + off) : nullptr;
+        off += bytes;
+        return p;
+    }
 };
 
 // ---- launch plumbing ----------------------------------------------------------
@@ -96,17 +121,16 @@ size_t blocked_workspace_bytes(const BlockedPlan &p, int batch);
 
 // Enqueue a whole inversion on `stream`.  ws: workspace of at least the size
 // reported above, 256-byte aligned.
+// T = float, or double: the fp64 twin (matrix_inversion_FP64 of the reference), same launches on doubles.
 // pivoting = false: the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10), the diagonal entry is the pivot
-hipError_t sweep_invert(const SweepPlan &p, const float *d_a, float *d_inv, int batch, int *d_status, void *ws,
+template <typename T>
+hipError_t sweep_invert(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, void *ws,
                         hipStream_t stream, Profiler *prof, bool pivoting = true);
-// the fp64 twin (matrix_inversion_FP64 of the reference): same launches on doubles
-hipError_t sweep_invert_f64(const SweepPlan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
-                            hipStream_t stream, Profiler *prof, bool pivoting = true);
 // fp64 blocked path (mi32_blocked64.hip): windowed sweep steps + rank-bw updates on the fp64 matrix cores
 struct Blocked64Plan {
     int n, np, ld;  // matrix order, padded order (multiple of 64, identity padding), row stride in doubles
     int bw;         // outer block width (multiple of 64, <= 256)
-    int tr;         // rows per workgroup of the step kernel (16 or 32)
+    int tr;         // rows per workgroup of the step kernel (8 or 32)
     int row_tiles;  // workgroups per step launch = arg-max records per column
 };
 Blocked64Plan make_blocked64_plan(int n, int bw);
@@ -128,6 +152,16 @@ struct BlockedExec {
 };
 hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, int batch, int *d_status, void *ws,
                           const BlockedExec &ex);
+// getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths (mi32_sweep.hip).  Working
+// column c holds inverse column orig[c].  orig and invp hold np entries per matrix, np apart.
+// invp <- the inverse of orig; a matrix whose guard word is MI32_RUNTIME_ERROR is skipped (guard may be null).
+void launch_invert_perm(const int *orig, int *invp, int np, int batch, const int *guard, hipStream_t stream);
+// launch_invert_perm, then out (n x n per matrix) <- the working copy w (row stride ld, wstride elements per matrix)
+// with its columns gathered through invp
+// (T = float or double)
+template <typename T>
+void launch_unpermute(const T *w, int ld, size_t wstride, const int *orig, int *invp, int np, int n, int batch, T *out,
+                      hipStream_t stream);
 hipError_t residual_launch(const float *d_a, const float *d_x, int n, int batch, double *d_out, void *ws,
                            hipStream_t stream);
 size_t residual_workspace_bytes(int n, int batch);

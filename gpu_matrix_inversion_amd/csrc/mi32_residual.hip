@@ -11,7 +11,6 @@
 
 namespace mi32 {
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // workspace: per matrix rowsum_right[n], rowsum_left[n], sumsq (doubles)
 size_t residual_workspace_bytes(int n, int batch) { return align256(((size_t)2 * n + 2) * sizeof(double) * batch); }
 

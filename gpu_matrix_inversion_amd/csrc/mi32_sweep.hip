@@ -55,37 +55,31 @@ SweepPlan make_sweep_plan(int n)
 }
 
 // workspace: [W0][W1][keys0][keys1][orig][invp], each region 256-B aligned
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct SweepWs {
     void *w0, *w1;   // the two working copies (element type T)
     void *k0, *k1;   // per-row-tile arg-max records (PivotRec<T>)
     int *orig, *invp;
     size_t wstride;  // elements per matrix
 };
-static size_t sweep_carve(const SweepPlan &p, int batch, void *base, SweepWs *o, size_t elem_bytes)
+static size_t sweep_carve(const SweepPlan &p, int batch, void *base, SweepWs &o, size_t elem_bytes)
 {
     const size_t wbytes = align256((size_t)p.n * p.ld * elem_bytes);
     const size_t kbytes = align256((size_t)p.row_tiles * 2 * sizeof(unsigned long long) * batch);
     const size_t ibytes = align256((size_t)p.n * sizeof(int) * batch);
-    char *c = (char *)base;
-    size_t off = 0;
-    if (o) { o->w0 = (void *)(c + off); o->wstride = wbytes / elem_bytes; }
-    off += wbytes * batch;
-    if (o) o->w1 = (void *)(c + off);
-    off += wbytes * batch;
-    if (o) o->k0 = (void *)(c + off);
-    off += kbytes;
-    if (o) o->k1 = (void *)(c + off);
-    off += kbytes;
-    if (o) o->orig = (int *)(c + off);
-    off += ibytes;
-    if (o) o->invp = (int *)(c + off);
-    off += ibytes;
-    return off;
+    WsCarver c(base);
+    o.wstride = wbytes / elem_bytes;
+    o.w0 = c.take<void>(wbytes * batch);
+    o.w1 = c.take<void>(wbytes * batch);
+    o.k0 = c.take<void>(kbytes);
+    o.k1 = c.take<void>(kbytes);
+    o.orig = c.take<int>(ibytes);
+    o.invp = c.take<int>(ibytes);
+    return c.off;
 }
 size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes)
 {
-    return sweep_carve(p, batch, nullptr, nullptr, elem_bytes);
+    SweepWs ws;
+    return sweep_carve(p, batch, nullptr, ws, elem_bytes);
 }
 
 // ---- makeAugmentedMatrix counterpart (mat_inv_32.cpp:177-192) ---------------
@@ -258,19 +252,21 @@ __global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_kernel(const T *_
     }
 }
 
-// ---- getInvertedMatrix counterpart (mat_inv_32.cpp:195-203) ------------------
-// Working column c holds inverse column orig[c]; gather through the inverse map
-// so that the stores are coalesced.
-__global__ void invert_perm_kernel(const int *__restrict__ orig, int *__restrict__ invp, int n)
+// ---- getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths -------------
+// Working column c holds inverse column orig[c]; gather through the inverse map so that the stores are coalesced.
+// The maps of matrix b start at b * istride (np: the padded order of the blocked paths, n for the sweep).
+__global__ void invert_perm_kernel(const int *__restrict__ orig, int *__restrict__ invp, int n, int istride,
+                                   const int *__restrict__ guard)
 {
     const int b = blockIdx.y;
+    if (matrix_given_up(guard, b)) return;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < n) invp[(size_t)b * n + orig[(size_t)b * n + c]] = c;
+    if (c < n) invp[(size_t)b * istride + orig[(size_t)b * istride + c]] = c;
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void unpermute_columns_kernel(const T *__restrict__ w_all, int ld, size_t wstride,
-                                                                 const int *__restrict__ invp, int n,
+                                                                 const int *__restrict__ invp, int np, int n,
                                                                  T *__restrict__ out)
 {
     const int b = blockIdx.z;
@@ -278,7 +274,7 @@ __global__ __launch_bounds__(256) void unpermute_columns_kernel(const T *__restr
     if (j >= n) return;
     const T *w = w_all + (size_t)b * wstride;
     T *o = out + (size_t)b * n * n;
-    const int c = invp[(size_t)b * n + j];
+    const int c = invp[(size_t)b * np + j];
     const int i0 = blockIdx.y * 16;
 #pragma unroll 4
     for (int u = 0; u < 16; ++u) {
@@ -286,6 +282,22 @@ __global__ __launch_bounds__(256) void unpermute_columns_kernel(const T *__restr
         if (i < n) o[(size_t)i * n + j] = w[(size_t)i * ld + c];
     }
 }
+
+void launch_invert_perm(const int *orig, int *invp, int np, int batch, const int *guard, hipStream_t stream)
+{
+    hipLaunchKernelGGL(invert_perm_kernel, dim3((np + 255) / 256, batch), dim3(256), 0, stream, orig, invp, np, np,
+                       guard);
+}
+template <typename T>
+void launch_unpermute(const T *w, int ld, size_t wstride, const int *orig, int *invp, int np, int n, int batch, T *out,
+                      hipStream_t stream)
+{
+    launch_invert_perm(orig, invp, np, batch, nullptr, stream);
+    hipLaunchKernelGGL((unpermute_columns_kernel<T>), dim3((n + 255) / 256, (n + 15) / 16, batch), dim3(256), 0, stream,
+                       w, ld, wstride, invp, np, n, out);
+}
+template void launch_unpermute(const float *, int, size_t, const int *, int *, int, int, int, float *, hipStream_t);
+template void launch_unpermute(const double *, int, size_t, const int *, int *, int, int, int, double *, hipStream_t);
 
 template <typename T, int TR>
 static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, const SweepWs &ws,
@@ -316,19 +328,16 @@ static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batc
     }
     const T *fin = (p.n % 2 == 0) ? w0 : w1;  // the last-written copy (mat_inv_32.cpp:369-372)
     ProfScope ps(prof, KC_FINISH, stream);
-    hipLaunchKernelGGL(invert_perm_kernel, dim3((p.n + 255) / 256, batch), dim3(256), 0, stream, ws.orig, ws.invp,
-                       p.n);
-    hipLaunchKernelGGL((unpermute_columns_kernel<T>), dim3((p.n + 255) / 256, (p.n + 15) / 16, batch), dim3(256), 0,
-                       stream, fin, p.ld, ws.wstride, ws.invp, p.n, d_inv);
+    launch_unpermute(fin, p.ld, ws.wstride, ws.orig, ws.invp, p.n, p.n, batch, d_inv, stream);
     return hipGetLastError();
 }
 
 template <typename T>
-static hipError_t sweep_invert_t(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, void *wsp,
-                                 hipStream_t stream, Profiler *prof, bool pivoting)
+hipError_t sweep_invert(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, void *wsp,
+                        hipStream_t stream, Profiler *prof, bool pivoting)
 {
     SweepWs ws;
-    sweep_carve(p, batch, wsp, &ws, sizeof(T));
+    sweep_carve(p, batch, wsp, ws, sizeof(T));
     switch (p.tr) {
         case 4: return sweep_run<T, 4>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
         case 8: return sweep_run<T, 8>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
@@ -336,16 +345,7 @@ static hipError_t sweep_invert_t(const SweepPlan &p, const T *d_a, T *d_inv, int
         default: return sweep_run<T, 32>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
     }
 }
-
-hipError_t sweep_invert(const SweepPlan &p, const float *d_a, float *d_inv, int batch, int *d_status, void *wsp,
-                        hipStream_t stream, Profiler *prof, bool pivoting)
-{
-    return sweep_invert_t<float>(p, d_a, d_inv, batch, d_status, wsp, stream, prof, pivoting);
-}
-hipError_t sweep_invert_f64(const SweepPlan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *wsp,
-                            hipStream_t stream, Profiler *prof, bool pivoting)
-{
-    return sweep_invert_t<double>(p, d_a, d_inv, batch, d_status, wsp, stream, prof, pivoting);
-}
+template hipError_t sweep_invert(const SweepPlan &, const float *, float *, int, int *, void *, hipStream_t, Profiler *, bool);
+template hipError_t sweep_invert(const SweepPlan &, const double *, double *, int, int *, void *, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

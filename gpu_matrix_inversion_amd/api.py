@@ -77,7 +77,10 @@ def matrix_inv_64(matrix_vector, matrix_order: int) -> np.ndarray:
 def matrix_inversion_no_pivots(matrix_vector, matrix_order: int) -> np.ndarray:
     """Drop-in for the reference's ``matrix_inversion_no_pivots(std::vector<double>, int)`` (headers.h:11,
     matrix_inversion_no_pivots.cpp:10): Gauss-Jordan in double with the diagonal entry as every step's pivot --
-    for diagonally dominant inputs.  Empty array for a bad shape or when a zero diagonal entry is met."""
+    for diagonally dominant inputs.  Empty array for a bad shape, a non-finite input entry, or when a zero / non-finite
+    diagonal entry is met.  From N = 512 on it runs on the blocked fp64 no-pivot path: the same result bit for bit
+    (``np.array_equal``) as the step-by-step order, given finite intermediates; a zero multiplier is multiplied
+    through there, so the sign of a zero entry can differ."""
     return _invert_flat("mi32_matrix_inversion_no_pivots", matrix_vector, matrix_order, np.float64)
 
 
@@ -124,7 +127,9 @@ def fp32_bench(matrix_vector, matrix_order: int):
 
 
 def fp64_bench(matrix_vector, matrix_order: int, pivoting: bool = True):
-    """``Res FP64_bench`` / ``Res no_pivots_bench`` of the reference (headers.h:14,16): ``(inverse float64, times)``."""
+    """``Res FP64_bench`` / ``Res no_pivots_bench`` of the reference (headers.h:14,16): ``(inverse float64, times)``.
+    With ``pivoting=False`` from N = 512 on (the blocked no-pivot path), ``times["pivot"]`` is the diagonal blocks and
+    ``times["column"]`` the block-column, strip and rank-bw updates; on the sweep kernels the pivot slot is 0."""
     return _bench("mi32_bench_64", matrix_vector, matrix_order, np.float64, 1 if pivoting else 0)
 
 
@@ -185,7 +190,7 @@ class Inverter:
         _lib.check(self._lib.mi32_set_algo(self._h, self.algo), "mi32_set_algo")
         if panel_width or block_width:
             _lib.check(self._lib.mi32_set_blocking(self._h, panel_width, block_width), "mi32_set_blocking")
-        if not pivoting:  # the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10); fp32: blocked from 512 rows on
+        if not pivoting:  # the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10): blocked from 512 rows on
             _lib.check(self._lib.mi32_set_pivoting(self._h, 0), "mi32_set_pivoting")
 
     def close(self):
@@ -214,7 +219,8 @@ class Inverter:
         return w.value, bw.value
 
     def resolved_blocking_f64(self, n: int) -> int:
-        """Outer block width of the fp64 blocked path for this order; 0 where the unblocked sweep runs."""
+        """Outer block width of the fp64 blocked path for this order (with ``pivoting=False``: of the fp64 no-pivot
+        path, 64 or 128); 0 where the unblocked sweep runs."""
         bw = ctypes.c_int()
         _lib.check(self._lib.mi32_resolve_blocking_f64(self._h, int(n), ctypes.byref(bw)), "mi32_resolve_blocking_f64")
         return bw.value
@@ -234,8 +240,8 @@ class Inverter:
         _lib.check(self._lib.mi32_reserve(self._h, int(n), int(batch)), "mi32_reserve")
 
     def inv(self, a, out=None, status=None):
-        """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin, sweep path) contiguous tensor on this
-        device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
+        """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin; sweep or blocked as resolved_blocking_f64
+        reports) contiguous tensor on this device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
         torch = self._torch
         if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
             raise ValueError("expected a float32 or float64 tensor on the GPU")

@@ -101,6 +101,13 @@ __global__ __launch_bounds__(256) void b64_init_kernel(const double *__restrict_
     if (nonfinite && status) status[b] = MI32_SINGULAR;  // status[b] was zeroed by the host; same value from every writer
 }
 
+void launch_b64_init(const double *d_a, int n, int np, int ld, size_t wstride, double *w0, int *orig, int batch,
+                     int *status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(b64_init_kernel, dim3((np + 255) / 256, (np + 15) / 16, batch), dim3(256), 0, stream, d_a, n, np,
+                       ld, wstride, w0, orig, status);
+}
+
 // ---- arg-max records of column c over the rows >= c (the first column of a block), row map reset ----
 __global__ __launch_bounds__(64) void b64_block_prep_kernel(const double *__restrict__ w_all, int np, int ld, size_t wstride,
                                                              int c, PivotRec<double> *__restrict__ keys, int npart,
@@ -368,8 +375,7 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
     }
     {
         ProfScope ps(prof, KC_INIT, stream);
-        hipLaunchKernelGGL(b64_init_kernel, dim3((np + 255) / 256, (np + 15) / 16, batch), dim3(256), 0, stream, d_a, p.n,
-                           np, p.ld, ws.wstride, ws.w0, ws.orig, d_status);
+        launch_b64_init(d_a, p.n, np, p.ld, ws.wstride, ws.w0, ws.orig, batch, d_status, stream);
     }
     double *cur = ws.w0, *oth = ws.w1;
     PivotRec<double> *kin = ws.k0, *kout = ws.k1;

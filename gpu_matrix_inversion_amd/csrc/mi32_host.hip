@@ -232,7 +232,7 @@ struct mi32_context {
     void *ws = nullptr;
     size_t ws_bytes = 0;
     int algo = MI32_ALGO_AUTO;
-    bool pivoting = true;  // false: the reference's no-pivot variant (sweep kernels, the diagonal entry is the pivot)
+    bool pivoting = true;  // false: the reference's no-pivot variant (the diagonal entry is every step's pivot)
     int panel_w = 0;
     int block_w = 0;
     // staging for the host-pointer entry points
@@ -610,24 +610,25 @@ int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *
 }
 
 // fp64: blocked (windowed steps + rank-bw updates on the fp64 matrix cores) from N = 256 on, measured cross-over;
-// the no-pivot variant and MI32_ALGO_SWEEP keep the unblocked sweep
+// the no-pivot variant: its own blocked path (mi32_nopivot64.hip) from N = 512 on, the cross-over of the fp32
+// no-pivot path; MI32_ALGO_SWEEP keeps the unblocked sweep
 static int resolve_algo_f64(const mi32_context *h, int n)
 {
-    if (h && !h->pivoting) return MI32_ALGO_SWEEP;
     int algo = h ? h->algo : MI32_ALGO_AUTO;
     if (algo == MI32_ALGO_AUTO) algo = env_int("MI32_ALGO", MI32_ALGO_AUTO);
-    if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= 256) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
+    const int cross = (h && !h->pivoting) ? 512 : 256;
+    if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
     return algo;
 }
-static Blocked64Plan plan_blocked64(const mi32_context *h, int n)
-{
-    return make_blocked64_plan(n, h && h->block_w ? h->block_w : env_int("MI32_BLOCK_W64", 0));
-}
+static int block_w64(const mi32_context *h) { return h && h->block_w ? h->block_w : env_int("MI32_BLOCK_W64", 0); }
+static Blocked64Plan plan_blocked64(const mi32_context *h, int n) { return make_blocked64_plan(n, block_w64(h)); }
+static NoPivot64Plan plan_nopivot64(const mi32_context *h, int n) { return make_nopivot64_plan(n, block_w64(h)); }
 
 int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width)
 {
     if (n <= 0 || !block_width) return MI32_BAD_SHAPE;
-    *block_width = resolve_algo_f64(h, n) == MI32_ALGO_BLOCKED ? plan_blocked64(h, n).bw : 0;
+    if (resolve_algo_f64(h, n) != MI32_ALGO_BLOCKED) *block_width = 0;
+    else *block_width = (h && !h->pivoting) ? plan_nopivot64(h, n).bw : plan_blocked64(h, n).bw;
     return MI32_OK;
 }
 
@@ -637,14 +638,19 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     const bool blocked = resolve_algo_f64(h, n) == MI32_ALGO_BLOCKED;
+    const bool nopivot = blocked && !h->pivoting;
     const Blocked64Plan bp = plan_blocked64(h, n);
+    const NoPivot64Plan npp = plan_nopivot64(h, n);
     const SweepPlan sp = make_sweep_plan(n);
-    int rc = ensure_ws(h, blocked ? blocked64_workspace_bytes(bp, batch) : sweep_workspace_bytes(sp, batch, sizeof(double)));
+    int rc = ensure_ws(h, nopivot ? nopivot64_workspace_bytes(npp, batch)
+                          : blocked ? blocked64_workspace_bytes(bp, batch)
+                                    : sweep_workspace_bytes(sp, batch, sizeof(double)));
     if (rc != MI32_OK) return rc;
     rc = status_buffer(h, d_status, batch, &d_status);
     if (rc != MI32_OK) return rc;
-    const hipError_t e = blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof)
-                                 : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
+    const hipError_t e = nopivot ? nopivot64_invert(npp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof)
+                         : blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof)
+                                   : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     if (e != hipSuccess) return fail(e, "kernel launch");
     return MI32_OK;
 }

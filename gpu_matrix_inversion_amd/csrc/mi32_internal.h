@@ -137,6 +137,21 @@ Blocked64Plan make_blocked64_plan(int n, int bw);
 size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch);
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
                             hipStream_t stream, Profiler *prof);
+// makeAugmented counterpart of the fp64 blocked paths: w0 <- diag(A, I) (np x np, row stride ld, wstride doubles per
+// matrix), orig <- the identity, status[b] <- MI32_SINGULAR for a non-finite input entry (status may be null)
+void launch_b64_init(const double *d_a, int n, int np, int ld, size_t wstride, double *w0, int *orig, int batch,
+                     int *status, hipStream_t stream);
+// fp64 no-pivot path (mi32_nopivot64.hip): the reference's order element by element, per block of bw steps the
+// diagonal block on one workgroup, the block columns / pivot-row strips of every other row / column, and one
+// rank-bw update on the fp64 matrix cores
+struct NoPivot64Plan {
+    int n, np, ld;  // matrix order, padded order (multiple of bw, identity padding), row stride in doubles
+    int bw;         // block width: 64 (default) or 128
+};
+NoPivot64Plan make_nopivot64_plan(int n, int bw);
+size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch);
+hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
+                            hipStream_t stream, Profiler *prof);
 
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"

@@ -109,16 +109,22 @@ int mi32_matrix_inv_64(const double *a_rowmajor, size_t a_len, int n, double *in
 /* The reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10, headers.h:11): the same steps with the
  * diagonal entry as pivot, no search and no swap -- for diagonally dominant inputs.  Host-pointer twin in double
  * (as the reference ships it); mi32_set_pivoting(h, 0) selects it for the device-resident calls of a context, in
- * either precision.  fp64 runs on the sweep path; fp32 takes the blocked path from 512 rows on: without a search the
- * W pivot rows of a sub-panel are known in advance, so the "panel" is their W x W diagonal block and every other row
- * is taken through the W steps by the update tiles on the whole chip (N = 4096: 5.7 ms against 92 ms for the sweep
- * kernels), bit-identical to the step-by-step restatement.  A zero / non-finite diagonal entry -> MI32_SINGULAR. */
+ * either precision.  Both take a blocked path from 512 rows on (below, and under MI32_ALGO_SWEEP, the sweep kernels;
+ * an explicit MI32_ALGO_BLOCKED at any order).  fp32: without a search the W pivot rows of a sub-panel are known in
+ * advance, so the "panel" is their W x W diagonal block and every other row is taken through the W steps by the
+ * update tiles on the whole chip (N = 4096: 5.7 ms against 92 ms for the sweep kernels).  fp64 (mi32_nopivot64.hip):
+ * per block of bw steps the bw x bw diagonal block on one workgroup, the block columns of every other row and the
+ * pivot rows' entries of every other column on the whole chip, one rank-bw update on v_mfma_f64_16x16x4_f64
+ * (N = 4096: 8 ms against 240 ms for the sweep kernels).  Both are bit-identical to the step-by-step restatement,
+ * with two caveats for fp64: a zero multiplier is multiplied through rather than skipped, so the sign of a zero
+ * entry can differ, and the equality assumes finite intermediates.  A zero / non-finite diagonal entry or a
+ * non-finite input entry -> MI32_SINGULAR (per batch member; a singular member's output values are unspecified). */
 int mi32_matrix_inversion_no_pivots(const double *a_rowmajor, size_t a_len, int n, double *inv_rowmajor);
 int mi32_set_pivoting(mi32_handle_t h, int enable);
 int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status);
 /* outer block width of the fp64 blocked path for this order (the step kernels run on a window of that many columns,
- * one rank-bw update on the fp64 matrix cores per block); 0 where the unblocked sweep is used (N < 256,
- * MI32_ALGO_SWEEP, pivoting off) */
+ * one rank-bw update on the fp64 matrix cores per block; 64, 128 or 256), or, with pivoting off, of the fp64 no-pivot
+ * path (64 or 128); 0 where the unblocked sweep is used (N < 256, N < 512 with pivoting off, MI32_ALGO_SWEEP) */
 int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width);
 
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and

@@ -17,6 +17,10 @@ inline std::vector<double> matrix_inv_64(std::vector<double> matrix_vector, int 
 
 // The reference's no-pivot variant (headers.h:11, body matrix_inversion_no_pivots.cpp:10): Gauss-Jordan in double
 // with the diagonal entry as the pivot of every step (findCrr / fixRow / copyCirColumn / fixColumn, kernels :13-70)
-// -- for diagonally dominant inputs.  Same call shape; an empty vector for a bad shape or when a zero / non-finite
-// diagonal entry is met (the reference returns {} when the reduced left half is not exactly I, :670).
+// -- for diagonally dominant inputs.  Same call shape; an empty vector for a bad shape, a non-finite input entry, or
+// when a zero / non-finite diagonal entry is met (the reference returns {} when the reduced left half is not exactly
+// I, :670).  From N = 512 on it runs blocked, the O(N^3) part on the fp64 matrix cores, with every element taken
+// through the reference's own chain of operations: the result is the reference order's, bit for bit, except that a
+// zero multiplier is multiplied through rather than skipped (the sign of a zero entry can differ); the equality
+// assumes finite intermediates.
 std::vector<double> matrix_inversion_no_pivots(std::vector<double> matrix_vector, int matrix_order);

@@ -117,6 +117,9 @@ def load() -> ctypes.CDLL:
     lib.mi32_shard_range.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip]
     lib.mi32_debug_drop_panel_group.restype = ctypes.c_int
     lib.mi32_debug_drop_panel_group.argtypes = [ctypes.c_int]
+    if hasattr(lib, "mi32_debug_dpp_selftest"):  # (tools/ab_bench.py also loads builds older than the self-test)
+        lib.mi32_debug_dpp_selftest.restype = ctypes.c_int
+        lib.mi32_debug_dpp_selftest.argtypes = [vp, vp, ctypes.c_int, vp]
     lib.mi32_matrix_inv_32_batched_multi.restype = ctypes.c_int
     lib.mi32_matrix_inv_32_batched_multi.argtypes = [fp, ctypes.c_int, ctypes.c_int, fp, ip, ctypes.c_int]
     lib.mi32_create.restype = ctypes.c_int

@@ -105,6 +105,8 @@ static void panel_geometry(const BlockedPlan &p, int nrows, int &nt, int &rpt)
     else {
         nt = p.nthreads_panel;
         while (rpt * nt < nrows) rpt *= 2;
+        // 2049 ... 3072 rows at 1024 threads: three rows per lane (a fourth, dead row costs every pivot step its issue)
+        if (nt == 1024 && rpt == 4 && 3 * nt >= nrows) rpt = 3;
     }
 }
 
@@ -298,6 +300,63 @@ __device__ __forceinline__ float lane_bcast(float v, int srclane)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srclane));
 }
 
+// ---- a wave-uniform row of 16 floats in ONE register (entry c in lane c of every row of 16 lanes), used through a
+// DPP source: row_newbcast:c = "lane c of my own row of 16".  Correct on gfx950 -- mi32_debug_dpp_selftest below is the
+// proof -- but NOT used by the panel step: an fp32 FMA with a DPP source issues at two thirds of the plain rate
+// (tools/valu_peak.hip), which cost the 4-rows-per-lane panels 4 us per launch.
+// Both forms read the row register from OTHER lanes: full EXEC only (a disabled source lane delivers no data),
+// row_mask / bank_mask 0xf, and no VALU write of the row register in the two instructions before.
+//   row_fmac<C>:   dst = fma(row[C], -f, dst)  -- the single-rounding FMA of __builtin_fmaf(-f, row[C], dst)
+//   row_select<C>: lane == pick ? row[C] : old
+template <int C>
+__device__ __forceinline__ void row_fmac(float &dst, float row, float f)
+{
+    static_assert(C >= 0 && C < 16, "row_newbcast addresses one row of 16 lanes");
+    asm volatile("v_fmac_f32_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+                 : "+v"(dst) : "v"(row), "v"(f), "n"(C));
+}
+template <int C>
+__device__ __forceinline__ float row_select(float old, float row, int lane, int pick)
+{
+    static_assert(C >= 0 && C < 16, "row_newbcast addresses one row of 16 lanes");
+    asm volatile("v_cmp_ne_u32 vcc, %3, %2\n\t"
+                 "v_cndmask_b32_dpp %0, %1, %0, vcc row_newbcast:%4 row_mask:0xf bank_mask:0xf"
+                 : "+v"(old) : "v"(row), "v"(lane), "s"(pick), "n"(C) : "vcc");
+    return old;
+}
+
+// The self-test: one wave per case, in[case][3][64] = {row, f, acc} words; out[case][16][4][64] = for every C:
+// row_fmac, __builtin_fmaf on the entry fetched with ds_bpermute, row_select, the same select in plain C++.
+// Words 0 / 1 and 2 / 3 must agree bit for bit.
+template <int C>
+__device__ __forceinline__ void dpp_selftest_case(float row, float f, float acc, int lane, int pick, unsigned *out)
+{
+    const float rc = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane & ~15) + C) * 4, __float_as_int(row)));
+    float d = acc;
+    row_fmac<C>(d, row, f);
+    const int pk = (pick + 5 * C) & 63;
+    out[(C * 4 + 0) * 64 + lane] = __float_as_uint(d);
+    out[(C * 4 + 1) * 64 + lane] = __float_as_uint(__builtin_fmaf(-f, rc, acc));
+    out[(C * 4 + 2) * 64 + lane] = __float_as_uint(row_select<C>(acc, row, lane, pk));
+    out[(C * 4 + 3) * 64 + lane] = __float_as_uint(lane == pk ? rc : acc);
+}
+template <int... Cs>
+__device__ __forceinline__ void dpp_selftest_cases(float row, float f, float acc, int lane, int pick, unsigned *out,
+                                                   std::integer_sequence<int, Cs...>)
+{
+    (dpp_selftest_case<Cs>(row, f, acc, lane, pick, out), ...);
+}
+__global__ __launch_bounds__(64) void dpp_selftest_kernel(const unsigned *__restrict__ in, unsigned *__restrict__ out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned *q = in + (size_t)blockIdx.x * 3 * 64;
+    // (the loads' s_waitcnt stands between them and the first DPP read)
+    const float row = __uint_as_float(q[lane]), f = __uint_as_float(q[64 + lane]), acc = __uint_as_float(q[128 + lane]);
+    const int pick = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 7u) & 63);
+    dpp_selftest_cases(row, f, acc, lane, pick, out + (size_t)blockIdx.x * 16 * 4 * 64,
+                       std::make_integer_sequence<int, 16>{});
+}
+
 // ---- the pivot-row strip: BK pivot steps on the BK pivot rows alone, one column per quad ------------
 // Every column outside a (sub-)panel sees that panel's BK pivot steps as
 //     u_m = x[row of step m] / pivot_m                       fixRow,    mat_inv_32.cpp:138-150
@@ -464,11 +523,17 @@ struct __attribute__((aligned(16))) PanelShared {
 };
 
 // which matrix row register row k of thread tid holds: V consecutive rows per thread so that the
-// compact panel is loaded and stored with one 4*V-byte access per column
+// compact panel is loaded and stored with one 4*V-byte access per column (three rows per lane: V = 1 -- a vector of
+// three floats occupies 16 bytes)
+template <int RPT>
+constexpr int panel_vec()
+{
+    return RPT == 3 ? 1 : (RPT < 4 ? RPT : 4);
+}
 template <int NT, int RPT>
 __device__ __forceinline__ int panel_row(int tid, int k)
 {
-    constexpr int V = RPT < 4 ? RPT : 4;
+    constexpr int V = panel_vec<RPT>();
     return (k / V) * (V * NT) + V * tid + (k % V);
 }
 
@@ -547,7 +612,7 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
 #pragma unroll
         for (int k = 0; k < RPT; ++k) mt_store<1>(mtp + (size_t)R * mtld, (unsigned)moff[k] * 4u, col[k]);
     } else {
-        constexpr int V = RPT < 4 ? RPT : 4;
+        constexpr int V = panel_vec<RPT>();
         typedef float mvecV __attribute__((ext_vector_type(V)));
         const unsigned voff = (unsigned)(wave_u * 64 + lane) * (4u * V);
 #pragma unroll
@@ -828,7 +893,7 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
     static_assert(!(FUSED && MULTI), "multi-workgroup panels are never fused");
     if (matrix_given_up(A.guard, b)) return;
     const bool has_prev = FUSED && A.has_prev;
-    constexpr int V = RPT < 4 ? RPT : 4;
+    constexpr int V = panel_vec<RPT>();
     constexpr int NW = NT / 64;
     typedef float vecV __attribute__((ext_vector_type(V)));
     typedef int ivecV __attribute__((ext_vector_type(V)));
@@ -2004,10 +2069,11 @@ static hipError_t with_constant(int v, F &&f)
 // Fused launches exist for the panel geometries of at most kFusedRows rows (see "Fused mode" in blocked_invert).
 static constexpr int kFusedRows = 2048;
 // The instances of gj_subpanel_kernel: every panel geometry make_blocked_plan can give a block -- one row per lane at
-// 256 threads; at 512 threads at most 8 rows per lane and 128 floats of slab, at 1024 threads at most 64 floats.
+// 256 threads; at 512 threads at most 8 rows per lane and 128 floats of slab, at 1024 threads at most 64 floats
+// (three rows per lane: at 1024 threads only).
 constexpr bool subpanel_instance(int nt, int rpt, int w, bool fused)
 {
-    const bool fits = nt == 256 ? rpt == 1 : nt == 512 ? (rpt <= 8 && rpt * w <= 128) : rpt * w <= 64;
+    const bool fits = nt == 256 ? rpt == 1 : nt == 512 ? (rpt != 3 && rpt <= 8 && rpt * w <= 128) : rpt * w <= 64;
     return fits && (!fused || nt * rpt <= kFusedRows);
 }
 
@@ -2062,7 +2128,7 @@ static hipError_t dispatch_subpanel(const BlockedPlan &p, int w, const SubpanelA
     A.upd_wgs = A.batch * (tiles / (nt / 256));
     const int nwgs = A.batch + A.upd_wgs + (os_tiles + nt / 256 - 1) / (nt / 256);
     return with_constant<256, 512, 1024>(nt, [&](auto NT) {
-        return with_constant<1, 2, 4, 8, 16>(rpt, [&](auto RPT) {
+        return with_constant<1, 2, 3, 4, 8, 16>(rpt, [&](auto RPT) {
             return with_constant<4, 8, 16, 32>(w, [&](auto W) {
                 return with_constant<0, 1>(A.upd_on, [&](auto FUSED) {
                     return launch_subpanel<NT, RPT, W, FUSED != 0>(A, nwgs, stream);
@@ -2385,6 +2451,14 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                            d_inv, d_status);
     }
     return hipGetLastError();
+}
+
+// tests only: runs dpp_selftest_kernel on `ncases` waves.  dev_in: ncases x 3 x 64 words, dev_out: ncases x 16 x 4 x 64.
+extern "C" int mi32_debug_dpp_selftest(const unsigned *dev_in, unsigned *dev_out, int ncases, void *stream)
+{
+    if (dev_in == nullptr || dev_out == nullptr || ncases < 1) return 1;
+    hipLaunchKernelGGL(dpp_selftest_kernel, dim3(ncases), dim3(64), 0, (hipStream_t)stream, dev_in, dev_out);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
 #ifdef MI32_PANEL_STAMPS

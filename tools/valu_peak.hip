@@ -1,10 +1,23 @@
 // Diagnostic (not part of the product): fp32 VALU issue rates on this device -- v_fma_f32 against v_pk_fma_f32
 // (two fp32 lanes per instruction) in the shape the panel kernel uses them: 1024-thread workgroups, one per CU,
-// 64 independent accumulators per lane, a broadcast multiplier.
+// 64 independent accumulators per lane, a broadcast multiplier; and against v_fmac_f32 with a DPP source
+// (row_newbcast: the 16 row entries in ONE register instead of 16).
 // Build: hipcc -O3 --offload-arch=gfx950 tools/valu_peak.hip -o tools/valu_peak
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <utility>
 typedef float f2v __attribute__((ext_vector_type(2)));
+
+template <int C>
+__device__ __forceinline__ void dpp_fmac(float &a, float row, float f)
+{
+    asm volatile("v_fmac_f32_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(a) : "v"(row), "v"(f), "n"(C));
+}
+template <int... Cs>
+__device__ __forceinline__ void dpp_fmac_row(float *a, float row, float f, std::integer_sequence<int, Cs...>)
+{
+    (dpp_fmac<Cs>(a[Cs], row, f), ...);
+}
 
 template <int MODE, int NT>
 __global__ __launch_bounds__(NT) void valu_loop(float *out, int iters, float seed)
@@ -22,6 +35,8 @@ __global__ __launch_bounds__(NT) void valu_loop(float *out, int iters, float see
             if (MODE == 0) {
 #pragma unroll
                 for (int c = 0; c < 16; ++c) a[k * 16 + c] = __builtin_fmaf(-f[k], p[c], a[k * 16 + c]);
+            } else if (MODE == 2) {
+                dpp_fmac_row(&a[k * 16], p[(int)(threadIdx.x & 15)], f[k], std::make_integer_sequence<int, 16>{});
             } else {
                 const f2v nf = {-f[k], -f[k]};
 #pragma unroll
@@ -69,8 +84,10 @@ int main()
 {
     run<0, 1024>("v_fma_f32", 256);
     run<1, 1024>("v_pk_fma_f32", 256);
+    run<2, 1024>("v_fmac_f32_dpp row_newbcast", 256);
     run<0, 256>("v_fma_f32", 256);
     run<1, 256>("v_pk_fma_f32", 256);
+    run<2, 256>("v_fmac_f32_dpp row_newbcast", 256);
     run<0, 256>("v_fma_f32", 1024);
     run<1, 256>("v_pk_fma_f32", 1024);
     return 0;

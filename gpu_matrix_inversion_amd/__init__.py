@@ -7,6 +7,7 @@ C++ drop-in: include/mat_inv_32.h) and this thin Python host mirror.
 from ._lib import (  # noqa: F401
     ALGO_AUTO,
     ALGO_BLOCKED,
+    ALGO_RESIDENT,
     ALGO_SWEEP,
     MI32_BAD_SHAPE,
     MI32_OK,

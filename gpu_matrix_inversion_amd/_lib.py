@@ -23,7 +23,8 @@ MI32_RUNTIME_ERROR = 3
 ALGO_AUTO = 0
 ALGO_SWEEP = 1
 ALGO_BLOCKED = 2
-ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED}
+ALGO_RESIDENT = 3
+ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "resident": ALGO_RESIDENT}
 KERNEL_CLASSES = ("init", "sweep_step", "panel", "update_in_block", "update_rank_bw", "finish", "panel_transpose")
 
 # every symbol include/mat_inv_32_c.h declares
@@ -56,6 +57,7 @@ C_ABI_SYMBOLS = (
     "mi32_resolve_blocking_f64",
     "mi32_resolve_blocking",
     "mi32_resolve_panel_widths",
+    "mi32_resolve_resident",
     "mi32_dominant_kernel",
     "mi32_last_error",
     "mi32_version",
@@ -173,6 +175,8 @@ def load() -> ctypes.CDLL:
     lib.mi32_resolve_blocking_f64.argtypes = [vp, ctypes.c_int, ip]
     lib.mi32_resolve_panel_widths.restype = ctypes.c_int
     lib.mi32_resolve_panel_widths.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
+    lib.mi32_resolve_resident.restype = ctypes.c_int
+    lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
     lib.mi32_dominant_kernel.restype = ctypes.c_char_p
     lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
     lib.mi32_last_error.restype = ctypes.c_char_p

@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_SWEEP, MI32_OK, MI32_SINGULAR, Mi32Error
+from ._lib import ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_RESIDENT, ALGO_SWEEP, MI32_OK, MI32_SINGULAR, Mi32Error
 
 
 def _algo_id(algo) -> int:
@@ -224,6 +224,14 @@ class Inverter:
         bw = ctypes.c_int()
         _lib.check(self._lib.mi32_resolve_blocking_f64(self._h, int(n), ctypes.byref(bw)), "mi32_resolve_blocking_f64")
         return bw.value
+
+    def resolved_resident(self, n: int, elem_bytes: int = 4):
+        """(lanes per matrix, largest order) of the register-resident path (``algo="resident"``): 8 / 16 / 32 / 64
+        lanes for ``1 <= n <= 64``, 0 above, where that algorithm falls back to what ``auto`` resolves to."""
+        lanes, top = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._lib.mi32_resolve_resident(self._h, int(n), int(elem_bytes), ctypes.byref(lanes),
+                                                   ctypes.byref(top)), "mi32_resolve_resident")
+        return lanes.value, top.value
 
     def resolved_panel_widths(self, n: int, batch: int = 1):
         """Sub-panel width of every outer block (narrow while many rows are still candidates)."""

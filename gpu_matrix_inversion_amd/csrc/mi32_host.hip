@@ -302,6 +302,8 @@ static int resolve_algo(const mi32_context *h, int n)
 {
     int algo = h ? h->algo : MI32_ALGO_AUTO;
     if (algo == MI32_ALGO_AUTO) algo = env_int("MI32_ALGO", MI32_ALGO_AUTO);
+    // the register-resident path holds orders up to 64; above, RESIDENT resolves to what AUTO resolves to
+    if (algo == MI32_ALGO_RESIDENT && n <= kResidentMaxOrder) return algo;
     // the no-pivot variant (fp32): blocked from 512 rows on (the W x W diagonal block is its whole "panel")
     const int cross = (h && !h->pivoting) ? 512 : 32;
     if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;  // measured cross-over on MI355X
@@ -328,7 +330,8 @@ static BlockedPlan plan_blocked(const mi32_context *h, int n, int batch)
 static size_t ws_bytes_for(const mi32_context *h, int n, int batch, int algo)
 {
     size_t a;
-    if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
+    if (algo == MI32_ALGO_RESIDENT) a = 0;  // no working copy: only the residual check needs a workspace
+    else if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
     else {
         const BlockedPlan p = plan_blocked(h, n, batch);
         // a batch that may be split in two halves (mi32_inv_device) carves one workspace per half
@@ -476,7 +479,7 @@ int mi32_set_stream(mi32_handle_t h, void *hip_stream)
 
 int mi32_set_algo(mi32_handle_t h, int algo)
 {
-    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_BLOCKED) return MI32_BAD_SHAPE;
+    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_RESIDENT) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     h->algo = algo;
     return MI32_OK;
@@ -535,9 +538,19 @@ int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, in
     return MI32_OK;
 }
 
+int mi32_resolve_resident(mi32_handle_t /*h*/, int n, int elem_bytes, int *lanes_per_matrix, int *max_order)
+{
+    if (n <= 0 || (elem_bytes != 4 && elem_bytes != 8)) return MI32_BAD_SHAPE;
+    if (lanes_per_matrix) *lanes_per_matrix = resident_lanes(n);
+    if (max_order) *max_order = kResidentMaxOrder;
+    return MI32_OK;
+}
+
 const char *mi32_dominant_kernel(int algo)
 {
-    return algo == MI32_ALGO_SWEEP ? "gj_sweep_step_kernel" : "gj_rank_bw2_kernel";
+    return algo == MI32_ALGO_RESIDENT ? "gj_resident_kernel"
+           : algo == MI32_ALGO_SWEEP  ? "gj_sweep_step_kernel"
+                                      : "gj_rank_bw2_kernel";
 }
 
 int mi32_reserve(mi32_handle_t h, int n, int batch)
@@ -570,7 +583,9 @@ int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *
     rc = status_buffer(h, d_status, batch, &d_status);
     if (rc != MI32_OK) return rc;
     hipError_t e;
-    if (algo == MI32_ALGO_SWEEP)
+    if (algo == MI32_ALGO_RESIDENT)
+        e = resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
+    else if (algo == MI32_ALGO_SWEEP)
         e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     else {
         BlockedExec ex;
@@ -616,6 +631,7 @@ static int resolve_algo_f64(const mi32_context *h, int n)
 {
     int algo = h ? h->algo : MI32_ALGO_AUTO;
     if (algo == MI32_ALGO_AUTO) algo = env_int("MI32_ALGO", MI32_ALGO_AUTO);
+    if (algo == MI32_ALGO_RESIDENT && n <= kResidentMaxOrder) return algo;
     const int cross = (h && !h->pivoting) ? 512 : 256;
     if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
     return algo;
@@ -637,7 +653,15 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
     if (!h || !d_a || !d_inv || n <= 0 || batch <= 0 || d_a == d_inv) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
-    const bool blocked = resolve_algo_f64(h, n) == MI32_ALGO_BLOCKED;
+    const int algo = resolve_algo_f64(h, n);
+    if (algo == MI32_ALGO_RESIDENT) {
+        int rc = status_buffer(h, d_status, batch, &d_status);
+        if (rc != MI32_OK) return rc;
+        const hipError_t e = resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
+        if (e != hipSuccess) return fail(e, "kernel launch");
+        return MI32_OK;
+    }
+    const bool blocked = algo == MI32_ALGO_BLOCKED;
     const bool nopivot = blocked && !h->pivoting;
     const Blocked64Plan bp = plan_blocked64(h, n);
     const NoPivot64Plan npp = plan_nopivot64(h, n);

@@ -153,6 +153,15 @@ size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch);
 hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
                             hipStream_t stream, Profiler *prof);
 
+// register-resident path (mi32_resident.hip): orders up to kResidentMaxOrder, one launch, no workspace.  A group of
+// resident_lanes(n) lanes (8 / 16 / 32 / 64; 0 when the order is out of range) holds one matrix; d_status must not
+// be null.  Bit-identical to the sweep path.
+static constexpr int kResidentMaxOrder = 64;
+int resident_lanes(int n);
+template <typename T>
+hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                           bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

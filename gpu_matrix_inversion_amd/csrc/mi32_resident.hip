@@ -1,0 +1,206 @@
+// mi32_resident.hip -- the register-resident path for large batches of small matrices (n <= 64), gfx950.
+//
+// One launch per call: a group of L lanes (L = 8, 16, 32 or 64, the smallest that is >= n) owns one matrix from
+// the first pivot search to the un-permuted inverse; a wave holds 64 / L matrices, a workgroup four waves.  One
+// global read and one global write per element, no workspace, no batch index in blockIdx.y / .z (the matrix index
+// is a 64-bit function of blockIdx.x alone).
+//
+// Layout: lane j of the group holds COLUMN j of the working matrix, a[0 .. L) in registers, the N x N in-place
+// form of mi32_sweep.hip (column r holds, from step r on, the one right-half column of [A|I] that went dense at
+// step r).  Padding never reaches a stored value: a row >= n is NaN in every column -- a NaN never wins a pivot
+// search, and a row only ever changes itself unless it is the pivot row -- and a lane >= n holds zeros, is read by
+// no step r < n and never stores.
+//
+// Per pivot step r, the five kernels of the reference (mat_inv_32.cpp:317-362) in the arithmetic of
+// gj_sweep_step_kernel, hence the same bits as the CPU oracle:
+//   1. maxPivot / finalMaxPivot: column r lives in ONE lane, so the search is a scan over that lane's registers
+//      (every lane scans its own column, lane r's answer is broadcast): PivotRec<T> of mi32_sweep_common.h
+//   2. pivotElements: the pivot row's entry of this lane's column is picked by a compare/select chain on p (a
+//      run-time register index would go through scratch); slot p receives the old row r
+//   3. fixRow: ONE IEEE division per lane and step, prn = a[p][j] / piv; column r's lane takes 1 / piv
+//   4. fixColumn: row i != r takes its multiplier f = old a[i][r] from column r's lane of the group; column r's own
+//      entry becomes 0 first (the implicit identity column); a[i] = fma(-f, prn, a[i]), skipped when f == 0
+//   5. a zero / NaN / infinite pivot, or a non-finite input entry, flags the member MI32_SINGULAR
+// The column permutation of the sweep (working column c holds inverse column orig[c]) is carried in the lanes
+// (lane c holds orig[c]) and applied by the store.
+//
+// The loops over ROWS are fully unrolled, so every register index is a compile-time constant (no scratch).  The
+// loop over pivot STEPS is unrolled for L <= 16 only: for L = 32 / 64 the unrolled body would be 1024 / 4096 row
+// updates of straight-line code per instance (~75 / ~300 KB, more than an instruction cache holds, times 8
+// instances), so there r is a run-time, wave-uniform value that is only ever compared with the compile-time row
+// index or used as a lane index.
+#include "mi32_internal.h"
+#include "mi32_sweep_common.h"
+
+namespace mi32 {
+
+static constexpr int kResidentThreads = 256;
+
+int resident_lanes(int n) { return n <= 0 || n > kResidentMaxOrder ? 0 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+
+// the value lane `src` of this lane's group of L holds.  L = 64: the group is the wave and every caller's src is
+// wave-uniform, so this is a v_readlane into a scalar register; smaller groups go through ds_bpermute.
+template <int L>
+__device__ __forceinline__ int group_bcast(int v, int src)
+{
+    if constexpr (L == 64) return __builtin_amdgcn_readlane(v, src);
+    else return __shfl(v, src, L);
+}
+template <int L>
+__device__ __forceinline__ float group_bcast(float v, int src)
+{
+    return __int_as_float(group_bcast<L>(__float_as_int(v), src));
+}
+template <int L>
+__device__ __forceinline__ double group_bcast(double v, int src)
+{
+    return __hiloint2double(group_bcast<L>(__double2hiint(v), src), group_bcast<L>(__double2loint(v), src));
+}
+
+// never a pivot candidate (PivotRec<T>::make turns a NaN into "no candidate")
+__device__ __forceinline__ float not_a_candidate(float) { return __builtin_nanf(""); }
+__device__ __forceinline__ double not_a_candidate(double) { return __builtin_nan(""); }
+
+// A wave-uniform row number as a vector register the compiler cannot see through.  With a run-time step the row
+// tests `i >= r`, `i == r`, `i == p` of an unrolled row loop are otherwise evaluated on the scalar unit, all of them
+// ahead of the loop, and their 2 L mask registers are spilled to vector-register lanes (v_writelane / v_readlane
+// around every use: measured in the code object, 204 registers at L = 64).  As a vector compare each test is one
+// instruction whose mask is consumed by the next.  A compile-time row number stays what it is.
+template <int L>
+__device__ __forceinline__ int row_number(int r)
+{
+    if constexpr (L > 16) asm volatile("" : "+v"(r));
+    return r;
+}
+
+// One pivot step on the group's matrix.  r: the step (a compile-time constant after unrolling for L <= 16).
+template <typename T, int L, bool PIVOT>
+__device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int j, int &orig, bool &bad)
+{
+    // 1. the pivot row p of column r: rows >= n hold NaN and are no candidates, like the rows above r
+    int p = r;
+    if constexpr (PIVOT) {
+        const int rv = row_number<L>(r);
+        PivotRec<T> best = PivotRec<T>::none();
+#pragma unroll
+        for (int i = 0; i < L; ++i) {
+            const T cand = (i >= rv) ? a[i] : not_a_candidate(T(0));
+            best = PivotRec<T>::best_of(PivotRec<T>::make(cand, i), best);
+        }
+        p = group_bcast<L>(best.row(r), r);
+    }
+    // 2. pivotElements: this column's entry of row r, then its entry of row p (the pivot row), whose slot
+    //    receives the old row r
+    T ar = T(0);
+    {
+        const int rv = row_number<L>(r);
+#pragma unroll
+        for (int i = 0; i < L; ++i) ar = (i == rv) ? a[i] : ar;
+    }
+    T ap = ar;
+    if constexpr (PIVOT) {
+        const int pv = row_number<L>(p);
+#pragma unroll
+        for (int i = 0; i < L; ++i) {
+            ap = (i == pv) ? a[i] : ap;
+            a[i] = (i == pv) ? ar : a[i];
+            // both selects of a row next to its compare: scheduled apart, the L masks stay live and are spilled
+            if constexpr (L > 16) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // 3. fixRow: the pivot is column r's entry of row p (mat_inv_32.cpp:70,129-130)
+    const T piv = group_bcast<L>(ap, r);
+    bad = bad || piv == T(0) || piv - piv != T(0);  // zero, NaN or infinite pivot
+    const bool is_r = (j == r);
+    const T prn = (is_r ? T(1) : ap) / piv;
+    // 4. fixColumn; slot r takes the normalised pivot row
+    {
+        const int rv = row_number<L>(r);
+#pragma unroll
+        for (int i = 0; i < L; ++i) {
+            const T f = group_bcast<L>(a[i], r);    // the multiplier: old a[i][r]
+            const T base = is_r ? T(0) : a[i];      // the implicit identity column's entry in this row
+            const T upd = (f != T(0)) ? fma_t(-f, prn, base) : base;
+            a[i] = (i == rv) ? prn : upd;
+        }
+    }
+    // the column permutation: orig[r] <-> orig[p]
+    if constexpr (PIVOT) {
+        const int o_r = group_bcast<L>(orig, r), o_p = group_bcast<L>(orig, p);
+        orig = is_r ? o_p : (j == p) ? o_r : orig;
+    }
+}
+
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                       int n, int batch, int *__restrict__ status)
+{
+    constexpr int kGroups = kResidentThreads / L;  // matrices per workgroup
+    const int j = threadIdx.x & (L - 1);
+    const long long b = (long long)blockIdx.x * kGroups + threadIdx.x / L;
+    // a group past the end of the batch runs the steps on zeros (the cross-lane operations are whole-wave) and
+    // neither loads nor stores
+    const bool mine = b < (long long)batch && j < n;
+    const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
+    T a[L];
+    bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        if (i < n) {
+            a[i] = mine ? in[mat + (size_t)i * n + j] : T(0);
+            bad = bad || (a[i] - a[i] != T(0));
+        } else {
+            a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
+        }
+    }
+    int orig = j;
+    if constexpr (L <= 16) {
+#pragma unroll
+        for (int r = 0; r < L; ++r)
+            if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);  // n is wave-uniform: a scalar branch
+    } else {
+#pragma unroll 1
+        for (int r = 0; r < n; ++r) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int i = 0; i < L; ++i)
+        if (i < n) out[mat + (size_t)i * n + orig] = a[i];
+    // status[b] was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
+    if (bad) status[b] = MI32_SINGULAR;
+}
+
+template <typename T, int L>
+static void resident_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting)
+{
+    constexpr int kGroups = kResidentThreads / L;
+    const dim3 grid((unsigned)(((long long)batch + kGroups - 1) / kGroups));
+    if (pivoting)
+        hipLaunchKernelGGL((gj_resident_kernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n, batch,
+                           d_status);
+    else
+        hipLaunchKernelGGL((gj_resident_kernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n, batch,
+                           d_status);
+}
+
+template <typename T>
+hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                           bool pivoting)
+{
+    const int lanes = resident_lanes(n);
+    if (lanes == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream);  // MI32_OK
+    if (e != hipSuccess) return e;
+    ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
+    switch (lanes) {
+        case 8: resident_launch<T, 8>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 16: resident_launch<T, 16>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 32: resident_launch<T, 32>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        default: resident_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+    }
+    return hipGetLastError();
+}
+template hipError_t resident_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
+template hipError_t resident_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+
+}  // namespace mi32

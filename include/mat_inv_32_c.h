@@ -45,7 +45,14 @@ typedef enum mi32_algo {
      * updates on the fp32 matrix cores (v_mfma_f32_32x32x2_f32); the pivot
      * search / swap / normalise / eliminate steps run on a register-resident
      * panel.  Equal to SWEEP up to fp32 rounding. */
-    MI32_ALGO_BLOCKED = 2
+    MI32_ALGO_BLOCKED = 2,
+    /* Large batches of small matrices (n <= 64): one launch in which a group of 8 / 16 / 32 / 64 lanes keeps one
+     * matrix in registers from the first pivot search to the un-permuted inverse -- one global read and one
+     * global write per element, no workspace, any batch size the buffers hold (the other two paths stop at
+     * 65535 members).  The arithmetic of SWEEP, element by element: bit-identical to the CPU oracle, in fp32
+     * and fp64, with and without pivoting.  Never chosen by AUTO; for n > 64 it resolves to what AUTO
+     * resolves to. */
+    MI32_ALGO_RESIDENT = 3
 } mi32_algo;
 
 typedef struct mi32_context *mi32_handle_t;
@@ -137,7 +144,8 @@ int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, in
 /* When enabled, every kernel launch of this context is bracketed by two HIP events
  * recorded on the launch stream.  mi32_get_profile synchronises those events and returns,
  * per kernel class, the summed milliseconds and the number of launches since the last
- * call.  Classes (MI32_KC_*): 0 init (makeAugmented), 1 sweep step, 2 panel steps,
+ * call.  Classes (MI32_KC_*): 0 init (makeAugmented), 1 sweep step, 2 panel steps (and
+ * the one launch of the register-resident path),
  * 3 in-block rank-w update, 4 rank-bw update (fp32 MFMA), 5 finish (getInverted),
  * 6 multiplier transposition in front of each rank-bw update (its A operand). */
 #define MI32_KC_COUNT 7
@@ -174,6 +182,11 @@ int mi32_resolve_blocking(mi32_handle_t h, int n, int batch, int *panel_width, i
  * first blocks of a large matrix use narrower sub-panels): *nblocks receives the number of outer blocks,
  * widths[0 .. min(capacity, *nblocks)) their sub-panel widths. */
 int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, int capacity, int *nblocks);
+/* The register-resident path (MI32_ALGO_RESIDENT), answered without a device (h may be NULL): *lanes_per_matrix =
+ * lanes that hold one matrix of this order (8 / 16 / 32 / 64 for 1 <= n <= 64, 0 above: RESIDENT falls back
+ * there), *max_order = the largest order it takes (64).  elem_bytes: 4 (fp32) or 8 (fp64); anything else, or
+ * n <= 0, is MI32_BAD_SHAPE. */
+int mi32_resolve_resident(mi32_handle_t h, int n, int elem_bytes, int *lanes_per_matrix, int *max_order);
 /* name of the dominant device kernel of that algorithm (for rocprof filtering) */
 const char *mi32_dominant_kernel(int algo);
 /* thread-local description of the last MI32_RUNTIME_ERROR */

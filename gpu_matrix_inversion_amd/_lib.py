@@ -24,7 +24,9 @@ ALGO_AUTO = 0
 ALGO_SWEEP = 1
 ALGO_BLOCKED = 2
 ALGO_RESIDENT = 3
-ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "resident": ALGO_RESIDENT}
+ALGO_WORKGROUP = 4
+ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "resident": ALGO_RESIDENT,
+              "workgroup": ALGO_WORKGROUP}
 KERNEL_CLASSES = ("init", "sweep_step", "panel", "update_in_block", "update_rank_bw", "finish", "panel_transpose")
 
 # every symbol include/mat_inv_32_c.h declares
@@ -58,6 +60,7 @@ C_ABI_SYMBOLS = (
     "mi32_resolve_blocking",
     "mi32_resolve_panel_widths",
     "mi32_resolve_resident",
+    "mi32_resolve_workgroup",
     "mi32_dominant_kernel",
     "mi32_last_error",
     "mi32_version",
@@ -177,6 +180,8 @@ def load() -> ctypes.CDLL:
     lib.mi32_resolve_panel_widths.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
     lib.mi32_resolve_resident.restype = ctypes.c_int
     lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
+    lib.mi32_resolve_workgroup.restype = ctypes.c_int
+    lib.mi32_resolve_workgroup.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
     lib.mi32_dominant_kernel.restype = ctypes.c_char_p
     lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
     lib.mi32_last_error.restype = ctypes.c_char_p

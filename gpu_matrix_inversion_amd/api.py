@@ -22,7 +22,8 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_RESIDENT, ALGO_SWEEP, MI32_OK, MI32_SINGULAR, Mi32Error
+from ._lib import (ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_RESIDENT, ALGO_SWEEP, ALGO_WORKGROUP, MI32_OK, MI32_SINGULAR,
+                   Mi32Error)
 
 
 def _algo_id(algo) -> int:
@@ -232,6 +233,15 @@ class Inverter:
         _lib.check(self._lib.mi32_resolve_resident(self._h, int(n), int(elem_bytes), ctypes.byref(lanes),
                                                    ctypes.byref(top)), "mi32_resolve_resident")
         return lanes.value, top.value
+
+    def resolved_workgroup(self, n: int, elem_bytes: int = 4):
+        """(threads per matrix, register rows per thread, largest order) of the workgroup-resident path
+        (``algo="workgroup"``): 256 threads and 40 / 48 / 56 / 64 rows for ``65 <= n <= 128``; (0, 0, 128) outside,
+        where that algorithm resolves to ``resident`` (``n <= 64``) or to what ``auto`` resolves to."""
+        threads, rows, top = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._lib.mi32_resolve_workgroup(self._h, int(n), int(elem_bytes), ctypes.byref(threads),
+                                                    ctypes.byref(rows), ctypes.byref(top)), "mi32_resolve_workgroup")
+        return threads.value, rows.value, top.value
 
     def resolved_panel_widths(self, n: int, batch: int = 1):
         """Sub-panel width of every outer block (narrow while many rows are still candidates)."""

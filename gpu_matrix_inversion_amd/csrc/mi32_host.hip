@@ -298,12 +298,17 @@ static void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive)
     *exclusive = excl;
 }
 
+// MI32_ALGO_WORKGROUP up to 128 rows: the register-resident path takes the orders it holds, so that one setting serves
+// orders on both sides of 64; above 128 it resolves to what AUTO resolves to
+static int workgroup_or_resident(int n) { return n <= kResidentMaxOrder ? MI32_ALGO_RESIDENT : MI32_ALGO_WORKGROUP; }
+
 static int resolve_algo(const mi32_context *h, int n)
 {
     int algo = h ? h->algo : MI32_ALGO_AUTO;
     if (algo == MI32_ALGO_AUTO) algo = env_int("MI32_ALGO", MI32_ALGO_AUTO);
     // the register-resident path holds orders up to 64; above, RESIDENT resolves to what AUTO resolves to
     if (algo == MI32_ALGO_RESIDENT && n <= kResidentMaxOrder) return algo;
+    if (algo == MI32_ALGO_WORKGROUP && n <= kWorkgroupMaxOrder) return workgroup_or_resident(n);
     // the no-pivot variant (fp32): blocked from 512 rows on (the W x W diagonal block is its whole "panel")
     const int cross = (h && !h->pivoting) ? 512 : 32;
     if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;  // measured cross-over on MI355X
@@ -330,7 +335,7 @@ static BlockedPlan plan_blocked(const mi32_context *h, int n, int batch)
 static size_t ws_bytes_for(const mi32_context *h, int n, int batch, int algo)
 {
     size_t a;
-    if (algo == MI32_ALGO_RESIDENT) a = 0;  // no working copy: only the residual check needs a workspace
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) a = 0;  // no working copy: only the residual check needs a workspace
     else if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
     else {
         const BlockedPlan p = plan_blocked(h, n, batch);
@@ -479,7 +484,7 @@ int mi32_set_stream(mi32_handle_t h, void *hip_stream)
 
 int mi32_set_algo(mi32_handle_t h, int algo)
 {
-    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_RESIDENT) return MI32_BAD_SHAPE;
+    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_WORKGROUP) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     h->algo = algo;
     return MI32_OK;
@@ -546,9 +551,21 @@ int mi32_resolve_resident(mi32_handle_t /*h*/, int n, int elem_bytes, int *lanes
     return MI32_OK;
 }
 
+int mi32_resolve_workgroup(mi32_handle_t /*h*/, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
+                           int *max_order)
+{
+    if (n <= 0 || (elem_bytes != 4 && elem_bytes != 8)) return MI32_BAD_SHAPE;
+    const int rpt = workgroup_rows_per_thread(n);
+    if (threads_per_matrix) *threads_per_matrix = rpt ? 256 : 0;
+    if (rows_per_thread) *rows_per_thread = rpt;
+    if (max_order) *max_order = kWorkgroupMaxOrder;
+    return MI32_OK;
+}
+
 const char *mi32_dominant_kernel(int algo)
 {
-    return algo == MI32_ALGO_RESIDENT ? "gj_resident_kernel"
+    return algo == MI32_ALGO_WORKGROUP ? "gj_workgroup_kernel"
+           : algo == MI32_ALGO_RESIDENT ? "gj_resident_kernel"
            : algo == MI32_ALGO_SWEEP  ? "gj_sweep_step_kernel"
                                       : "gj_rank_bw2_kernel";
 }
@@ -585,6 +602,8 @@ int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *
     hipError_t e;
     if (algo == MI32_ALGO_RESIDENT)
         e = resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
+    else if (algo == MI32_ALGO_WORKGROUP)
+        e = workgroup_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
     else if (algo == MI32_ALGO_SWEEP)
         e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     else {
@@ -632,6 +651,7 @@ static int resolve_algo_f64(const mi32_context *h, int n)
     int algo = h ? h->algo : MI32_ALGO_AUTO;
     if (algo == MI32_ALGO_AUTO) algo = env_int("MI32_ALGO", MI32_ALGO_AUTO);
     if (algo == MI32_ALGO_RESIDENT && n <= kResidentMaxOrder) return algo;
+    if (algo == MI32_ALGO_WORKGROUP && n <= kWorkgroupMaxOrder) return workgroup_or_resident(n);
     const int cross = (h && !h->pivoting) ? 512 : 256;
     if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
     return algo;
@@ -654,10 +674,12 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     const int algo = resolve_algo_f64(h, n);
-    if (algo == MI32_ALGO_RESIDENT) {
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) {
         int rc = status_buffer(h, d_status, batch, &d_status);
         if (rc != MI32_OK) return rc;
-        const hipError_t e = resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
+        const hipError_t e = algo == MI32_ALGO_RESIDENT
+                                 ? resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting)
+                                 : workgroup_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
         if (e != hipSuccess) return fail(e, "kernel launch");
         return MI32_OK;
     }

@@ -162,6 +162,15 @@ template <typename T>
 hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
                            bool pivoting);
 
+// workgroup-resident path (mi32_workgroup.hip): orders kResidentMaxOrder + 1 ... kWorkgroupMaxOrder, one launch, no
+// workspace.  One workgroup of 256 threads holds one matrix in registers, workgroup_rows_per_thread(n) rows per thread
+// (40 / 48 / 56 / 64; 0 when the order is out of range); d_status must not be null.  Bit-identical to the sweep path.
+static constexpr int kWorkgroupMaxOrder = 128;
+int workgroup_rows_per_thread(int n);
+template <typename T>
+hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                            bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

@@ -1,0 +1,214 @@
+// mi32_workgroup.hip -- the workgroup-resident path for large batches of matrices of order 65 ... 128, gfx950.
+//
+// One launch per call: one workgroup of 256 threads owns one matrix from the load to the un-permuted inverse.  One
+// global read and one global write per element, no workspace, the matrix index is blockIdx.x alone (64-bit offsets).
+//
+// Layout: the matrix lives in the workgroup's REGISTERS.  Thread (slab h, column j) -- j = threadIdx.x & 127,
+// h = threadIdx.x >> 7, so a slab is two whole waves -- holds the register slots h * RPT ... h * RPT + RPT - 1 of
+// column j; RPT = 40 / 48 / 56 / 64 gives 80 / 96 / 112 / 128 padded rows.  A slot >= n is NaN in every column (a NaN
+// never wins a pivot search, and a row only ever changes itself unless it is the pivot row); a column >= n holds
+// zeros, is published by no step r < n and never stores.
+//
+// Labels instead of swaps: slot s holds the logical row label[s] (the identity at the start).  pivotElements exchanges
+// two labels and moves no data; the search considers slots with label >= r and breaks ties by the label; the store
+// writes slot s to row label[s].  The column permutation of the sweep (working column c holds inverse column orig[c],
+// orig[r] <-> orig[p] per step) is the inverse of the label permutation (label[s]: r <-> p by value), so column j
+// stores to column slot_of[j], the slot whose label is j, and no second table is carried.
+//
+// LDS carries only the per-step exchange: the published column r (the multiplier column and the search's input) and the
+// normalised pivot row, both double-buffered by the parity of the step, so that a step needs two barriers.  Per step r,
+// in the arithmetic of gj_sweep_step_kernel / resident_step (hence the same bits as the CPU oracle):
+//   a. the two threads of column r publish their slots and then zero them (the implicit identity column's entries)
+//   b. barrier; EVERY wave searches the published column redundantly: lane l builds the PivotRec<T> of slots l and
+//      l + 64 from its copy of their labels, one wave reduction; the labels live in two registers per lane of every
+//      wave (kept identical by construction) and reach LDS once, for the store
+//   c. the slab that holds the pivot slot picks its entry with a wave-uniform switch (scalar branches, no run-time
+//      register index), divides ONCE per column, prn = a[p][j] / piv (column r: 1 / piv), and publishes prn
+//   d. barrier; every slot takes its multiplier f = published column entry by ds_read_b128 at compile-time offsets (all
+//      lanes read one address: a broadcast) and a[i] = fma(-f, prn, a[i]), skipped when f == 0; the pivot slot
+//      is then overwritten with prn by a second wave-uniform switch
+//   e. a zero / NaN / infinite pivot, or a non-finite input entry, flags the member MI32_SINGULAR
+#include "mi32_internal.h"
+#include "mi32_sweep_common.h"
+
+namespace mi32 {
+
+static constexpr int kWorkgroupThreads = 256;
+static constexpr int kWorkgroupColumns = 128;  // column lanes per slab; also the most padded rows (2 x 64)
+
+int workgroup_rows_per_thread(int n)
+{
+    return n <= kResidentMaxOrder || n > kWorkgroupMaxOrder ? 0 : n <= 80 ? 40 : n <= 96 ? 48 : n <= 112 ? 56 : 64;
+}
+
+__device__ __forceinline__ float wg_not_a_candidate(float) { return __builtin_nanf(""); }
+__device__ __forceinline__ double wg_not_a_candidate(double) { return __builtin_nan(""); }
+
+// `X(i)` for i = 0 ... 63 as the cases of a switch; slots >= RPT are discarded at compile time
+#define MI32_WG_CASES8(X, b) X(b + 0) X(b + 1) X(b + 2) X(b + 3) X(b + 4) X(b + 5) X(b + 6) X(b + 7)
+#define MI32_WG_CASES64(X)                                                                                      \
+    MI32_WG_CASES8(X, 0) MI32_WG_CASES8(X, 8) MI32_WG_CASES8(X, 16) MI32_WG_CASES8(X, 24) MI32_WG_CASES8(X, 32) \
+    MI32_WG_CASES8(X, 40) MI32_WG_CASES8(X, 48) MI32_WG_CASES8(X, 56)
+
+// a[slot] for a wave-uniform slot held in a scalar register: a tree of scalar branches around one move
+template <typename T, int RPT>
+__device__ __forceinline__ T wg_pick(const T (&a)[RPT], int slot)
+{
+    T v = T(0);
+#define MI32_WG_PICK(i) \
+    case (i):           \
+        if constexpr ((i) < RPT) v = a[(i)]; \
+        break;
+    switch (slot) { MI32_WG_CASES64(MI32_WG_PICK) default: break; }
+#undef MI32_WG_PICK
+    return v;
+}
+template <typename T, int RPT>
+__device__ __forceinline__ void wg_put(T (&a)[RPT], int slot, T v)
+{
+#define MI32_WG_PUT(i) \
+    case (i):          \
+        if constexpr ((i) < RPT) a[(i)] = v; \
+        break;
+    switch (slot) { MI32_WG_CASES64(MI32_WG_PUT) default: break; }
+#undef MI32_WG_PUT
+}
+
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                         int n, int *__restrict__ status)
+{
+    static_assert(RPT % 8 == 0 && RPT >= 40 && RPT <= 64, "rows per thread");
+    constexpr int P = 2 * RPT;  // padded rows
+    __shared__ __attribute__((aligned(32))) T s_col[2][kWorkgroupColumns];   // published column r, by step parity
+    __shared__ __attribute__((aligned(32))) T s_prow[2][kWorkgroupColumns];  // normalised pivot row, by step parity
+    __shared__ __attribute__((aligned(16))) int s_label[kWorkgroupColumns];  // slot -> logical row, for the store
+    __shared__ int s_slot_of[kWorkgroupColumns];                             // logical row -> slot, for the store
+
+    const int j = threadIdx.x & (kWorkgroupColumns - 1);
+    const int h = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 7);  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int slot0 = h * RPT;
+    const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
+    const bool mine = j < n;
+
+    T a[RPT];
+    bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+        const bool live = mine && slot0 + i < n;
+        const T v = in[live ? mat + (size_t)(slot0 + i) * n + j : mat];  // unconditional: the loads stay in flight together
+        bad = bad || (live && v - v != T(0));
+        a[i] = slot0 + i < n ? (mine ? v : T(0)) : wg_not_a_candidate(T(0));
+    }
+    // this wave's copy of the labels of slots lane and lane + 64 (slots >= P exist in no register: never candidates)
+    int lab0 = lane, lab1 = lane + 64;
+
+#pragma unroll 1
+    for (int r = 0; r < n; ++r) {
+        T *const colp = s_col[r & 1];
+        T *const prowp = s_prow[r & 1];
+        // a. column r: publish, then the implicit identity column takes its place
+        if (j == r) {
+#pragma unroll
+            for (int i = 0; i < RPT; i += 4) {
+                *reinterpret_cast<Vec4<T> *>(&colp[slot0 + i]) = Vec4<T>{a[i], a[i + 1], a[i + 2], a[i + 3]};
+                a[i] = a[i + 1] = a[i + 2] = a[i + 3] = T(0);
+            }
+        }
+        __syncthreads();
+        // b. the pivot slot sp
+        int sp = r;  // without pivoting the labels stay the identity
+        if constexpr (PIVOT) {
+            const T v0 = colp[lane];
+            const T v1 = lane + 64 < P ? colp[lane + 64] : wg_not_a_candidate(T(0));  // (in bounds: 128 entries; a slot >= P is none)
+            const PivotRec<T> k0 = PivotRec<T>::make(lab0 >= r ? v0 : wg_not_a_candidate(T(0)), lab0);
+            const PivotRec<T> k1 = PivotRec<T>::make(lab1 >= r ? v1 : wg_not_a_candidate(T(0)), lab1);
+            const PivotRec<T> best = wave_max_rec(PivotRec<T>::best_of(k0, k1));
+            const int pl = __builtin_amdgcn_readfirstlane(best.row(r));  // the pivot's logical row; r when nothing is a candidate
+            const unsigned long long m0 = __builtin_amdgcn_ballot_w64(lab0 == pl);
+            const unsigned long long m1 = __builtin_amdgcn_ballot_w64(lab1 == pl);
+            sp = m0 ? __builtin_ctzll(m0) : 64 + __builtin_ctzll(m1);
+            // pivotElements: the two labels change places
+            lab0 = lab0 == pl ? r : lab0 == r ? pl : lab0;
+            lab1 = lab1 == pl ? r : lab1 == r ? pl : lab1;
+        }
+        const T piv = colp[sp];
+        bad = bad || piv == T(0) || piv - piv != T(0);  // zero, NaN or infinite pivot
+        const int hp = sp >= RPT ? 1 : 0, lp = sp - hp * RPT;
+        // c. fixRow in the slab that holds the pivot slot
+        if (h == hp) prowp[j] = (j == r ? T(1) : wg_pick<T, RPT>(a, lp)) / piv;
+        __syncthreads();
+        // d. fixColumn
+        const T prn = prowp[j];
+#pragma unroll
+        for (int i = 0; i < RPT; i += 4) {
+            const Vec4<T> f = *reinterpret_cast<const Vec4<T> *>(&colp[slot0 + i]);  // the multipliers: old a[i][r]
+            a[i + 0] = (f.x != T(0)) ? fma_t(-f.x, prn, a[i + 0]) : a[i + 0];
+            a[i + 1] = (f.y != T(0)) ? fma_t(-f.y, prn, a[i + 1]) : a[i + 1];
+            a[i + 2] = (f.z != T(0)) ? fma_t(-f.z, prn, a[i + 2]) : a[i + 2];
+            a[i + 3] = (f.w != T(0)) ? fma_t(-f.w, prn, a[i + 3]) : a[i + 3];
+        }
+        if (h == hp) wg_put<T, RPT>(a, lp, prn);  // the pivot slot takes the normalised pivot row
+    }
+
+    int oc = j;
+    if constexpr (PIVOT) {
+        if (threadIdx.x < 64) {
+            s_label[lane] = lab0;
+            s_label[lane + 64] = lab1;
+            s_slot_of[lab0] = lane;
+            s_slot_of[lab1] = lane + 64;
+        }
+        __syncthreads();
+        oc = s_slot_of[j];
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+        if (slot0 + i < n) {
+            const int row = PIVOT ? s_label[slot0 + i] : slot0 + i;
+            // (both are < n by construction: the labels of the slots < n are a permutation of 0 ... n - 1)
+            if (row < n && oc < n) out[mat + (size_t)row * n + oc] = a[i];
+        }
+    }
+    // status[b] was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
+    if (bad) status[blockIdx.x] = MI32_SINGULAR;
+}
+
+#undef MI32_WG_CASES8
+#undef MI32_WG_CASES64
+
+template <typename T, int RPT>
+static void workgroup_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting)
+{
+    const dim3 grid((unsigned)batch);
+    if (pivoting)
+        hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
+                           d_status);
+    else
+        hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
+                           d_status);
+}
+
+template <typename T>
+hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                            bool pivoting)
+{
+    const int rpt = workgroup_rows_per_thread(n);
+    if (rpt == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream);  // MI32_OK
+    if (e != hipSuccess) return e;
+    ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
+    switch (rpt) {
+        case 40: workgroup_launch<T, 40>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 48: workgroup_launch<T, 48>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 56: workgroup_launch<T, 56>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        default: workgroup_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+    }
+    return hipGetLastError();
+}
+template hipError_t workgroup_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+
+}  // namespace mi32

@@ -52,7 +52,14 @@ typedef enum mi32_algo {
      * 65535 members).  The arithmetic of SWEEP, element by element: bit-identical to the CPU oracle, in fp32
      * and fp64, with and without pivoting.  Never chosen by AUTO; for n > 64 it resolves to what AUTO
      * resolves to. */
-    MI32_ALGO_RESIDENT = 3
+    MI32_ALGO_RESIDENT = 3,
+    /* Large batches of matrices of order 65 ... 128: one launch in which one workgroup of 256 threads keeps one
+     * matrix in its registers (40 / 48 / 56 / 64 rows per thread, so an order-65 matrix does not pay for 128 rows)
+     * from the load to the un-permuted inverse -- one global read and one global write per element, no workspace,
+     * any batch size the buffers hold.  The arithmetic of SWEEP, element by element: bit-identical to the CPU
+     * oracle, in fp32 and fp64, with and without pivoting.  Never chosen by AUTO; n <= 64 resolves to RESIDENT
+     * (one setting serves orders on both sides of 64), n > 128 to what AUTO resolves to. */
+    MI32_ALGO_WORKGROUP = 4
 } mi32_algo;
 
 typedef struct mi32_context *mi32_handle_t;
@@ -145,7 +152,7 @@ int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, in
  * recorded on the launch stream.  mi32_get_profile synchronises those events and returns,
  * per kernel class, the summed milliseconds and the number of launches since the last
  * call.  Classes (MI32_KC_*): 0 init (makeAugmented), 1 sweep step, 2 panel steps (and
- * the one launch of the register-resident path),
+ * the one launch of the register-resident and workgroup-resident paths),
  * 3 in-block rank-w update, 4 rank-bw update (fp32 MFMA), 5 finish (getInverted),
  * 6 multiplier transposition in front of each rank-bw update (its A operand). */
 #define MI32_KC_COUNT 7
@@ -187,6 +194,13 @@ int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, in
  * there), *max_order = the largest order it takes (64).  elem_bytes: 4 (fp32) or 8 (fp64); anything else, or
  * n <= 0, is MI32_BAD_SHAPE. */
 int mi32_resolve_resident(mi32_handle_t h, int n, int elem_bytes, int *lanes_per_matrix, int *max_order);
+/* The workgroup-resident path (MI32_ALGO_WORKGROUP), answered without a device (h may be NULL): *threads_per_matrix =
+ * threads that hold one matrix of this order (256 for 65 <= n <= 128, 0 outside: WORKGROUP resolves to RESIDENT
+ * below and to AUTO's choice above), *rows_per_thread = register rows per thread (40 / 48 / 56 / 64 for orders up to
+ * 80 / 96 / 112 / 128, 0 outside), *max_order = the largest order it takes (128).  elem_bytes: 4 (fp32) or 8 (fp64);
+ * anything else, or n <= 0, is MI32_BAD_SHAPE.  The output pointers are optional. */
+int mi32_resolve_workgroup(mi32_handle_t h, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
+                           int *max_order);
 /* name of the dominant device kernel of that algorithm (for rocprof filtering) */
 const char *mi32_dominant_kernel(int algo);
 /* thread-local description of the last MI32_RUNTIME_ERROR */

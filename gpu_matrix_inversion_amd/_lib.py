@@ -27,6 +27,8 @@ ALGO_RESIDENT = 3
 ALGO_WORKGROUP = 4
 ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "resident": ALGO_RESIDENT,
               "workgroup": ALGO_WORKGROUP}
+# the eight kernel classes of a variable-size batch: the largest order each takes (mi32_vbatch_bin)
+VBATCH_CLASS_TOPS = (8, 16, 32, 64, 80, 96, 112, 128)
 KERNEL_CLASSES = ("init", "sweep_step", "panel", "update_in_block", "update_rank_bw", "finish", "panel_transpose")
 
 # every symbol include/mat_inv_32_c.h declares
@@ -61,6 +63,12 @@ C_ABI_SYMBOLS = (
     "mi32_resolve_panel_widths",
     "mi32_resolve_resident",
     "mi32_resolve_workgroup",
+    "mi32_vbatch_bin",
+    "mi32_vbatch_create",
+    "mi32_vbatch_destroy",
+    "mi32_vbatch_info",
+    "mi32_inv_device_vbatched",
+    "mi32_inv_device_vbatched_f64",
     "mi32_dominant_kernel",
     "mi32_last_error",
     "mi32_version",
@@ -182,6 +190,17 @@ def load() -> ctypes.CDLL:
     lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
     lib.mi32_resolve_workgroup.restype = ctypes.c_int
     lib.mi32_resolve_workgroup.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
+    lib.mi32_vbatch_bin.restype = ctypes.c_int
+    lib.mi32_vbatch_bin.argtypes = [ip, ctypes.c_int, ip, ip]
+    lib.mi32_vbatch_create.restype = ctypes.c_int
+    lib.mi32_vbatch_create.argtypes = [vp, ip, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.mi32_vbatch_destroy.restype = ctypes.c_int
+    lib.mi32_vbatch_destroy.argtypes = [vp]
+    lib.mi32_vbatch_info.restype = ctypes.c_int
+    lib.mi32_vbatch_info.argtypes = [vp, ip, ip]
+    for fn in (lib.mi32_inv_device_vbatched, lib.mi32_inv_device_vbatched_f64):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.mi32_dominant_kernel.restype = ctypes.c_char_p
     lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
     lib.mi32_last_error.restype = ctypes.c_char_p

@@ -172,6 +172,72 @@ def just_inv(K: int, seed=None, inv=None):
     return end - start, a, res
 
 
+def vbatch_bin(orders):
+    """``(perm, class_begin)`` of ``mi32_vbatch_bin`` (host only): the member indices sorted by order (stable) and the
+    nine boundaries of the eight kernel classes in that list."""
+    o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
+    perm = np.empty(o.size, np.int32)
+    begin = np.empty(9, np.int32)
+    ip = ctypes.POINTER(ctypes.c_int)
+    _lib.check(_lib.load().mi32_vbatch_bin(o.ctypes.data_as(ip), int(o.size), perm.ctypes.data_as(ip),
+                                           begin.ctypes.data_as(ip)), "mi32_vbatch_bin")
+    return perm, begin
+
+
+class RaggedPlan:
+    """A batch of members of mixed orders 1 ... 128 (``Inverter.plan_ragged``): the orders, binned once into the eight
+    kernel classes and uploaded to the device.  Immutable; usable any number of times and from any ``Inverter`` on
+    the same device.  ``close()`` frees its device memory and is safe while calls are still in flight."""
+
+    def __init__(self, inverter, orders):
+        torch = inverter._torch
+        o = np.asarray(orders)
+        if o.ndim != 1 or o.size == 0 or not (np.issubdtype(o.dtype, np.integer) or o.dtype == np.bool_):
+            raise ValueError("orders: a non-empty 1-D sequence of integers")
+        if o.min() < 1 or o.max() > 128:
+            raise ValueError("orders must lie in 1 ... 128")
+        self.orders = np.ascontiguousarray(o, dtype=np.int32)
+        self.orders.setflags(write=False)
+        self.batch = int(o.size)
+        self.device = inverter.device
+        self._lib = inverter._lib
+        p = ctypes.c_void_p()
+        _lib.check(self._lib.mi32_vbatch_create(inverter._h, self.orders.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                self.batch, ctypes.byref(p)), "mi32_vbatch_create")
+        self._p = p
+        begin = (ctypes.c_int * 9)()
+        _lib.check(self._lib.mi32_vbatch_info(self._p, None, begin), "mi32_vbatch_info")
+        self.class_counts = [int(begin[k + 1] - begin[k]) for k in range(8)]
+        sq = self.orders.astype(np.int64) ** 2
+        self.flat_size = int(sq.sum())
+        # element offset of every member in the packed layout: member b at sum_{i<b} n_i^2
+        self._offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(sq)[:-1]))).to(self.device)
+        self._ptrs = {}  # (base address, dtype) -> int64 device tensor of member addresses in the packed layout
+
+    def packed_pointers(self, flat):
+        """int64 device tensor of the member addresses inside the packed tensor ``flat`` (cached per base and dtype)."""
+        key = (flat.data_ptr(), flat.dtype)
+        ptrs = self._ptrs.get(key)
+        if ptrs is None:
+            if len(self._ptrs) >= 8:
+                self._ptrs.clear()
+            ptrs = self._offsets * flat.element_size() + flat.data_ptr()
+            self._ptrs[key] = ptrs
+        return ptrs
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self._lib.mi32_vbatch_destroy(self._p)
+            self._p = None
+            self._ptrs = {}
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Inverter:
     """Device-resident inversion of torch CUDA(HIP) tensors through the C ABI handle."""
 
@@ -193,8 +259,12 @@ class Inverter:
             _lib.check(self._lib.mi32_set_blocking(self._h, panel_width, block_width), "mi32_set_blocking")
         if not pivoting:  # the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10): blocked from 512 rows on
             _lib.check(self._lib.mi32_set_pivoting(self._h, 0), "mi32_set_pivoting")
+        self._diag_plan = None  # (orders, plan, block offsets, leading dimensions) of the last inv_diag_blocks call
 
     def close(self):
+        if getattr(self, "_diag_plan", None):
+            self._diag_plan[1].close()
+            self._diag_plan = None
         if getattr(self, "_h", None):
             self._lib.mi32_destroy(self._h)
             self._h = None
@@ -282,6 +352,103 @@ class Inverter:
         _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b, ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(status.data_ptr())), "mi32_inv_device")
         return (out[0] if squeeze else out), status
+
+    # ---- variable-size batches: mixed orders 1 ... 128, each member at its own pointer and leading dimension ----
+    def plan_ragged(self, orders) -> RaggedPlan:
+        """Bin a batch of members of the given orders (a sequence or an int array, each 1 ... 128) once."""
+        return RaggedPlan(self, orders)
+
+    def _check_plan(self, plan):
+        if not isinstance(plan, RaggedPlan) or not plan._p:
+            raise ValueError("expected an open RaggedPlan")
+        if plan.device != self.device:
+            raise ValueError(f"the plan lives on {plan.device}, this Inverter on {self.device}")
+
+    def _check_tensor(self, t, dtype, what, numel=None):
+        if t.device != self.device:
+            raise ValueError(f"{what} is on {t.device}, expected {self.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"{what} is {t.dtype}, expected {dtype}")
+        if t.dim() != 1 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+            raise ValueError(f"{what}: expected a contiguous 1-D tensor" + (f" of {numel} entries" if numel else ""))
+
+    def inv_pointers(self, plan, a_ptrs, out_ptrs, dtype, lda=None, ldout=None, status=None):
+        """The low-level form: ``a_ptrs`` / ``out_ptrs`` are int64 device tensors of ``plan.batch`` member addresses
+        (row-major members of ``dtype`` float32 / float64), ``lda`` / ``ldout`` int32 device tensors of leading
+        dimensions in elements (None: the member's order).  A member may be inverted in place (same address, same
+        leading dimension); members that overlap otherwise are undefined.  Asynchronous on torch's current stream.
+        Returns the status tensor (int32[batch], the caller's member order)."""
+        torch = self._torch
+        self._check_plan(plan)
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype: torch.float32 or torch.float64")
+        self._check_tensor(a_ptrs, torch.int64, "a_ptrs", plan.batch)
+        self._check_tensor(out_ptrs, torch.int64, "out_ptrs", plan.batch)
+        for ld, what in ((lda, "lda"), (ldout, "ldout")):
+            if ld is not None:
+                self._check_tensor(ld, torch.int32, what, plan.batch)
+        if status is None:
+            status = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
+        else:
+            self._check_tensor(status, torch.int32, "status", plan.batch)
+        self._bind_stream()
+        fn = self._lib.mi32_inv_device_vbatched if dtype == torch.float32 else self._lib.mi32_inv_device_vbatched_f64
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(out_ptrs), ptr(ldout), ptr(status)),
+                   "mi32_inv_device_vbatched")
+        return status
+
+    def inv_ragged(self, plan, a_flat, out=None, status=None):
+        """The packed layout: ``a_flat`` is a 1-D float32 / float64 device tensor in which member b holds its
+        ``n_b * n_b`` row-major elements at offset ``sum_{i<b} n_i^2``.  One call, at most eight launches.  ``out``
+        may be ``a_flat`` itself (in place).  Returns ``(out_flat, status)``."""
+        torch = self._torch
+        self._check_plan(plan)
+        if a_flat.dtype not in (torch.float32, torch.float64):
+            raise ValueError("expected a float32 or float64 tensor")
+        self._check_tensor(a_flat, a_flat.dtype, "a_flat")
+        if a_flat.numel() != plan.flat_size:
+            raise ValueError(f"a_flat holds {a_flat.numel()} elements, the plan's members {plan.flat_size}")
+        if out is None:
+            out = torch.empty_like(a_flat)
+        else:
+            self._check_tensor(out, a_flat.dtype, "out", plan.flat_size)
+        status = self.inv_pointers(plan, plan.packed_pointers(a_flat), plan.packed_pointers(out), a_flat.dtype,
+                                   status=status)
+        return out, status
+
+    def inv_diag_blocks(self, m, block_orders, out=None):
+        """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
+        orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
+        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``."""
+        torch = self._torch
+        if m.dtype not in (torch.float32, torch.float64):
+            raise ValueError("expected a float32 or float64 matrix")
+        if m.device != self.device:
+            raise ValueError(f"m is on {m.device}, expected {self.device}")
+        if m.dim() != 2 or m.shape[0] != m.shape[1] or not m.is_contiguous():
+            raise ValueError("expected a contiguous square matrix")
+        orders = np.asarray(block_orders)
+        if orders.ndim != 1 or orders.size == 0 or int(orders.sum()) != m.shape[0]:
+            raise ValueError("block_orders must sum to the matrix order")
+        if out is None:
+            out = torch.zeros_like(m)
+        elif out.shape != m.shape or out.dtype != m.dtype or out.device != m.device or not out.is_contiguous():
+            raise ValueError("out: a contiguous matrix of m's shape, dtype and device")
+        ld = m.shape[0]
+        key = orders.astype(np.int32).tobytes()
+        if self._diag_plan is None or self._diag_plan[0] != key:
+            if self._diag_plan is not None:
+                self._diag_plan[1].close()
+            plan = self.plan_ragged(orders)
+            off = np.concatenate(([0], np.cumsum(orders.astype(np.int64))[:-1]))
+            # block b starts at row off_b, column off_b: element off_b * (ld + 1)
+            self._diag_plan = (key, plan, torch.from_numpy(off * (ld + 1)).to(self.device),
+                               torch.full((orders.size,), ld, dtype=torch.int32, device=self.device))
+        _, plan, elem_off, lds = self._diag_plan
+        status = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
+                                   elem_off * out.element_size() + out.data_ptr(), m.dtype, lda=lds, ldout=lds)
+        return out, status
 
     def set_lookahead(self, enable: bool):
         _lib.check(self._lib.mi32_set_lookahead(self._h, 1 if enable else 0), "mi32_set_lookahead")

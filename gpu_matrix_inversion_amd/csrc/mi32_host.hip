@@ -246,6 +246,17 @@ struct mi32_context {
     std::mutex mu;
 };
 
+// A variable-size batch plan (mi32_vbatch_create): immutable after creation.  The orders and the sorted member list
+// are the only device memory it owns, 8 bytes per member.
+static constexpr int kVbatchClasses = 8;
+struct mi32_vbatch {
+    int device = 0;
+    int batch = 0;
+    int class_begin[kVbatchClasses + 1] = {};  // class k takes d_members[class_begin[k] .. class_begin[k + 1])
+    int *d_orders = nullptr;   // int[batch], the caller's member order
+    int *d_members = nullptr;  // int[batch], member indices in ascending order of their orders (stable)
+};
+
 static thread_local std::string g_last_error;
 // Host-pointer entry points (fp32 and fp64 alike) share the default context's staging buffers and the two
 // timing words below: ONE mutex serialises them all.
@@ -393,7 +404,7 @@ static int ensure_ws(mi32_context *h, size_t bytes)
 
 extern "C" {
 
-int mi32_version(void) { return 120; }
+int mi32_version(void) { return 130; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)
@@ -699,6 +710,137 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
                                    : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     if (e != hipSuccess) return fail(e, "kernel launch");
     return MI32_OK;
+}
+
+// ---- variable-size batches ---------------------------------------------------------------------------------------
+// The kernel class of an order: 0 ... 3 the register-resident instances (8 / 16 / 32 / 64 lanes), 4 ... 7 the
+// workgroup-resident ones (40 / 48 / 56 / 64 rows per thread); resident_lanes and workgroup_rows_per_thread stay the
+// single source of the boundaries.  -1: no instance takes the order.
+static int vbatch_class(int n)
+{
+    switch (resident_lanes(n)) {
+        case 8: return 0;
+        case 16: return 1;
+        case 32: return 2;
+        case 64: return 3;
+        default: break;
+    }
+    switch (workgroup_rows_per_thread(n)) {
+        case 40: return 4;
+        case 48: return 5;
+        case 56: return 6;
+        case 64: return 7;
+        default: return -1;
+    }
+}
+static const int kVbatchLanes[4] = {8, 16, 32, 64};
+static const int kVbatchRows[4] = {40, 48, 56, 64};
+
+int mi32_vbatch_bin(const int *orders, int batch, int *perm, int *class_begin)
+{
+    if (!orders || !perm || !class_begin || batch <= 0) return MI32_BAD_SHAPE;
+    // a counting sort: O(batch), stable
+    int start[kWorkgroupMaxOrder + 2] = {};
+    for (int b = 0; b < batch; ++b) {
+        const int n = orders[b];
+        if (n < 1 || n > kWorkgroupMaxOrder) return MI32_BAD_SHAPE;
+        ++start[n + 1];
+    }
+    for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = 0;
+    for (int n = 1; n <= kWorkgroupMaxOrder; ++n) {
+        class_begin[vbatch_class(n) + 1] += start[n + 1];  // the members of order n (every order 1 ... 128 has a class)
+        start[n + 1] += start[n];                          // start[n]: where the members of order n begin
+    }
+    for (int k = 0; k < kVbatchClasses; ++k) class_begin[k + 1] += class_begin[k];
+    for (int b = 0; b < batch; ++b) perm[start[orders[b]]++] = b;
+    return MI32_OK;
+}
+
+int mi32_vbatch_create(mi32_handle_t h, const int *orders, int batch, mi32_vbatch_t *out)
+{
+    if (!out) return MI32_BAD_SHAPE;
+    *out = nullptr;
+    if (!h || !orders || batch <= 0) return MI32_BAD_SHAPE;
+    std::vector<int> perm((size_t)batch);
+    mi32_vbatch *p = new (std::nothrow) mi32_vbatch();
+    if (!p) return MI32_RUNTIME_ERROR;
+    const int rc = mi32_vbatch_bin(orders, batch, perm.data(), p->class_begin);
+    if (rc != MI32_OK) {
+        delete p;
+        return rc;
+    }
+    p->device = h->device;
+    p->batch = batch;
+    const size_t bytes = (size_t)batch * sizeof(int);
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_orders, bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_members, bytes);
+    // synchronous copies from pageable memory: the host arrays may go away when this returns
+    if (e == hipSuccess) e = hipMemcpy(p->d_orders, orders, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_members, perm.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)mi32_vbatch_destroy(p);
+        return fail(e, "mi32_vbatch_create");
+    }
+    *out = p;
+    return MI32_OK;
+}
+
+int mi32_vbatch_destroy(mi32_vbatch_t p)
+{
+    if (!p) return MI32_OK;
+    (void)hipSetDevice(p->device);
+    // hipFree synchronises with the device: calls that still read the plan finish first
+    if (p->d_orders) (void)hipFree(p->d_orders);
+    if (p->d_members) (void)hipFree(p->d_members);
+    delete p;
+    return MI32_OK;
+}
+
+int mi32_vbatch_info(mi32_vbatch_t p, int *batch, int *class_begin)
+{
+    if (!p) return MI32_BAD_SHAPE;
+    if (batch) *batch = p->batch;
+    if (class_begin)
+        for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = p->class_begin[k];
+    return MI32_OK;
+}
+
+}  // extern "C"
+
+template <typename T>
+static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
+                               T *const *d_inv, const int *d_ldinv, int *d_status)
+{
+    if (!h || !p || !d_a || !d_inv || p->device != h->device) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const int rc = status_buffer(h, d_status, p->batch, &d_status);
+    if (rc != MI32_OK) return rc;
+    MI32_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)p->batch, h->stream));  // MI32_OK
+    const VbatchArgs<T> v{p->d_orders, p->d_members, d_a, d_inv, d_lda, d_ldinv, d_status};
+    for (int k = 0; k < kVbatchClasses; ++k) {
+        const int first = p->class_begin[k], count = p->class_begin[k + 1] - first;
+        if (count == 0) continue;  // a class without members is not launched
+        const hipError_t e = k < 4 ? resident_vinvert(kVbatchLanes[k], v, first, count, h->stream, h->prof, h->pivoting)
+                                   : workgroup_vinvert(kVbatchRows[k - 4], v, first, count, h->stream, h->prof, h->pivoting);
+        if (e != hipSuccess) return fail(e, "kernel launch");
+    }
+    return MI32_OK;
+}
+
+extern "C" {
+
+int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                             float *const *d_inv, const int *d_ldinv, int *d_status)
+{
+    return inv_device_vbatched(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+}
+
+int mi32_inv_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                 double *const *d_inv, const int *d_ldinv, int *d_status)
+{
+    return inv_device_vbatched(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
 }
 
 int mi32_set_profiling(mi32_handle_t h, int enable)

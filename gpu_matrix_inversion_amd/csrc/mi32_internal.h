@@ -171,6 +171,27 @@ template <typename T>
 hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
                             bool pivoting);
 
+// variable-size batches (mi32_vbatch_*): members of any orders 1 ... kWorkgroupMaxOrder, each at its own pointer and
+// leading dimensions, on the two paths above.  Everything here is device memory.  `members` is the plan's list of
+// member indices sorted by order; a launch takes the `count` members from `first` on, which all belong to one kernel
+// instance (lanes per matrix / rows per thread), and looks everything else up by the member index.
+template <typename T>
+struct VbatchArgs {
+    const int *orders;   // int[batch], in the caller's member order
+    const int *members;  // int[batch], the member indices in ascending order of their orders (stable)
+    const T *const *a;   // member pointers, row-major, rows lda[b] elements apart
+    T *const *inv;
+    const int *lda;      // null: orders[b]
+    const int *ldinv;    // null: orders[b]
+    int *status;         // int[batch], zeroed by the host before the launches
+};
+template <typename T>
+hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
+                            bool pivoting);
+template <typename T>
+hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int first, int count, hipStream_t stream,
+                             Profiler *prof, bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

@@ -29,6 +29,9 @@
 // updates of straight-line code per instance (~75 / ~300 KB, more than an instruction cache holds, times 8
 // instances), so there r is a run-time, wave-uniform value that is only ever compared with the compile-time row
 // index or used as a lane index.
+//
+// gj_resident_vkernel is the same body for a variable-size batch (mi32_inv_device_vbatched): every group looks up its
+// member's order, pointers and leading dimensions, and the groups of a wave may differ in order.
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -131,6 +134,55 @@ __device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int 
     }
 }
 
+// One member from the load to the un-permuted inverse, shared by the uniform and the variable-size kernel.  `in` /
+// `out`: the member's first element, rows lda / ldo elements apart; n: this GROUP's order (the same in its L lanes,
+// 0 for a group that owns no member: it neither loads nor stores); nmax: the largest order in the wave, wave-uniform.
+// With UNIFORM_N every group of the wave has the order nmax (or none: the steps then run on zeros) and the step loop
+// is the uniform kernel's; without, a group sits out the steps past its own order -- a step on a finished group would
+// flag it and destroy its result -- and every cross-lane operation of resident_step stays inside its group of L
+// lanes, all of them in or all of them out.  Every element is in registers before the first store.
+template <typename T, int L, bool PIVOT, bool UNIFORM_N>
+__device__ __forceinline__ void resident_member(const T *in, T *out, const int n, const int nmax, const int lda,
+                                                const int ldo, const int j, const bool mine, int *status_word)
+{
+    T a[L];
+    bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        if (i < n) {
+            a[i] = mine ? in[(size_t)i * lda + j] : T(0);
+            bad = bad || (a[i] - a[i] != T(0));
+        } else {
+            a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
+        }
+    }
+    int orig = j;
+    if constexpr (L <= 16) {
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            if constexpr (UNIFORM_N) {
+                if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);  // n is wave-uniform: a scalar branch
+            } else {
+                if (r < nmax) {  // wave-uniform: no wave walks through the steps none of its groups takes
+                    if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+                }
+            }
+        }
+    } else {
+#pragma unroll 1
+        for (int r = 0; r < nmax; ++r) {
+            if constexpr (UNIFORM_N) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+            else if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+        }
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int i = 0; i < L; ++i)
+        if (i < n) out[(size_t)i * ldo + orig] = a[i];
+    // the status word was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
+    if (bad) *status_word = MI32_SINGULAR;
+}
+
 template <typename T, int L, bool PIVOT>
 __global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *__restrict__ in, T *__restrict__ out,
                                                                        int n, int batch, int *__restrict__ status)
@@ -142,32 +194,44 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *
     // neither loads nor stores
     const bool mine = b < (long long)batch && j < n;
     const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
-    T a[L];
-    bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
+    resident_member<T, L, PIVOT, true>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+}
+
+// The variable-size kernel: group g of the launch takes member members[first + g] of the plan's sorted list and reads
+// that member's order, pointers and leading dimensions (a null lda / ldinv: the order).  The list is sorted by order,
+// so the groups of a wave almost always share one; where they do not the wave loops to its largest.  For L = 64 the
+// group is the wave.  The member pointers carry no __restrict__: a member may be inverted in place.
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_vkernel(const VbatchArgs<T> v, const int first,
+                                                                        const int count)
+{
+    constexpr int kGroups = kResidentThreads / L;
+    const int j = threadIdx.x & (L - 1);
+    const long long g = (long long)blockIdx.x * kGroups + threadIdx.x / L;
+    const bool valid = g < (long long)count;
+    const int m = valid ? v.members[(size_t)first + (size_t)g] : 0;
+    int n = valid ? v.orders[m] : 0;
+    if constexpr (L == 64) n = __builtin_amdgcn_readfirstlane(n);  // the group is the wave
+    int nmax = n;
+    if constexpr (L < 64) {
 #pragma unroll
-    for (int i = 0; i < L; ++i) {
-        if (i < n) {
-            a[i] = mine ? in[mat + (size_t)i * n + j] : T(0);
-            bad = bad || (a[i] - a[i] != T(0));
-        } else {
-            a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
+        for (int off = L; off < 64; off <<= 1) {
+            const int o = __shfl_xor(nmax, off, 64);
+            nmax = o > nmax ? o : nmax;
         }
+        nmax = __builtin_amdgcn_readfirstlane(nmax);
     }
-    int orig = j;
-    if constexpr (L <= 16) {
-#pragma unroll
-        for (int r = 0; r < L; ++r)
-            if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);  // n is wave-uniform: a scalar branch
-    } else {
-#pragma unroll 1
-        for (int r = 0; r < n; ++r) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+    const bool mine = valid && j < n;
+    const T *in = nullptr;
+    T *out = nullptr;
+    int lda = n, ldo = n;
+    if (mine) {
+        in = v.a[m];
+        out = v.inv[m];
+        if (v.lda) lda = v.lda[m];
+        if (v.ldinv) ldo = v.ldinv[m];
     }
-    if (!mine) return;
-#pragma unroll
-    for (int i = 0; i < L; ++i)
-        if (i < n) out[mat + (size_t)i * n + orig] = a[i];
-    // status[b] was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
-    if (bad) status[b] = MI32_SINGULAR;
+    resident_member<T, L, PIVOT, false>(in, out, n, nmax, lda, ldo, j, mine, v.status + m);
 }
 
 template <typename T, int L>
@@ -202,5 +266,34 @@ hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_stat
 }
 template hipError_t resident_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
 template hipError_t resident_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+
+template <typename T, int L>
+static void resident_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
+{
+    constexpr int kGroups = kResidentThreads / L;
+    const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
+    if (pivoting)
+        hipLaunchKernelGGL((gj_resident_vkernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
+    else
+        hipLaunchKernelGGL((gj_resident_vkernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
+}
+
+template <typename T>
+hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
+                            bool pivoting)
+{
+    if (count <= 0 || first < 0 || !v.status) return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    switch (lanes) {
+        case 8: resident_vlaunch<T, 8>(v, first, count, stream, pivoting); break;
+        case 16: resident_vlaunch<T, 16>(v, first, count, stream, pivoting); break;
+        case 32: resident_vlaunch<T, 32>(v, first, count, stream, pivoting); break;
+        case 64: resident_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t resident_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t resident_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

@@ -28,6 +28,9 @@
 //      lanes read one address: a broadcast) and a[i] = fma(-f, prn, a[i]), skipped when f == 0; the pivot slot
 //      is then overwritten with prn by a second wave-uniform switch
 //   e. a zero / NaN / infinite pivot, or a non-finite input entry, flags the member MI32_SINGULAR
+//
+// gj_workgroup_vkernel is the same body for a variable-size batch (mi32_inv_device_vbatched): the workgroup looks up
+// its member's order, pointers and leading dimensions from blockIdx.x.
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -74,9 +77,15 @@ __device__ __forceinline__ void wg_put(T (&a)[RPT], int slot, T v)
 #undef MI32_WG_PUT
 }
 
-template <typename T, int RPT, bool PIVOT>
-__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T *__restrict__ in, T *__restrict__ out,
-                                                                         int n, int *__restrict__ status)
+// One member from the load to the un-permuted inverse on the whole workgroup, shared by the uniform and the
+// variable-size kernel.  `in` / `out`: the member's first element, rows lda / ldo elements apart; everything but the
+// thread's own column is workgroup-uniform.  Every element is in registers before the first store (the step loop's
+// barriers lie between), so `out` may be `in`.  ROW_POINTER: the loads walk a pointer advanced by lda instead of forming
+// row * lda + j per row (the same addresses; which of the two keeps the row masks out of the registers differs
+// between the instances, see the variable-size kernel).
+template <typename T, int RPT, bool PIVOT, bool ROW_POINTER>
+__device__ __forceinline__ void workgroup_member(const T *in, T *out, const int n, const int lda, const int ldo,
+                                                 int *status_word)
 {
     static_assert(RPT % 8 == 0 && RPT >= 40 && RPT <= 64, "rows per thread");
     constexpr int P = 2 * RPT;  // padded rows
@@ -89,15 +98,21 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T
     const int h = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 7);  // wave-uniform
     const int lane = threadIdx.x & 63;
     const int slot0 = h * RPT;
-    const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
     const bool mine = j < n;
 
     T a[RPT];
+    const T *rowp = in + ((size_t)slot0 * (size_t)lda + (size_t)j);  // this thread's entry of its slab's first row
     bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
         const bool live = mine && slot0 + i < n;
-        const T v = in[live ? mat + (size_t)(slot0 + i) * n + j : mat];  // unconditional: the loads stay in flight together
+        T v;  // loaded unconditionally (a dead slot reads the member's first element): the loads stay in flight together
+        if constexpr (ROW_POINTER) {
+            v = *(live ? rowp : in);
+            rowp += lda;
+        } else {
+            v = in[live ? (size_t)(slot0 + i) * lda + j : 0];
+        }
         bad = bad || (live && v - v != T(0));
         a[i] = slot0 + i < n ? (mine ? v : T(0)) : wg_not_a_candidate(T(0));
     }
@@ -169,11 +184,35 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T
         if (slot0 + i < n) {
             const int row = PIVOT ? s_label[slot0 + i] : slot0 + i;
             // (both are < n by construction: the labels of the slots < n are a permutation of 0 ... n - 1)
-            if (row < n && oc < n) out[mat + (size_t)row * n + oc] = a[i];
+            if (row < n && oc < n) out[(size_t)row * ldo + oc] = a[i];
         }
     }
-    // status[b] was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
-    if (bad) status[blockIdx.x] = MI32_SINGULAR;
+    // the status word was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
+    if (bad) *status_word = MI32_SINGULAR;
+}
+
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                         int n, int *__restrict__ status)
+{
+    const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
+    workgroup_member<T, RPT, PIVOT, false>(in + mat, out + mat, n, n, n, status + blockIdx.x);
+}
+
+// The variable-size kernel: workgroup g of the launch takes member members[first + g] of the plan's sorted list; its
+// order, pointers and leading dimensions (a null lda / ldinv: the order) are workgroup-uniform values.  The member
+// pointers carry no __restrict__: a member may be inverted in place.
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_vkernel(const VbatchArgs<T> v, const int first)
+{
+    const int m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
+    const int n = __builtin_amdgcn_readfirstlane(v.orders[m]);
+    const int lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[m]) : n;
+    const int ldo = v.ldinv ? __builtin_amdgcn_readfirstlane(v.ldinv[m]) : n;
+    // with a leading dimension of its own the compiler branches around each row's 64-bit address and, at 56 and 64 rows
+    // per thread, spills the row masks to vector-register lanes (fp32 without pivoting: 129 / 132 registers); the row
+    // pointer avoids that there (101 / 118) and costs registers at 40 and 48 rows, hence the switch on RPT
+    workgroup_member<T, RPT, PIVOT, (RPT >= 56)>(v.a[m], v.inv[m], n, lda, ldo, v.status + m);
 }
 
 #undef MI32_WG_CASES8
@@ -210,5 +249,33 @@ hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_sta
 }
 template hipError_t workgroup_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
 template hipError_t workgroup_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+
+template <typename T, int RPT>
+static void workgroup_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
+{
+    const dim3 grid((unsigned)count);
+    if (pivoting)
+        hipLaunchKernelGGL((gj_workgroup_vkernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
+    else
+        hipLaunchKernelGGL((gj_workgroup_vkernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
+}
+
+template <typename T>
+hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int first, int count, hipStream_t stream,
+                             Profiler *prof, bool pivoting)
+{
+    if (count <= 0 || first < 0 || !v.status) return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    switch (rows_per_thread) {
+        case 40: workgroup_vlaunch<T, 40>(v, first, count, stream, pivoting); break;
+        case 48: workgroup_vlaunch<T, 48>(v, first, count, stream, pivoting); break;
+        case 56: workgroup_vlaunch<T, 56>(v, first, count, stream, pivoting); break;
+        case 64: workgroup_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t workgroup_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

@@ -141,6 +141,43 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
  * path (64 or 128); 0 where the unblocked sweep is used (N < 256, N < 512 with pivoting off, MI32_ALGO_SWEEP) */
 int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width);
 
+/* ---- variable-size batches: members of mixed orders, each at its own pointer and leading dimension ---------------- */
+/* One call inverts `batch` members of any orders from 1 to 128 (block-Jacobi blocks, per-element blocks, the diagonal
+ * blocks of a larger matrix) on the register-resident and workgroup-resident kernels: the members are binned once by
+ * order into the eight kernel classes -- orders up to 8 / 16 / 32 / 64 (lanes per matrix) and up to 80 / 96 / 112 / 128
+ * (rows per thread) -- and a call enqueues one status memset and one launch per class that has members, at most eight.
+ * Every member does the arithmetic of the uniform paths, so every member is bit-identical to the CPU oracle, in fp32
+ * and fp64, with pivoting and without (the context's setting).
+ *
+ * The binning itself, pure host code (no device): perm[0 .. batch) <- the member indices in ascending order of
+ * their orders, members of equal order in their original sequence (a counting sort, O(batch)); class_begin[0 .. 9)
+ * <- class k takes perm[class_begin[k] .. class_begin[k + 1]).  batch <= 0, a NULL argument or an order outside
+ * 1 ... 128 is MI32_BAD_SHAPE. */
+int mi32_vbatch_bin(const int *orders, int batch, int *perm, int *class_begin /* int[9] */);
+/* A plan: bins once and uploads the orders and the sorted member list to the context's device -- 8 bytes per member,
+ * the only device memory the feature owns.  `orders` is a HOST array and may go away when the call returns.  Same
+ * error rules as the binning.  The plan is immutable: it may be used any number of times, from any thread, and from
+ * any context on the same device. */
+typedef struct mi32_vbatch *mi32_vbatch_t;
+int mi32_vbatch_create(mi32_handle_t h, const int *orders, int batch, mi32_vbatch_t *out);
+/* frees the plan; safe while calls that use it are still in flight (freeing device memory waits for them) */
+int mi32_vbatch_destroy(mi32_vbatch_t p);
+/* *batch (may be NULL) <- the members of the plan, class_begin[0 .. 9) (may be NULL) <- its class ranges */
+int mi32_vbatch_info(mi32_vbatch_t p, int *batch, int *class_begin /* int[9] */);
+/* d_a, d_inv: DEVICE arrays of `batch` device pointers, member b row-major with rows d_lda[b] / d_ldinv[b] elements
+ * apart; element alignment is all a member needs.  d_lda, d_ldinv: device int[batch], either may be NULL = the
+ * member's order; a leading dimension below the order is the caller's error and is not checked on the device.
+ * d_status: device int[batch] in the caller's member order, NULL = the context keeps the words itself.  Padding --
+ * the elements between column n[b] and the leading dimension -- is never read and never written: a NaN there does
+ * not flag the member.  A member may be inverted in place (d_inv[b] == d_a[b] with equal leading dimensions: every
+ * element of a member is in registers before its first store); members that overlap in any other way, with
+ * themselves or with one another, are undefined.  Any batch size the buffers hold.  Asynchronous on the context's
+ * stream; the launches are recorded under profiling class 2.  A plan of another device is MI32_BAD_SHAPE. */
+int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                             float *const *d_inv, const int *d_ldinv, int *d_status);
+int mi32_inv_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                 double *const *d_inv, const int *d_ldinv, int *d_status);
+
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all

@@ -17,8 +17,8 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import (EPS32, ROOT, check_against_oracle_digest, forward_tolerance, gate_matrix, golden_files, load_golden,
-                      load_oracle_digest, rel_err)
+from conftest import (EPS32, ROOT, canonical_bytes, check_against_oracle_digest, forward_tolerance, gate_matrix, golden_files,
+                      load_golden, load_oracle_digest, rel_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -247,9 +247,13 @@ def test_zero_and_rank_deficient_are_status_singular(oracle, inv_sweep, inv_bloc
             assert st[0] == want == oracle.STATUS_SINGULAR
     # an overflowing pivot chain: huge entries make an infinite intermediate -> flagged, never "OK with inf"
     a = gate_matrix(n, 79) * np.float32(3e38)
+    want, info = oracle.matrix_inv_32_inplace(a, n, return_info=True)
+    assert info["status"] == oracle.matrix_inv_32(a, n, return_info=True)[1]["status"]
+    assert info["status"] == oracle.STATUS_SINGULAR or np.isfinite(want).all()
     for inv in (inv_sweep, inv_blocked):
         x, st = run(inv, a)
-        assert st[0] == oracle.STATUS_SINGULAR or np.isfinite(x).all()
+        assert st[0] == info["status"]
+        assert st[0] == oracle.STATUS_SINGULAR or (np.isfinite(x).all() and canonical_bytes(x) == canonical_bytes(want))
 
 
 def test_a_batch_keeps_valid_members_when_one_is_nonfinite(oracle, inv_blocked):

@@ -172,6 +172,32 @@ def just_inv(K: int, seed=None, inv=None):
     return end - start, a, res
 
 
+def slogdet_from_frexp(mant, exp):
+    """``(sign, logabsdet)``, both float64, of determinants given as the pair ``det = mant * 2**exp`` that
+    ``Inverter.inv_det`` and the ``det=True`` calls return: ``sign = torch.sign(mant)`` and ``logabsdet = log|mant| +
+    exp * ln 2`` -- the layout of ``torch.linalg.slogdet``.  A zero mantissa gives ``(0, -inf)``, a NaN mantissa
+    ``(NaN, NaN)``.  Pure torch: works on CPU tensors too."""
+    import math
+
+    import torch
+
+    m = mant.to(torch.float64)
+    sign = torch.where(torch.isnan(m), m, torch.sign(m))  # torch.sign alone turns a NaN into 0
+    return sign, torch.log(torch.abs(m)) + exp.to(torch.float64) * math.log(2.0)
+
+
+def det_from_frexp(mant, exp, dtype=None):
+    """The determinants themselves, ``ldexp(mant, exp)``, as ``dtype`` (float64 by default).  Unlike the pair this can
+    overflow to +-inf or underflow to 0: the determinant of 128 pivots of 2**100 is far outside any float format.  Use
+    ``slogdet_from_frexp`` where the magnitude is not known to be moderate.  Pure torch: works on CPU tensors too."""
+    import torch
+
+    # in two halves: 2**exp alone may overflow or underflow where mant * 2**exp does not (the first product is exact)
+    half = torch.div(exp, 2, rounding_mode="floor")
+    d = mant.to(torch.float64) * torch.exp2(half.to(torch.float64)) * torch.exp2((exp - half).to(torch.float64))
+    return d if dtype is None else d.to(dtype)
+
+
 def vbatch_bin(orders):
     """``(perm, class_begin)`` of ``mi32_vbatch_bin`` (host only): the member indices sorted by order (stable) and the
     nine boundaries of the eight kernel classes in that list."""
@@ -353,6 +379,46 @@ class Inverter:
                       ctypes.c_void_p(status.data_ptr())), "mi32_inv_device")
         return (out[0] if squeeze else out), status
 
+    def inv_det(self, a, out=None, status=None, want_inverse=True):
+        """The inverse and the determinant of every member from one launch.  a: (N,N) or (B,N,N) float32 / float64 on
+        this device, N <= 128 (a larger N raises ValueError).  Returns ``(inverse, status, det_mant, det_exp)``:
+        ``det = det_mant * 2**det_exp`` with ``det_mant`` float64[B], ``|det_mant|`` in [0.5, 1), and ``det_exp``
+        int32[B] (``slogdet_from_frexp`` / ``det_from_frexp`` turn the pair into log-determinant and sign, or the value).
+        A singular member's pair is ``(0.0, 0)`` where an exactly zero pivot was met with pivoting on, ``(NaN, 0)``
+        otherwise.  Inverse and status are those of ``inv`` bit for bit.  Always runs on the register-resident
+        (N <= 64) or workgroup-resident kernels, whatever ``algo`` is.  ``want_inverse=False``: the determinant-only
+        form, the inverse is not stored and None is returned in its place.  Asynchronous on torch's current stream."""
+        torch = self._torch
+        if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
+            raise ValueError("expected a float32 or float64 tensor on the GPU")
+        squeeze = a.dim() == 2
+        a3 = a.unsqueeze(0) if squeeze else a
+        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
+            raise ValueError("expected (N,N) or (B,N,N)")
+        if a3.shape[1] > 128:
+            raise ValueError("inv_det takes orders up to 128")
+        a3 = a3.contiguous()
+        b, n = a3.shape[0], a3.shape[1]
+        if not want_inverse:
+            if out is not None:
+                raise ValueError("out given with want_inverse=False")
+        elif out is None:
+            out = torch.empty_like(a3)
+        else:
+            out = out.view(b, n, n)
+            if not out.is_contiguous() or out.data_ptr() == a3.data_ptr():
+                raise ValueError("out must be contiguous and must not alias the input")
+        if status is None:
+            status = torch.empty(b, dtype=torch.int32, device=a3.device)
+        det_mant = torch.empty(b, dtype=torch.float64, device=a3.device)
+        det_exp = torch.empty(b, dtype=torch.int32, device=a3.device)
+        self._bind_stream()
+        fn = self._lib.mi32_inv_det_device if a.dtype == torch.float32 else self._lib.mi32_inv_det_device_f64
+        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
+                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
+                      ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())), "mi32_inv_det_device")
+        return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
+
     # ---- variable-size batches: mixed orders 1 ... 128, each member at its own pointer and leading dimension ----
     def plan_ragged(self, orders) -> RaggedPlan:
         """Bin a batch of members of the given orders (a sequence or an int array, each 1 ... 128) once."""
@@ -372,18 +438,23 @@ class Inverter:
         if t.dim() != 1 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
             raise ValueError(f"{what}: expected a contiguous 1-D tensor" + (f" of {numel} entries" if numel else ""))
 
-    def inv_pointers(self, plan, a_ptrs, out_ptrs, dtype, lda=None, ldout=None, status=None):
+    def inv_pointers(self, plan, a_ptrs, out_ptrs, dtype, lda=None, ldout=None, status=None, *, det=False):
         """The low-level form: ``a_ptrs`` / ``out_ptrs`` are int64 device tensors of ``plan.batch`` member addresses
         (row-major members of ``dtype`` float32 / float64), ``lda`` / ``ldout`` int32 device tensors of leading
         dimensions in elements (None: the member's order).  A member may be inverted in place (same address, same
         leading dimension); members that overlap otherwise are undefined.  Asynchronous on torch's current stream.
-        Returns the status tensor (int32[batch], the caller's member order)."""
+        Returns the status tensor (int32[batch], the caller's member order).  ``det=True``: the determinants come
+        from the same launches and ``(status, (det_mant, det_exp))`` is returned (float64[batch] and int32[batch] in
+        the caller's member order, the pair of ``inv_det``); ``out_ptrs=None`` is then the determinant-only form."""
         torch = self._torch
         self._check_plan(plan)
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("dtype: torch.float32 or torch.float64")
         self._check_tensor(a_ptrs, torch.int64, "a_ptrs", plan.batch)
-        self._check_tensor(out_ptrs, torch.int64, "out_ptrs", plan.batch)
+        if out_ptrs is None and not det:
+            raise ValueError("out_ptrs=None needs det=True (the determinant-only form)")
+        if out_ptrs is not None:
+            self._check_tensor(out_ptrs, torch.int64, "out_ptrs", plan.batch)
         for ld, what in ((lda, "lda"), (ldout, "ldout")):
             if ld is not None:
                 self._check_tensor(ld, torch.int32, what, plan.batch)
@@ -392,16 +463,25 @@ class Inverter:
         else:
             self._check_tensor(status, torch.int32, "status", plan.batch)
         self._bind_stream()
-        fn = self._lib.mi32_inv_device_vbatched if dtype == torch.float32 else self._lib.mi32_inv_device_vbatched_f64
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        if det:
+            det_mant = torch.empty(plan.batch, dtype=torch.float64, device=self.device)
+            det_exp = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
+            fn = (self._lib.mi32_inv_det_device_vbatched if dtype == torch.float32
+                  else self._lib.mi32_inv_det_device_vbatched_f64)
+            _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(out_ptrs), ptr(ldout), ptr(status), ptr(det_mant),
+                          ptr(det_exp)), "mi32_inv_det_device_vbatched")
+            return status, (det_mant, det_exp)
+        fn = self._lib.mi32_inv_device_vbatched if dtype == torch.float32 else self._lib.mi32_inv_device_vbatched_f64
         _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(out_ptrs), ptr(ldout), ptr(status)),
                    "mi32_inv_device_vbatched")
         return status
 
-    def inv_ragged(self, plan, a_flat, out=None, status=None):
+    def inv_ragged(self, plan, a_flat, out=None, status=None, *, det=False):
         """The packed layout: ``a_flat`` is a 1-D float32 / float64 device tensor in which member b holds its
         ``n_b * n_b`` row-major elements at offset ``sum_{i<b} n_i^2``.  One call, at most eight launches.  ``out``
-        may be ``a_flat`` itself (in place).  Returns ``(out_flat, status)``."""
+        may be ``a_flat`` itself (in place).  Returns ``(out_flat, status)``; with ``det=True``
+        ``(out_flat, status, (det_mant, det_exp))``, the pair of ``inv_det`` in the caller's member order."""
         torch = self._torch
         self._check_plan(plan)
         if a_flat.dtype not in (torch.float32, torch.float64):
@@ -413,14 +493,16 @@ class Inverter:
             out = torch.empty_like(a_flat)
         else:
             self._check_tensor(out, a_flat.dtype, "out", plan.flat_size)
-        status = self.inv_pointers(plan, plan.packed_pointers(a_flat), plan.packed_pointers(out), a_flat.dtype,
-                                   status=status)
-        return out, status
+        r = self.inv_pointers(plan, plan.packed_pointers(a_flat), plan.packed_pointers(out), a_flat.dtype,
+                              status=status, det=det)
+        return (out, r[0], r[1]) if det else (out, r)
 
-    def inv_diag_blocks(self, m, block_orders, out=None):
+    def inv_diag_blocks(self, m, block_orders, out=None, *, det=False):
         """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
         orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
-        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``."""
+        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``; with
+        ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block (the determinant of the block-diagonal
+        matrix is their product: add the logarithms of ``slogdet_from_frexp``)."""
         torch = self._torch
         if m.dtype not in (torch.float32, torch.float64):
             raise ValueError("expected a float32 or float64 matrix")
@@ -446,9 +528,9 @@ class Inverter:
             self._diag_plan = (key, plan, torch.from_numpy(off * (ld + 1)).to(self.device),
                                torch.full((orders.size,), ld, dtype=torch.int32, device=self.device))
         _, plan, elem_off, lds = self._diag_plan
-        status = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
-                                   elem_off * out.element_size() + out.data_ptr(), m.dtype, lda=lds, ldout=lds)
-        return out, status
+        r = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
+                              elem_off * out.element_size() + out.data_ptr(), m.dtype, lda=lds, ldout=lds, det=det)
+        return (out, r[0], r[1]) if det else (out, r)
 
     def set_lookahead(self, enable: bool):
         _lib.check(self._lib.mi32_set_lookahead(self._h, 1 if enable else 0), "mi32_set_lookahead")

@@ -404,7 +404,7 @@ static int ensure_ws(mi32_context *h, size_t bytes)
 
 extern "C" {
 
-int mi32_version(void) { return 130; }
+int mi32_version(void) { return 140; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)
@@ -808,22 +808,51 @@ int mi32_vbatch_info(mi32_vbatch_t p, int *batch, int *class_begin)
 
 }  // extern "C"
 
+// the inverse with the determinant on the one-launch paths, whatever the context's algorithm (see the header); the
+// arguments are checked before the context is touched
 template <typename T>
-static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
-                               T *const *d_inv, const int *d_ldinv, int *d_status)
+static int inv_det_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, double *d_det_mant,
+                          int *d_det_exp)
 {
-    if (!h || !p || !d_a || !d_inv || p->device != h->device) return MI32_BAD_SHAPE;
+    if (!h || !d_a || n <= 0 || n > kWorkgroupMaxOrder || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp)
+        return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const int rc = status_buffer(h, d_status, batch, &d_status);
+    if (rc != MI32_OK) return rc;
+    const hipError_t e =
+        n <= kResidentMaxOrder
+            ? resident_invert_det(d_a, d_inv, n, batch, d_status, d_det_mant, d_det_exp, h->stream, h->prof, h->pivoting)
+            : workgroup_invert_det(d_a, d_inv, n, batch, d_status, d_det_mant, d_det_exp, h->stream, h->prof, h->pivoting);
+    if (e != hipSuccess) return fail(e, "kernel launch");
+    return MI32_OK;
+}
+
+// DET: the det kernels, d_inv may be null
+template <typename T, bool DET>
+static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
+                               T *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant = nullptr,
+                               int *d_det_exp = nullptr)
+{
+    if (!h || !p || !d_a || (!DET && !d_inv) || (DET && (!d_det_mant || !d_det_exp))) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     const int rc = status_buffer(h, d_status, p->batch, &d_status);
     if (rc != MI32_OK) return rc;
     MI32_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)p->batch, h->stream));  // MI32_OK
     const VbatchArgs<T> v{p->d_orders, p->d_members, d_a, d_inv, d_lda, d_ldinv, d_status};
+    const VbatchDetArgs<T> vd{v, d_det_mant, d_det_exp};
     for (int k = 0; k < kVbatchClasses; ++k) {
         const int first = p->class_begin[k], count = p->class_begin[k + 1] - first;
         if (count == 0) continue;  // a class without members is not launched
-        const hipError_t e = k < 4 ? resident_vinvert(kVbatchLanes[k], v, first, count, h->stream, h->prof, h->pivoting)
-                                   : workgroup_vinvert(kVbatchRows[k - 4], v, first, count, h->stream, h->prof, h->pivoting);
+        hipError_t e;
+        if constexpr (DET)
+            e = k < 4 ? resident_vinvert_det(kVbatchLanes[k], vd, first, count, h->stream, h->prof, h->pivoting)
+                      : workgroup_vinvert_det(kVbatchRows[k - 4], vd, first, count, h->stream, h->prof, h->pivoting);
+        else
+            e = k < 4 ? resident_vinvert(kVbatchLanes[k], v, first, count, h->stream, h->prof, h->pivoting)
+                      : workgroup_vinvert(kVbatchRows[k - 4], v, first, count, h->stream, h->prof, h->pivoting);
         if (e != hipSuccess) return fail(e, "kernel launch");
     }
     return MI32_OK;
@@ -834,13 +863,39 @@ extern "C" {
 int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
                              float *const *d_inv, const int *d_ldinv, int *d_status)
 {
-    return inv_device_vbatched(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+    return inv_device_vbatched<float, false>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
 }
 
 int mi32_inv_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
                                  double *const *d_inv, const int *d_ldinv, int *d_status)
 {
-    return inv_device_vbatched(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+    return inv_device_vbatched<double, false>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+}
+
+int mi32_inv_det_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                        double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                            double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                                 float *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                 int *d_det_exp)
+{
+    return inv_device_vbatched<float, true>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                     double *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                     int *d_det_exp)
+{
+    return inv_device_vbatched<double, true>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_set_profiling(mi32_handle_t h, int enable)

@@ -192,6 +192,78 @@ template <typename T>
 hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int first, int count, hipStream_t stream,
                              Profiler *prof, bool pivoting);
 
+// ---- the determinant beside the inverse (mi32_inv_det_device*) ------------------------------------------------------
+// The pivot steps of the two paths above already hold every pivot value and every row exchange, and elimination with
+// partial pivoting gives det A = (-1)^swaps * prod pivots.  The det kernels (gj_*_det_kernel / gj_*_det_vkernel) are the
+// same bodies with a compile-time switch; the elimination arithmetic is untouched.  The determinant is a pair like
+// frexp's, det = m * 2^e with |m| in [0.5, 1), built by a fixed recurrence of IEEE double operations.  It starts at
+// (1.0, 0); after step r has its pivot `piv` and knows whether row r and the pivot row differ (`swap`), while the member
+// is not flagged:
+//     (pm, pe) = frexp((double)piv);  if (swap) m = -m;  (m, k) = frexp(m * pm);  e += pe + k;
+// The step that flags the member ends the accumulation: (+0.0, 0) for an exactly zero pivot with pivoting on (the rest
+// of the column is exactly zero), (NaN, 0) for every other flag and for a non-finite input entry.
+struct DetAcc {
+    double m;
+    int e;
+    bool flagged;  // the member is flagged (by its input or an earlier step): the pair is final
+};
+// before the first step; input_bad: some entry of the member's input is not finite (the whole member's, not this lane's)
+__device__ __forceinline__ DetAcc det_start(const bool input_bad)
+{
+    return DetAcc{input_bad ? __builtin_nan("") : 1.0, 0, input_bad};
+}
+// The recurrence.  UNIFORM: every lane of the wave holds the same
+// member, so the accumulator is moved to scalar registers between steps -- it costs no vector register where the
+// elimination needs them all (fp64, 64 lanes, pivoting: 256).
+template <typename T, bool PIVOT, bool UNIFORM>
+__device__ __forceinline__ void det_accumulate(DetAcc &d, const T piv, const bool swap)
+{
+    const bool piv_bad = piv == T(0) || piv - piv != T(0);
+    const double pd = (double)piv;  // exact
+    const double pm = __builtin_amdgcn_frexp_mant(pd);
+    const int pe = __builtin_amdgcn_frexp_exp(pd);
+    const double prod = (swap ? -d.m : d.m) * pm;  // in +-[0.25, 1): never under- or overflows
+    const double ok_m = __builtin_amdgcn_frexp_mant(prod);
+    const int ok_e = d.e + pe + __builtin_amdgcn_frexp_exp(prod);
+    const double bad_m = (PIVOT && piv == T(0)) ? 0.0 : __builtin_nan("");
+    double m = d.flagged ? d.m : piv_bad ? bad_m : ok_m;
+    int e = d.flagged ? d.e : piv_bad ? 0 : ok_e;
+    if constexpr (UNIFORM) {
+        m = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(m)),
+                             __builtin_amdgcn_readfirstlane(__double2loint(m)));
+        e = __builtin_amdgcn_readfirstlane(e);
+    }
+    d.m = m;
+    d.e = e;
+    d.flagged = d.flagged || piv_bad;
+}
+// where a det kernel writes member b's pair; a plain kernel carries an empty one
+struct DetOut {
+    double *mant;
+    int *exp;
+};
+// VbatchArgs plus the determinant arrays (double[batch], int[batch], the caller's member order); v.inv may be null:
+// only status and determinant are written then
+template <typename T>
+struct VbatchDetArgs {
+    VbatchArgs<T> v;
+    double *det_mant;
+    int *det_exp;
+};
+// the launchers of the two paths with the determinant; d_inv / v.v.inv may be null (determinant only)
+template <typename T>
+hipError_t resident_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant, int *d_det_exp,
+                               hipStream_t stream, Profiler *prof, bool pivoting);
+template <typename T>
+hipError_t workgroup_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant,
+                                int *d_det_exp, hipStream_t stream, Profiler *prof, bool pivoting);
+template <typename T>
+hipError_t resident_vinvert_det(int lanes, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
+                                Profiler *prof, bool pivoting);
+template <typename T>
+hipError_t workgroup_vinvert_det(int rows_per_thread, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
+                                 Profiler *prof, bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

@@ -76,9 +76,11 @@ __device__ __forceinline__ int row_number(int r)
     return r;
 }
 
-// One pivot step on the group's matrix.  r: the step (a compile-time constant after unrolling for L <= 16).
-template <typename T, int L, bool PIVOT>
-__device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int j, int &orig, bool &bad)
+// One pivot step on the group's matrix.  r: the step (a compile-time constant after unrolling for L <= 16).  DET: the
+// step also multiplies its pivot into the determinant `det` (det_accumulate of mi32_internal.h); every lane of the group
+// holds the pivot and the swap predicate, so all of them accumulate, redundantly.
+template <typename T, int L, bool PIVOT, bool DET>
+__device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int j, int &orig, bool &bad, DetAcc &det)
 {
     // 1. the pivot row p of column r: rows >= n hold NaN and are no candidates, like the rows above r
     int p = r;
@@ -113,6 +115,7 @@ __device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int 
     }
     // 3. fixRow: the pivot is column r's entry of row p (mat_inv_32.cpp:70,129-130)
     const T piv = group_bcast<L>(ap, r);
+    if constexpr (DET) det_accumulate<T, PIVOT, L == 64>(det, piv, p != r);
     bad = bad || piv == T(0) || piv - piv != T(0);  // zero, NaN or infinite pivot
     const bool is_r = (j == r);
     const T prn = (is_r ? T(1) : ap) / piv;
@@ -140,10 +143,12 @@ __device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int 
 // With UNIFORM_N every group of the wave has the order nmax (or none: the steps then run on zeros) and the step loop
 // is the uniform kernel's; without, a group sits out the steps past its own order -- a step on a finished group would
 // flag it and destroy its result -- and every cross-lane operation of resident_step stays inside its group of L
-// lanes, all of them in or all of them out.  Every element is in registers before the first store.
-template <typename T, int L, bool PIVOT, bool UNIFORM_N>
+// lanes, all of them in or all of them out.  Every element is in registers before the first store.  DET: the group's
+// first lane also stores the member's determinant to *det_mant / *det_exp, and a null `out` skips the inverse's stores.
+template <typename T, int L, bool PIVOT, bool UNIFORM_N, bool DET>
 __device__ __forceinline__ void resident_member(const T *in, T *out, const int n, const int nmax, const int lda,
-                                                const int ldo, const int j, const bool mine, int *status_word)
+                                                const int ldo, const int j, const bool mine, int *status_word,
+                                                double *det_mant = nullptr, int *det_exp = nullptr)
 {
     T a[L];
     bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
@@ -157,28 +162,46 @@ __device__ __forceinline__ void resident_member(const T *in, T *out, const int n
         }
     }
     int orig = j;
+    DetAcc det = det_start(false);
+    if constexpr (DET) {
+        // a non-finite input entry, seen by the lane of its column alone: the group's accumulation never starts
+        const unsigned long long flagged = __builtin_amdgcn_ballot_w64(bad);
+        const int g0 = (int)(__lane_id() & ~(unsigned)(L - 1));  // the group's first lane in the wave
+        const unsigned long long group = L == 64 ? ~0ull : ((1ull << (L & 63)) - 1ull) << g0;
+        det = det_start((flagged & group) != 0ull);
+    }
     if constexpr (L <= 16) {
 #pragma unroll
         for (int r = 0; r < L; ++r) {
             if constexpr (UNIFORM_N) {
-                if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);  // n is wave-uniform: a scalar branch
+                if (r < n) resident_step<T, L, PIVOT, DET>(a, r, j, orig, bad, det);  // n is wave-uniform: a scalar branch
             } else {
                 if (r < nmax) {  // wave-uniform: no wave walks through the steps none of its groups takes
-                    if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+                    if (r < n) resident_step<T, L, PIVOT, DET>(a, r, j, orig, bad, det);
                 }
             }
         }
     } else {
 #pragma unroll 1
         for (int r = 0; r < nmax; ++r) {
-            if constexpr (UNIFORM_N) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
-            else if (r < n) resident_step<T, L, PIVOT>(a, r, j, orig, bad);
+            if constexpr (UNIFORM_N) resident_step<T, L, PIVOT, DET>(a, r, j, orig, bad, det);
+            else if (r < n) resident_step<T, L, PIVOT, DET>(a, r, j, orig, bad, det);
         }
     }
     if (!mine) return;
+    if constexpr (DET) {
+        if (j == 0) {
+            *det_mant = det.m;
+            *det_exp = det.e;
+        }
+    }
+    bool store = true;
+    if constexpr (DET) store = out != nullptr;  // determinant only: status and determinant are all that is written
+    if (store) {
 #pragma unroll
-    for (int i = 0; i < L; ++i)
-        if (i < n) out[(size_t)i * ldo + orig] = a[i];
+        for (int i = 0; i < L; ++i)
+            if (i < n) out[(size_t)i * ldo + orig] = a[i];
+    }
     // the status word was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
     if (bad) *status_word = MI32_SINGULAR;
 }
@@ -194,16 +217,33 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *
     // neither loads nor stores
     const bool mine = b < (long long)batch && j < n;
     const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
-    resident_member<T, L, PIVOT, true>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+    resident_member<T, L, PIVOT, true, false>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+}
+
+// gj_resident_kernel with the determinant: member b's pair goes to det_mant[b], det_exp[b]; a null `out`: no inverse
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_det_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                           int n, int batch, int *__restrict__ status,
+                                                                           double *__restrict__ det_mant,
+                                                                           int *__restrict__ det_exp)
+{
+    constexpr int kGroups = kResidentThreads / L;
+    const int j = threadIdx.x & (L - 1);
+    const long long b = (long long)blockIdx.x * kGroups + threadIdx.x / L;
+    const bool mine = b < (long long)batch && j < n;
+    const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
+    const size_t w = mine ? (size_t)b : 0;
+    resident_member<T, L, PIVOT, true, true>(in + mat, out ? out + mat : nullptr, n, n, n, n, j, mine, status + w,
+                                             det_mant + w, det_exp + w);
 }
 
 // The variable-size kernel: group g of the launch takes member members[first + g] of the plan's sorted list and reads
 // that member's order, pointers and leading dimensions (a null lda / ldinv: the order).  The list is sorted by order,
 // so the groups of a wave almost always share one; where they do not the wave loops to its largest.  For L = 64 the
 // group is the wave.  The member pointers carry no __restrict__: a member may be inverted in place.
-template <typename T, int L, bool PIVOT>
-__global__ __launch_bounds__(kResidentThreads) void gj_resident_vkernel(const VbatchArgs<T> v, const int first,
-                                                                        const int count)
+template <typename T, int L, bool PIVOT, bool DET>
+__device__ __forceinline__ void resident_vmember(const VbatchArgs<T> &v, const int first, const int count, double *det_mant,
+                                                 int *det_exp)
 {
     constexpr int kGroups = kResidentThreads / L;
     const int j = threadIdx.x & (L - 1);
@@ -227,19 +267,44 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_vkernel(const Vb
     int lda = n, ldo = n;
     if (mine) {
         in = v.a[m];
-        out = v.inv[m];
+        if (!DET || v.inv) out = v.inv[m];
         if (v.lda) lda = v.lda[m];
         if (v.ldinv) ldo = v.ldinv[m];
     }
-    resident_member<T, L, PIVOT, false>(in, out, n, nmax, lda, ldo, j, mine, v.status + m);
+    // the determinant lands at the caller's member index, like the status word
+    if constexpr (DET) resident_member<T, L, PIVOT, false, true>(in, out, n, nmax, lda, ldo, j, mine, v.status + m,
+                                                                 det_mant + m, det_exp + m);
+    else resident_member<T, L, PIVOT, false, false>(in, out, n, nmax, lda, ldo, j, mine, v.status + m);
+}
+
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_vkernel(const VbatchArgs<T> v, const int first,
+                                                                        const int count)
+{
+    resident_vmember<T, L, PIVOT, false>(v, first, count, nullptr, nullptr);
+}
+
+// gj_resident_vkernel with the determinant; v.v.inv may be null (determinant only)
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_det_vkernel(const VbatchDetArgs<T> v, const int first,
+                                                                            const int count)
+{
+    resident_vmember<T, L, PIVOT, true>(v.v, first, count, v.det_mant, v.det_exp);
 }
 
 template <typename T, int L>
-static void resident_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting)
+static void resident_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting,
+                            const DetOut det)
 {
     constexpr int kGroups = kResidentThreads / L;
     const dim3 grid((unsigned)(((long long)batch + kGroups - 1) / kGroups));
-    if (pivoting)
+    if (det.mant && pivoting)
+        hipLaunchKernelGGL((gj_resident_det_kernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
+                           batch, d_status, det.mant, det.exp);
+    else if (det.mant)
+        hipLaunchKernelGGL((gj_resident_det_kernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
+                           batch, d_status, det.mant, det.exp);
+    else if (pivoting)
         hipLaunchKernelGGL((gj_resident_kernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n, batch,
                            d_status);
     else
@@ -248,8 +313,8 @@ static void resident_launch(const T *d_a, T *d_inv, int n, int batch, int *d_sta
 }
 
 template <typename T>
-hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                           bool pivoting)
+static hipError_t resident_invert_impl(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream,
+                                       Profiler *prof, bool pivoting, const DetOut det)
 {
     const int lanes = resident_lanes(n);
     if (lanes == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
@@ -257,15 +322,32 @@ hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_stat
     if (e != hipSuccess) return e;
     ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
     switch (lanes) {
-        case 8: resident_launch<T, 8>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        case 16: resident_launch<T, 16>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        case 32: resident_launch<T, 32>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        default: resident_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 8: resident_launch<T, 8>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        case 16: resident_launch<T, 16>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        case 32: resident_launch<T, 32>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        default: resident_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
     }
     return hipGetLastError();
 }
+template <typename T>
+hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                           bool pivoting)
+{
+    return resident_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{nullptr, nullptr});
+}
+template <typename T>
+hipError_t resident_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant, int *d_det_exp,
+                               hipStream_t stream, Profiler *prof, bool pivoting)
+{
+    if (!d_det_mant || !d_det_exp) return hipErrorInvalidValue;
+    return resident_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{d_det_mant, d_det_exp});
+}
 template hipError_t resident_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
 template hipError_t resident_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+template hipError_t resident_invert_det(const float *, float *, int, int, int *, double *, int *, hipStream_t, Profiler *,
+                                        bool);
+template hipError_t resident_invert_det(const double *, double *, int, int, int *, double *, int *, hipStream_t, Profiler *,
+                                        bool);
 
 template <typename T, int L>
 static void resident_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
@@ -295,5 +377,34 @@ hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, int first, int co
 }
 template hipError_t resident_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
 template hipError_t resident_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
+
+template <typename T, int L>
+static void resident_det_vlaunch(const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
+{
+    constexpr int kGroups = kResidentThreads / L;
+    const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
+    if (pivoting)
+        hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
+    else
+        hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
+}
+
+template <typename T>
+hipError_t resident_vinvert_det(int lanes, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
+                                Profiler *prof, bool pivoting)
+{
+    if (count <= 0 || first < 0 || !v.v.status || !v.det_mant || !v.det_exp) return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    switch (lanes) {
+        case 8: resident_det_vlaunch<T, 8>(v, first, count, stream, pivoting); break;
+        case 16: resident_det_vlaunch<T, 16>(v, first, count, stream, pivoting); break;
+        case 32: resident_det_vlaunch<T, 32>(v, first, count, stream, pivoting); break;
+        case 64: resident_det_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t resident_vinvert_det(int, const VbatchDetArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t resident_vinvert_det(int, const VbatchDetArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

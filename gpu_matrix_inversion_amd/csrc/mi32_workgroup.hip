@@ -82,10 +82,13 @@ __device__ __forceinline__ void wg_put(T (&a)[RPT], int slot, T v)
 // thread's own column is workgroup-uniform.  Every element is in registers before the first store (the step loop's
 // barriers lie between), so `out` may be `in`.  ROW_POINTER: the loads walk a pointer advanced by lda instead of forming
 // row * lda + j per row (the same addresses; which of the two keeps the row masks out of the registers differs
-// between the instances, see the variable-size kernel).
-template <typename T, int RPT, bool PIVOT, bool ROW_POINTER>
+// between the instances, see the variable-size kernel).  DET: every thread also multiplies each step's pivot into the
+// determinant (det_accumulate of mi32_internal.h; the pivot and the swap predicate are workgroup-uniform, so the
+// accumulator lives in scalar registers), thread 0 stores it to *det_mant / *det_exp, and a null `out` skips the
+// inverse's stores.
+template <typename T, int RPT, bool PIVOT, bool ROW_POINTER, bool DET>
 __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int n, const int lda, const int ldo,
-                                                 int *status_word)
+                                                 int *status_word, double *det_mant = nullptr, int *det_exp = nullptr)
 {
     static_assert(RPT % 8 == 0 && RPT >= 40 && RPT <= 64, "rows per thread");
     constexpr int P = 2 * RPT;  // padded rows
@@ -118,6 +121,9 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
     }
     // this wave's copy of the labels of slots lane and lane + 64 (slots >= P exist in no register: never candidates)
     int lab0 = lane, lab1 = lane + 64;
+    DetAcc det = det_start(false);
+    // a non-finite input entry, seen by the thread that loaded it alone: the workgroup's accumulation never starts
+    if constexpr (DET) det = det_start(__syncthreads_or(bad) != 0);
 
 #pragma unroll 1
     for (int r = 0; r < n; ++r) {
@@ -134,6 +140,7 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
         __syncthreads();
         // b. the pivot slot sp
         int sp = r;  // without pivoting the labels stay the identity
+        bool swap = false;
         if constexpr (PIVOT) {
             const T v0 = colp[lane];
             const T v1 = lane + 64 < P ? colp[lane + 64] : wg_not_a_candidate(T(0));  // (in bounds: 128 entries; a slot >= P is none)
@@ -144,11 +151,13 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
             const unsigned long long m0 = __builtin_amdgcn_ballot_w64(lab0 == pl);
             const unsigned long long m1 = __builtin_amdgcn_ballot_w64(lab1 == pl);
             sp = m0 ? __builtin_ctzll(m0) : 64 + __builtin_ctzll(m1);
+            swap = pl != r;
             // pivotElements: the two labels change places
             lab0 = lab0 == pl ? r : lab0 == r ? pl : lab0;
             lab1 = lab1 == pl ? r : lab1 == r ? pl : lab1;
         }
         const T piv = colp[sp];
+        if constexpr (DET) det_accumulate<T, PIVOT, true>(det, piv, swap);
         bad = bad || piv == T(0) || piv - piv != T(0);  // zero, NaN or infinite pivot
         const int hp = sp >= RPT ? 1 : 0, lp = sp - hp * RPT;
         // c. fixRow in the slab that holds the pivot slot
@@ -179,12 +188,22 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
         oc = s_slot_of[j];
     }
     if (!mine) return;
+    if constexpr (DET) {
+        if (threadIdx.x == 0) {
+            *det_mant = det.m;
+            *det_exp = det.e;
+        }
+    }
+    bool store = true;
+    if constexpr (DET) store = out != nullptr;  // determinant only: status and determinant are all that is written
+    if (store) {
 #pragma unroll
-    for (int i = 0; i < RPT; ++i) {
-        if (slot0 + i < n) {
-            const int row = PIVOT ? s_label[slot0 + i] : slot0 + i;
-            // (both are < n by construction: the labels of the slots < n are a permutation of 0 ... n - 1)
-            if (row < n && oc < n) out[(size_t)row * ldo + oc] = a[i];
+        for (int i = 0; i < RPT; ++i) {
+            if (slot0 + i < n) {
+                const int row = PIVOT ? s_label[slot0 + i] : slot0 + i;
+                // (both are < n by construction: the labels of the slots < n are a permutation of 0 ... n - 1)
+                if (row < n && oc < n) out[(size_t)row * ldo + oc] = a[i];
+            }
         }
     }
     // the status word was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
@@ -196,7 +215,19 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_kernel(const T
                                                                          int n, int *__restrict__ status)
 {
     const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
-    workgroup_member<T, RPT, PIVOT, false>(in + mat, out + mat, n, n, n, status + blockIdx.x);
+    workgroup_member<T, RPT, PIVOT, false, false>(in + mat, out + mat, n, n, n, status + blockIdx.x);
+}
+
+// gj_workgroup_kernel with the determinant: member b's pair goes to det_mant[b], det_exp[b]; a null `out`: no inverse
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                             int n, int *__restrict__ status,
+                                                                             double *__restrict__ det_mant,
+                                                                             int *__restrict__ det_exp)
+{
+    const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
+    workgroup_member<T, RPT, PIVOT, false, true>(in + mat, out ? out + mat : nullptr, n, n, n, status + blockIdx.x,
+                                                 det_mant + blockIdx.x, det_exp + blockIdx.x);
 }
 
 // The variable-size kernel: workgroup g of the launch takes member members[first + g] of the plan's sorted list; its
@@ -212,17 +243,38 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_vkernel(const 
     // with a leading dimension of its own the compiler branches around each row's 64-bit address and, at 56 and 64 rows
     // per thread, spills the row masks to vector-register lanes (fp32 without pivoting: 129 / 132 registers); the row
     // pointer avoids that there (101 / 118) and costs registers at 40 and 48 rows, hence the switch on RPT
-    workgroup_member<T, RPT, PIVOT, (RPT >= 56)>(v.a[m], v.inv[m], n, lda, ldo, v.status + m);
+    workgroup_member<T, RPT, PIVOT, (RPT >= 56), false>(v.a[m], v.inv[m], n, lda, ldo, v.status + m);
+}
+
+// gj_workgroup_vkernel with the determinant, which lands at the caller's member index like the status word; v.v.inv may
+// be null (determinant only)
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_vkernel(const VbatchDetArgs<T> d, const int first)
+{
+    const VbatchArgs<T> &v = d.v;
+    const int m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
+    const int n = __builtin_amdgcn_readfirstlane(v.orders[m]);
+    const int lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[m]) : n;
+    const int ldo = v.ldinv ? __builtin_amdgcn_readfirstlane(v.ldinv[m]) : n;
+    workgroup_member<T, RPT, PIVOT, (RPT >= 56), true>(v.a[m], v.inv ? v.inv[m] : nullptr, n, lda, ldo, v.status + m,
+                                                       d.det_mant + m, d.det_exp + m);
 }
 
 #undef MI32_WG_CASES8
 #undef MI32_WG_CASES64
 
 template <typename T, int RPT>
-static void workgroup_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting)
+static void workgroup_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting,
+                             const DetOut det)
 {
     const dim3 grid((unsigned)batch);
-    if (pivoting)
+    if (det.mant && pivoting)
+        hipLaunchKernelGGL((gj_workgroup_det_kernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
+                           d_status, det.mant, det.exp);
+    else if (det.mant)
+        hipLaunchKernelGGL((gj_workgroup_det_kernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv,
+                           n, d_status, det.mant, det.exp);
+    else if (pivoting)
         hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
                            d_status);
     else
@@ -231,8 +283,8 @@ static void workgroup_launch(const T *d_a, T *d_inv, int n, int batch, int *d_st
 }
 
 template <typename T>
-hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                            bool pivoting)
+static hipError_t workgroup_invert_impl(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream,
+                                        Profiler *prof, bool pivoting, const DetOut det)
 {
     const int rpt = workgroup_rows_per_thread(n);
     if (rpt == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
@@ -240,15 +292,32 @@ hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_sta
     if (e != hipSuccess) return e;
     ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
     switch (rpt) {
-        case 40: workgroup_launch<T, 40>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        case 48: workgroup_launch<T, 48>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        case 56: workgroup_launch<T, 56>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
-        default: workgroup_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting); break;
+        case 40: workgroup_launch<T, 40>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        case 48: workgroup_launch<T, 48>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        case 56: workgroup_launch<T, 56>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
+        default: workgroup_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
     }
     return hipGetLastError();
 }
+template <typename T>
+hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
+                            bool pivoting)
+{
+    return workgroup_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{nullptr, nullptr});
+}
+template <typename T>
+hipError_t workgroup_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant,
+                                int *d_det_exp, hipStream_t stream, Profiler *prof, bool pivoting)
+{
+    if (!d_det_mant || !d_det_exp) return hipErrorInvalidValue;
+    return workgroup_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{d_det_mant, d_det_exp});
+}
 template hipError_t workgroup_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
 template hipError_t workgroup_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_invert_det(const float *, float *, int, int, int *, double *, int *, hipStream_t, Profiler *,
+                                         bool);
+template hipError_t workgroup_invert_det(const double *, double *, int, int, int *, double *, int *, hipStream_t,
+                                         Profiler *, bool);
 
 template <typename T, int RPT>
 static void workgroup_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
@@ -277,5 +346,33 @@ hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int fi
 }
 template hipError_t workgroup_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
 template hipError_t workgroup_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
+
+template <typename T, int RPT>
+static void workgroup_det_vlaunch(const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
+{
+    const dim3 grid((unsigned)count);
+    if (pivoting)
+        hipLaunchKernelGGL((gj_workgroup_det_vkernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
+    else
+        hipLaunchKernelGGL((gj_workgroup_det_vkernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
+}
+
+template <typename T>
+hipError_t workgroup_vinvert_det(int rows_per_thread, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
+                                 Profiler *prof, bool pivoting)
+{
+    if (count <= 0 || first < 0 || !v.v.status || !v.det_mant || !v.det_exp) return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    switch (rows_per_thread) {
+        case 40: workgroup_det_vlaunch<T, 40>(v, first, count, stream, pivoting); break;
+        case 48: workgroup_det_vlaunch<T, 48>(v, first, count, stream, pivoting); break;
+        case 56: workgroup_det_vlaunch<T, 56>(v, first, count, stream, pivoting); break;
+        case 64: workgroup_det_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t workgroup_vinvert_det(int, const VbatchDetArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_vinvert_det(int, const VbatchDetArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

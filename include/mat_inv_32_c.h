@@ -178,6 +178,40 @@ int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *cons
 int mi32_inv_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
                                  double *const *d_inv, const int *d_ldinv, int *d_status);
 
+/* ---- the determinant beside the inverse (orders 1 ... 128) -------------------------------------------------------- */
+/* The one-launch batch paths hold every pivot value and every row exchange of the elimination, and det A =
+ * (-1)^swaps * prod pivots: these calls return it with the inverse, from the same launch, at 12 bytes per member.
+ * The determinant is a pair like frexp's: det = d_det_mant[b] * 2^d_det_exp[b], |mantissa| in [0.5, 1); it cannot
+ * overflow.  log|det| = log|mantissa| + exponent * ln 2, its sign is the mantissa's.  The pair is defined by a fixed
+ * recurrence of IEEE double operations.  It starts at m = 1.0, e = 0; after pivot step r = 0 ... n-1 has chosen its
+ * pivot value piv and knows whether row r and the pivot row differ (swap; never with pivoting off), while the member is
+ * not flagged:
+ *     (pm, pe) = frexp((double)piv);   if (swap) m = -m;   (m, k) = frexp(m * pm);   e += pe + k;
+ * A member with status MI32_OK: (m, e).  A member flagged MI32_SINGULAR: the accumulation stops at the step that
+ * flags it (it never starts for a non-finite input entry) and the pair is (+0.0, 0) when pivoting is on and the flag
+ * was raised by an exactly zero pivot after finite input and finite earlier pivots -- the rest of that column is
+ * exactly zero, so the computed determinant is 0 -- and (NaN, 0) in every other case: a non-finite input entry, a NaN
+ * or infinite pivot, or any flag with pivoting off (a zero diagonal entry does not imply det = 0).
+ *
+ * 1 <= n <= 128.  These calls always run on the register-resident (n <= 64) or the workgroup-resident (65 ... 128)
+ * kernels, whatever mi32_set_algo says: every path gives the same inverse bits, so the setting shows in no result.
+ * The inverse and the status equal those of mi32_inv_device* bit for bit.  d_inv may be NULL (in the variable-size
+ * call: the pointer array): the inverse is then not stored, only status and determinant.  d_det_mant: device
+ * double[batch], d_det_exp: device int[batch], in the order of d_status (the caller's member order).  n > 128, a null
+ * d_det_mant / d_det_exp, batch <= 0 or a plan of another device -> MI32_BAD_SHAPE.  Everything else as for
+ * mi32_inv_device / mi32_inv_device_vbatched: the context's pivoting setting, a null d_status, in-place members of the
+ * variable-size call, asynchronous on the context's stream under profiling class 2. */
+int mi32_inv_det_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                        double *d_det_mant, int *d_det_exp);
+int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                            double *d_det_mant, int *d_det_exp);
+int mi32_inv_det_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                                 float *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                 int *d_det_exp);
+int mi32_inv_det_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                     double *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                     int *d_det_exp);
+
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all

@@ -353,9 +353,9 @@ class Inverter:
     def reserve(self, n: int, batch: int = 1):
         _lib.check(self._lib.mi32_reserve(self._h, int(n), int(batch)), "mi32_reserve")
 
-    def inv(self, a, out=None, status=None):
-        """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin; sweep or blocked as resolved_blocking_f64
-        reports) contiguous tensor on this device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
+    def _batch_args(self, a, out, status, want_inverse=True, max_order=None, too_large=None):
+        """The argument handling ``inv`` and ``inv_det`` share: ``(squeeze, a3, out, status)`` with ``a3`` the contiguous
+        (B,N,N) input, ``out`` the (B,N,N) output (None with ``want_inverse=False``) and ``status`` int32[B]."""
         torch = self._torch
         if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
             raise ValueError("expected a float32 or float64 tensor on the GPU")
@@ -363,9 +363,14 @@ class Inverter:
         a3 = a.unsqueeze(0) if squeeze else a
         if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
             raise ValueError("expected (N,N) or (B,N,N)")
+        if max_order is not None and a3.shape[1] > max_order:
+            raise ValueError(too_large)
         a3 = a3.contiguous()
         b, n = a3.shape[0], a3.shape[1]
-        if out is None:
+        if not want_inverse:
+            if out is not None:
+                raise ValueError("out given with want_inverse=False")
+        elif out is None:
             out = torch.empty_like(a3)
         else:
             out = out.view(b, n, n)
@@ -373,8 +378,15 @@ class Inverter:
                 raise ValueError("out must be contiguous and must not alias the input")
         if status is None:
             status = torch.empty(b, dtype=torch.int32, device=a3.device)
+        return squeeze, a3, out, status
+
+    def inv(self, a, out=None, status=None):
+        """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin; sweep or blocked as resolved_blocking_f64
+        reports) contiguous tensor on this device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
+        squeeze, a3, out, status = self._batch_args(a, out, status)
+        b, n = a3.shape[0], a3.shape[1]
         self._bind_stream()
-        fn = self._lib.mi32_inv_device if a.dtype == torch.float32 else self._lib.mi32_inv_device_f64
+        fn = self._lib.mi32_inv_device if a.dtype == self._torch.float32 else self._lib.mi32_inv_device_f64
         _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b, ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(status.data_ptr())), "mi32_inv_device")
         return (out[0] if squeeze else out), status
@@ -389,27 +401,8 @@ class Inverter:
         (N <= 64) or workgroup-resident kernels, whatever ``algo`` is.  ``want_inverse=False``: the determinant-only
         form, the inverse is not stored and None is returned in its place.  Asynchronous on torch's current stream."""
         torch = self._torch
-        if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
-            raise ValueError("expected a float32 or float64 tensor on the GPU")
-        squeeze = a.dim() == 2
-        a3 = a.unsqueeze(0) if squeeze else a
-        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
-            raise ValueError("expected (N,N) or (B,N,N)")
-        if a3.shape[1] > 128:
-            raise ValueError("inv_det takes orders up to 128")
-        a3 = a3.contiguous()
+        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse, 128, "inv_det takes orders up to 128")
         b, n = a3.shape[0], a3.shape[1]
-        if not want_inverse:
-            if out is not None:
-                raise ValueError("out given with want_inverse=False")
-        elif out is None:
-            out = torch.empty_like(a3)
-        else:
-            out = out.view(b, n, n)
-            if not out.is_contiguous() or out.data_ptr() == a3.data_ptr():
-                raise ValueError("out must be contiguous and must not alias the input")
-        if status is None:
-            status = torch.empty(b, dtype=torch.int32, device=a3.device)
         det_mant = torch.empty(b, dtype=torch.float64, device=a3.device)
         det_exp = torch.empty(b, dtype=torch.int32, device=a3.device)
         self._bind_stream()

@@ -402,6 +402,23 @@ static int ensure_ws(mi32_context *h, size_t bytes)
     return MI32_OK;
 }
 
+// A uniform batch on the one-launch paths: the register-resident kernels up to kResidentMaxOrder rows, the
+// workgroup-resident ones above (n <= kWorkgroupMaxOrder is the caller's business).  det: where the determinants go,
+// empty for none; d_inv may be null only with one.  The caller holds h->mu and has set the device.
+template <typename T>
+static int one_launch_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, const DetOut det)
+{
+    const int rc = status_buffer(h, d_status, batch, &d_status);
+    if (rc != MI32_OK) return rc;
+    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, h->stream);  // MI32_OK
+    if (e == hipSuccess)
+        e = n <= kResidentMaxOrder
+                ? resident_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, h->pivoting)
+                : workgroup_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, h->pivoting);
+    if (e != hipSuccess) return fail(e, "kernel launch");
+    return MI32_OK;
+}
+
 extern "C" {
 
 int mi32_version(void) { return 140; }
@@ -608,14 +625,12 @@ int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *
     const int algo = resolve_algo(h, n);
     int rc = ensure_ws(h, ws_bytes_for(h, n, batch, algo));
     if (rc != MI32_OK) return rc;
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
+        return one_launch_device(h, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
     rc = status_buffer(h, d_status, batch, &d_status);
     if (rc != MI32_OK) return rc;
     hipError_t e;
-    if (algo == MI32_ALGO_RESIDENT)
-        e = resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
-    else if (algo == MI32_ALGO_WORKGROUP)
-        e = workgroup_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
-    else if (algo == MI32_ALGO_SWEEP)
+    if (algo == MI32_ALGO_SWEEP)
         e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws, h->stream, h->prof, h->pivoting);
     else {
         BlockedExec ex;
@@ -685,15 +700,8 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     const int algo = resolve_algo_f64(h, n);
-    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) {
-        int rc = status_buffer(h, d_status, batch, &d_status);
-        if (rc != MI32_OK) return rc;
-        const hipError_t e = algo == MI32_ALGO_RESIDENT
-                                 ? resident_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting)
-                                 : workgroup_invert(d_a, d_inv, n, batch, d_status, h->stream, h->prof, h->pivoting);
-        if (e != hipSuccess) return fail(e, "kernel launch");
-        return MI32_OK;
-    }
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
+        return one_launch_device(h, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
     const bool blocked = algo == MI32_ALGO_BLOCKED;
     const bool nopivot = blocked && !h->pivoting;
     const Blocked64Plan bp = plan_blocked64(h, n);
@@ -818,14 +826,7 @@ static int inv_det_device(mi32_context *h, const T *d_a, int n, int batch, T *d_
         return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
-    const int rc = status_buffer(h, d_status, batch, &d_status);
-    if (rc != MI32_OK) return rc;
-    const hipError_t e =
-        n <= kResidentMaxOrder
-            ? resident_invert_det(d_a, d_inv, n, batch, d_status, d_det_mant, d_det_exp, h->stream, h->prof, h->pivoting)
-            : workgroup_invert_det(d_a, d_inv, n, batch, d_status, d_det_mant, d_det_exp, h->stream, h->prof, h->pivoting);
-    if (e != hipSuccess) return fail(e, "kernel launch");
-    return MI32_OK;
+    return one_launch_device(h, d_a, n, batch, d_inv, d_status, DetOut{d_det_mant, d_det_exp});
 }
 
 // DET: the det kernels, d_inv may be null
@@ -842,17 +843,13 @@ static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *c
     if (rc != MI32_OK) return rc;
     MI32_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)p->batch, h->stream));  // MI32_OK
     const VbatchArgs<T> v{p->d_orders, p->d_members, d_a, d_inv, d_lda, d_ldinv, d_status};
-    const VbatchDetArgs<T> vd{v, d_det_mant, d_det_exp};
+    const DetOut det = DET ? DetOut{d_det_mant, d_det_exp} : DetOut{nullptr, nullptr};
     for (int k = 0; k < kVbatchClasses; ++k) {
         const int first = p->class_begin[k], count = p->class_begin[k + 1] - first;
         if (count == 0) continue;  // a class without members is not launched
-        hipError_t e;
-        if constexpr (DET)
-            e = k < 4 ? resident_vinvert_det(kVbatchLanes[k], vd, first, count, h->stream, h->prof, h->pivoting)
-                      : workgroup_vinvert_det(kVbatchRows[k - 4], vd, first, count, h->stream, h->prof, h->pivoting);
-        else
-            e = k < 4 ? resident_vinvert(kVbatchLanes[k], v, first, count, h->stream, h->prof, h->pivoting)
-                      : workgroup_vinvert(kVbatchRows[k - 4], v, first, count, h->stream, h->prof, h->pivoting);
+        const hipError_t e =
+            k < 4 ? resident_vinvert(kVbatchLanes[k], v, det, first, count, h->stream, h->prof, h->pivoting)
+                  : workgroup_vinvert(kVbatchRows[k - 4], v, det, first, count, h->stream, h->prof, h->pivoting);
         if (e != hipSuccess) return fail(e, "kernel launch");
     }
     return MI32_OK;

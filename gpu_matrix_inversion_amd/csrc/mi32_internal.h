@@ -158,18 +158,12 @@ hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d
 // be null.  Bit-identical to the sweep path.
 static constexpr int kResidentMaxOrder = 64;
 int resident_lanes(int n);
-template <typename T>
-hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                           bool pivoting);
 
 // workgroup-resident path (mi32_workgroup.hip): orders kResidentMaxOrder + 1 ... kWorkgroupMaxOrder, one launch, no
 // workspace.  One workgroup of 256 threads holds one matrix in registers, workgroup_rows_per_thread(n) rows per thread
 // (40 / 48 / 56 / 64; 0 when the order is out of range); d_status must not be null.  Bit-identical to the sweep path.
 static constexpr int kWorkgroupMaxOrder = 128;
 int workgroup_rows_per_thread(int n);
-template <typename T>
-hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                            bool pivoting);
 
 // variable-size batches (mi32_vbatch_*): members of any orders 1 ... kWorkgroupMaxOrder, each at its own pointer and
 // leading dimensions, on the two paths above.  Everything here is device memory.  `members` is the plan's list of
@@ -185,12 +179,6 @@ struct VbatchArgs {
     const int *ldinv;    // null: orders[b]
     int *status;         // int[batch], zeroed by the host before the launches
 };
-template <typename T>
-hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
-                            bool pivoting);
-template <typename T>
-hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int first, int count, hipStream_t stream,
-                             Profiler *prof, bool pivoting);
 
 // ---- the determinant beside the inverse (mi32_inv_det_device*) ------------------------------------------------------
 // The pivot steps of the two paths above already hold every pivot value and every row exchange, and elimination with
@@ -237,32 +225,39 @@ __device__ __forceinline__ void det_accumulate(DetAcc &d, const T piv, const boo
     d.e = e;
     d.flagged = d.flagged || piv_bad;
 }
-// where a det kernel writes member b's pair; a plain kernel carries an empty one
+// where the determinants go: member b's pair to mant[b], exp[b].  Empty (both null): no determinant, the plain kernels
+// run; with one the det kernels run and the inverse's pointer(s) may be null (determinant only).
 struct DetOut {
     double *mant;
     int *exp;
+    bool empty() const { return !mant && !exp; }
+    bool valid() const { return !mant == !exp; }  // exactly one null member is no DetOut
 };
-// VbatchArgs plus the determinant arrays (double[batch], int[batch], the caller's member order); v.inv may be null:
-// only status and determinant are written then
+// the det kernels' argument: VbatchArgs plus the determinant arrays (double[batch], int[batch], the caller's member
+// order); v.inv may be null: only status and determinant are written then
 template <typename T>
 struct VbatchDetArgs {
     VbatchArgs<T> v;
     double *det_mant;
     int *det_exp;
 };
-// the launchers of the two paths with the determinant; d_inv / v.v.inv may be null (determinant only)
+
+// ---- the launchers of the two one-launch paths -----------------------------------------------------------------------
+// Per path a uniform batch and a slice of a variable-size plan (lanes / rows_per_thread: the slice's kernel class).  The
+// status words are zeroed by the host before the launch; hipErrorInvalidValue for an order or class without an instance,
+// a DetOut with exactly one null member, or a null inverse without a DetOut.
 template <typename T>
-hipError_t resident_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant, int *d_det_exp,
-                               hipStream_t stream, Profiler *prof, bool pivoting);
+hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, DetOut det, hipStream_t stream,
+                           Profiler *prof, bool pivoting);
 template <typename T>
-hipError_t workgroup_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant,
-                                int *d_det_exp, hipStream_t stream, Profiler *prof, bool pivoting);
+hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, DetOut det, int first, int count, hipStream_t stream,
+                            Profiler *prof, bool pivoting);
 template <typename T>
-hipError_t resident_vinvert_det(int lanes, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
-                                Profiler *prof, bool pivoting);
+hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, DetOut det, hipStream_t stream,
+                            Profiler *prof, bool pivoting);
 template <typename T>
-hipError_t workgroup_vinvert_det(int rows_per_thread, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
-                                 Profiler *prof, bool pivoting);
+hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, DetOut det, int first, int count,
+                             hipStream_t stream, Profiler *prof, bool pivoting);
 
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"

@@ -32,6 +32,8 @@
 //
 // gj_resident_vkernel is the same body for a variable-size batch (mi32_inv_device_vbatched): every group looks up its
 // member's order, pointers and leading dimensions, and the groups of a wave may differ in order.
+#include <type_traits>
+
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -59,10 +61,6 @@ __device__ __forceinline__ double group_bcast(double v, int src)
 {
     return __hiloint2double(group_bcast<L>(__double2hiint(v), src), group_bcast<L>(__double2loint(v), src));
 }
-
-// never a pivot candidate (PivotRec<T>::make turns a NaN into "no candidate")
-__device__ __forceinline__ float not_a_candidate(float) { return __builtin_nanf(""); }
-__device__ __forceinline__ double not_a_candidate(double) { return __builtin_nan(""); }
 
 // A wave-uniform row number as a vector register the compiler cannot see through.  With a run-time step the row
 // tests `i >= r`, `i == r`, `i == p` of an unrolled row loop are otherwise evaluated on the scalar unit, all of them
@@ -206,9 +204,11 @@ __device__ __forceinline__ void resident_member(const T *in, T *out, const int n
     if (bad) *status_word = MI32_SINGULAR;
 }
 
-template <typename T, int L, bool PIVOT>
-__global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *__restrict__ in, T *__restrict__ out,
-                                                                       int n, int batch, int *__restrict__ status)
+// The uniform kernel pair's body: group b of the launch takes member b of the batch.  DET: member b's determinant goes to
+// det_mant[b], det_exp[b], and a null `out` means no inverse.
+template <typename T, int L, bool PIVOT, bool DET>
+__device__ __forceinline__ void resident_umember(const T *in, T *out, const int n, const int batch, int *status,
+                                                 double *det_mant, int *det_exp)
 {
     constexpr int kGroups = kResidentThreads / L;  // matrices per workgroup
     const int j = threadIdx.x & (L - 1);
@@ -217,24 +217,30 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *
     // neither loads nor stores
     const bool mine = b < (long long)batch && j < n;
     const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
-    resident_member<T, L, PIVOT, true, false>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+    if constexpr (DET) {
+        const size_t w = mine ? (size_t)b : 0;
+        resident_member<T, L, PIVOT, true, true>(in + mat, out ? out + mat : nullptr, n, n, n, n, j, mine, status + w,
+                                                 det_mant + w, det_exp + w);
+    } else {
+        resident_member<T, L, PIVOT, true, false>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+    }
 }
 
-// gj_resident_kernel with the determinant: member b's pair goes to det_mant[b], det_exp[b]; a null `out`: no inverse
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                                                       int n, int batch, int *__restrict__ status)
+{
+    resident_umember<T, L, PIVOT, false>(in, out, n, batch, status, nullptr, nullptr);
+}
+
+// gj_resident_kernel with the determinant
 template <typename T, int L, bool PIVOT>
 __global__ __launch_bounds__(kResidentThreads) void gj_resident_det_kernel(const T *__restrict__ in, T *__restrict__ out,
                                                                            int n, int batch, int *__restrict__ status,
                                                                            double *__restrict__ det_mant,
                                                                            int *__restrict__ det_exp)
 {
-    constexpr int kGroups = kResidentThreads / L;
-    const int j = threadIdx.x & (L - 1);
-    const long long b = (long long)blockIdx.x * kGroups + threadIdx.x / L;
-    const bool mine = b < (long long)batch && j < n;
-    const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
-    const size_t w = mine ? (size_t)b : 0;
-    resident_member<T, L, PIVOT, true, true>(in + mat, out ? out + mat : nullptr, n, n, n, n, j, mine, status + w,
-                                             det_mant + w, det_exp + w);
+    resident_umember<T, L, PIVOT, true>(in, out, n, batch, status, det_mant, det_exp);
 }
 
 // The variable-size kernel: group g of the launch takes member members[first + g] of the plan's sorted list and reads
@@ -292,119 +298,70 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_det_vkernel(cons
     resident_vmember<T, L, PIVOT, true>(v.v, first, count, v.det_mant, v.det_exp);
 }
 
-template <typename T, int L>
-static void resident_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting,
-                            const DetOut det)
+// f(lanes, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time pair picks
+// a kernel instance.  false: no instance has that many lanes per matrix.
+template <typename F>
+static bool resident_instance(int lanes, bool pivoting, F f)
 {
-    constexpr int kGroups = kResidentThreads / L;
-    const dim3 grid((unsigned)(((long long)batch + kGroups - 1) / kGroups));
-    if (det.mant && pivoting)
-        hipLaunchKernelGGL((gj_resident_det_kernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
-                           batch, d_status, det.mant, det.exp);
-    else if (det.mant)
-        hipLaunchKernelGGL((gj_resident_det_kernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
-                           batch, d_status, det.mant, det.exp);
-    else if (pivoting)
-        hipLaunchKernelGGL((gj_resident_kernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n, batch,
-                           d_status);
-    else
-        hipLaunchKernelGGL((gj_resident_kernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n, batch,
-                           d_status);
+    const auto pick = [&](auto l) {
+        if (pivoting) f(l, std::true_type{});
+        else f(l, std::false_type{});
+        return true;
+    };
+    switch (lanes) {
+        case 8: return pick(std::integral_constant<int, 8>{});
+        case 16: return pick(std::integral_constant<int, 16>{});
+        case 32: return pick(std::integral_constant<int, 32>{});
+        case 64: return pick(std::integral_constant<int, 64>{});
+        default: return false;
+    }
 }
 
 template <typename T>
-static hipError_t resident_invert_impl(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream,
-                                       Profiler *prof, bool pivoting, const DetOut det)
+hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, const DetOut det, hipStream_t stream,
+                           Profiler *prof, bool pivoting)
 {
     const int lanes = resident_lanes(n);
-    if (lanes == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream);  // MI32_OK
-    if (e != hipSuccess) return e;
+    if (lanes == 0 || batch <= 0 || !d_status || !det.valid() || (!d_inv && det.empty())) return hipErrorInvalidValue;
     ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
-    switch (lanes) {
-        case 8: resident_launch<T, 8>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        case 16: resident_launch<T, 16>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        case 32: resident_launch<T, 32>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        default: resident_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-    }
+    resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+        constexpr int L = decltype(l)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        constexpr int kGroups = kResidentThreads / L;
+        const dim3 grid((unsigned)(((long long)batch + kGroups - 1) / kGroups));
+        if (det.empty())
+            hipLaunchKernelGGL((gj_resident_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
+                               batch, d_status);
+        else
+            hipLaunchKernelGGL((gj_resident_det_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv,
+                               n, batch, d_status, det.mant, det.exp);
+    });
     return hipGetLastError();
 }
-template <typename T>
-hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                           bool pivoting)
-{
-    return resident_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{nullptr, nullptr});
-}
-template <typename T>
-hipError_t resident_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant, int *d_det_exp,
-                               hipStream_t stream, Profiler *prof, bool pivoting)
-{
-    if (!d_det_mant || !d_det_exp) return hipErrorInvalidValue;
-    return resident_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{d_det_mant, d_det_exp});
-}
-template hipError_t resident_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
-template hipError_t resident_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
-template hipError_t resident_invert_det(const float *, float *, int, int, int *, double *, int *, hipStream_t, Profiler *,
-                                        bool);
-template hipError_t resident_invert_det(const double *, double *, int, int, int *, double *, int *, hipStream_t, Profiler *,
-                                        bool);
-
-template <typename T, int L>
-static void resident_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
-{
-    constexpr int kGroups = kResidentThreads / L;
-    const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
-    if (pivoting)
-        hipLaunchKernelGGL((gj_resident_vkernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
-    else
-        hipLaunchKernelGGL((gj_resident_vkernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
-}
+template hipError_t resident_invert(const float *, float *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
+template hipError_t resident_invert(const double *, double *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
 
 template <typename T>
-hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
-                            bool pivoting)
+hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, const DetOut det, int first, int count, hipStream_t stream,
+                            Profiler *prof, bool pivoting)
 {
-    if (count <= 0 || first < 0 || !v.status) return hipErrorInvalidValue;
+    if (count <= 0 || first < 0 || !v.status || !det.valid() || (!v.inv && det.empty())) return hipErrorInvalidValue;
+    const VbatchDetArgs<T> vd{v, det.mant, det.exp};
     ProfScope ps(prof, KC_PANEL, stream);
-    switch (lanes) {
-        case 8: resident_vlaunch<T, 8>(v, first, count, stream, pivoting); break;
-        case 16: resident_vlaunch<T, 16>(v, first, count, stream, pivoting); break;
-        case 32: resident_vlaunch<T, 32>(v, first, count, stream, pivoting); break;
-        case 64: resident_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool found = resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+        constexpr int L = decltype(l)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        constexpr int kGroups = kResidentThreads / L;
+        const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
+        if (det.empty())
+            hipLaunchKernelGGL((gj_resident_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
+        else
+            hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, vd, first,
+                               count);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
-template hipError_t resident_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
-template hipError_t resident_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
-
-template <typename T, int L>
-static void resident_det_vlaunch(const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
-{
-    constexpr int kGroups = kResidentThreads / L;
-    const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
-    if (pivoting)
-        hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, true>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
-    else
-        hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, false>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
-}
-
-template <typename T>
-hipError_t resident_vinvert_det(int lanes, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
-                                Profiler *prof, bool pivoting)
-{
-    if (count <= 0 || first < 0 || !v.v.status || !v.det_mant || !v.det_exp) return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_PANEL, stream);
-    switch (lanes) {
-        case 8: resident_det_vlaunch<T, 8>(v, first, count, stream, pivoting); break;
-        case 16: resident_det_vlaunch<T, 16>(v, first, count, stream, pivoting); break;
-        case 32: resident_det_vlaunch<T, 32>(v, first, count, stream, pivoting); break;
-        case 64: resident_det_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-template hipError_t resident_vinvert_det(int, const VbatchDetArgs<float> &, int, int, hipStream_t, Profiler *, bool);
-template hipError_t resident_vinvert_det(int, const VbatchDetArgs<double> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t resident_vinvert(int, const VbatchArgs<float> &, DetOut, int, int, hipStream_t, Profiler *, bool);
+template hipError_t resident_vinvert(int, const VbatchArgs<double> &, DetOut, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

@@ -64,8 +64,10 @@ __device__ __forceinline__ PivotRec<T> wave_max_rec(PivotRec<T> k)
     }
     return k;
 }
+// never a pivot candidate (PivotRec<T>::make turns a NaN into "no candidate")
+__device__ __forceinline__ float not_a_candidate(float) { return __builtin_nanf(""); }
+__device__ __forceinline__ double not_a_candidate(double) { return __builtin_nan(""); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
 
 }  // namespace mi32

@@ -31,6 +31,8 @@
 //
 // gj_workgroup_vkernel is the same body for a variable-size batch (mi32_inv_device_vbatched): the workgroup looks up
 // its member's order, pointers and leading dimensions from blockIdx.x.
+#include <type_traits>
+
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -43,9 +45,6 @@ int workgroup_rows_per_thread(int n)
 {
     return n <= kResidentMaxOrder || n > kWorkgroupMaxOrder ? 0 : n <= 80 ? 40 : n <= 96 ? 48 : n <= 112 ? 56 : 64;
 }
-
-__device__ __forceinline__ float wg_not_a_candidate(float) { return __builtin_nanf(""); }
-__device__ __forceinline__ double wg_not_a_candidate(double) { return __builtin_nan(""); }
 
 // `X(i)` for i = 0 ... 63 as the cases of a switch; slots >= RPT are discarded at compile time
 #define MI32_WG_CASES8(X, b) X(b + 0) X(b + 1) X(b + 2) X(b + 3) X(b + 4) X(b + 5) X(b + 6) X(b + 7)
@@ -117,7 +116,7 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
             v = in[live ? (size_t)(slot0 + i) * lda + j : 0];
         }
         bad = bad || (live && v - v != T(0));
-        a[i] = slot0 + i < n ? (mine ? v : T(0)) : wg_not_a_candidate(T(0));
+        a[i] = slot0 + i < n ? (mine ? v : T(0)) : not_a_candidate(T(0));
     }
     // this wave's copy of the labels of slots lane and lane + 64 (slots >= P exist in no register: never candidates)
     int lab0 = lane, lab1 = lane + 64;
@@ -143,9 +142,9 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
         bool swap = false;
         if constexpr (PIVOT) {
             const T v0 = colp[lane];
-            const T v1 = lane + 64 < P ? colp[lane + 64] : wg_not_a_candidate(T(0));  // (in bounds: 128 entries; a slot >= P is none)
-            const PivotRec<T> k0 = PivotRec<T>::make(lab0 >= r ? v0 : wg_not_a_candidate(T(0)), lab0);
-            const PivotRec<T> k1 = PivotRec<T>::make(lab1 >= r ? v1 : wg_not_a_candidate(T(0)), lab1);
+            const T v1 = lane + 64 < P ? colp[lane + 64] : not_a_candidate(T(0));  // (in bounds: 128 entries; a slot >= P is none)
+            const PivotRec<T> k0 = PivotRec<T>::make(lab0 >= r ? v0 : not_a_candidate(T(0)), lab0);
+            const PivotRec<T> k1 = PivotRec<T>::make(lab1 >= r ? v1 : not_a_candidate(T(0)), lab1);
             const PivotRec<T> best = wave_max_rec(PivotRec<T>::best_of(k0, k1));
             const int pl = __builtin_amdgcn_readfirstlane(best.row(r));  // the pivot's logical row; r when nothing is a candidate
             const unsigned long long m0 = __builtin_amdgcn_ballot_w64(lab0 == pl);
@@ -230,149 +229,109 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_kernel(con
                                                  det_mant + blockIdx.x, det_exp + blockIdx.x);
 }
 
-// The variable-size kernel: workgroup g of the launch takes member members[first + g] of the plan's sorted list; its
-// order, pointers and leading dimensions (a null lda / ldinv: the order) are workgroup-uniform values.  The member
-// pointers carry no __restrict__: a member may be inverted in place.
+// The variable-size kernels: workgroup g of the launch takes member members[first + g] of the plan's sorted list; its
+// order and leading dimensions (a null lda / ldinv: the order) are workgroup-uniform values.
+struct WorkgroupSlot {
+    int m, n, lda, ldo;  // the caller's member index, the member's order and leading dimensions
+};
+// (v by value: through a reference the kernel-argument loads are ordered differently)
+template <typename T>
+__device__ __forceinline__ WorkgroupSlot workgroup_slot(const VbatchArgs<T> v, const int first)
+{
+    WorkgroupSlot s;
+    s.m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
+    s.n = __builtin_amdgcn_readfirstlane(v.orders[s.m]);
+    s.lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[s.m]) : s.n;
+    s.ldo = v.ldinv ? __builtin_amdgcn_readfirstlane(v.ldinv[s.m]) : s.n;
+    return s;
+}
+
+// The member pointers carry no __restrict__: a member may be inverted in place.  ROW_POINTER = (RPT >= 56): with a
+// leading dimension of its own the compiler branches around each row's 64-bit address and, at 56 and 64 rows per
+// thread, spills the row masks to vector-register lanes (fp32 without pivoting: 129 / 132 registers); the row pointer
+// avoids that there (101 / 118) and costs registers at 40 and 48 rows.
 template <typename T, int RPT, bool PIVOT>
 __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_vkernel(const VbatchArgs<T> v, const int first)
 {
-    const int m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
-    const int n = __builtin_amdgcn_readfirstlane(v.orders[m]);
-    const int lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[m]) : n;
-    const int ldo = v.ldinv ? __builtin_amdgcn_readfirstlane(v.ldinv[m]) : n;
-    // with a leading dimension of its own the compiler branches around each row's 64-bit address and, at 56 and 64 rows
-    // per thread, spills the row masks to vector-register lanes (fp32 without pivoting: 129 / 132 registers); the row
-    // pointer avoids that there (101 / 118) and costs registers at 40 and 48 rows, hence the switch on RPT
-    workgroup_member<T, RPT, PIVOT, (RPT >= 56), false>(v.a[m], v.inv[m], n, lda, ldo, v.status + m);
+    const WorkgroupSlot s = workgroup_slot(v, first);
+    workgroup_member<T, RPT, PIVOT, (RPT >= 56), false>(v.a[s.m], v.inv[s.m], s.n, s.lda, s.ldo, v.status + s.m);
 }
 
-// gj_workgroup_vkernel with the determinant, which lands at the caller's member index like the status word; v.v.inv may
+// gj_workgroup_vkernel with the determinant, which lands at the caller's member index like the status word; d.v.inv may
 // be null (determinant only)
 template <typename T, int RPT, bool PIVOT>
 __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_vkernel(const VbatchDetArgs<T> d, const int first)
 {
-    const VbatchArgs<T> &v = d.v;
-    const int m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
-    const int n = __builtin_amdgcn_readfirstlane(v.orders[m]);
-    const int lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[m]) : n;
-    const int ldo = v.ldinv ? __builtin_amdgcn_readfirstlane(v.ldinv[m]) : n;
-    workgroup_member<T, RPT, PIVOT, (RPT >= 56), true>(v.a[m], v.inv ? v.inv[m] : nullptr, n, lda, ldo, v.status + m,
-                                                       d.det_mant + m, d.det_exp + m);
+    const WorkgroupSlot s = workgroup_slot(d.v, first);
+    workgroup_member<T, RPT, PIVOT, (RPT >= 56), true>(d.v.a[s.m], d.v.inv ? d.v.inv[s.m] : nullptr, s.n, s.lda, s.ldo,
+                                                       d.v.status + s.m, d.det_mant + s.m, d.det_exp + s.m);
 }
 
 #undef MI32_WG_CASES8
 #undef MI32_WG_CASES64
 
-template <typename T, int RPT>
-static void workgroup_launch(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, bool pivoting,
-                             const DetOut det)
+// f(rows per thread, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time
+// pair picks a kernel instance.  false: no instance has that many rows per thread.
+template <typename F>
+static bool workgroup_instance(int rows_per_thread, bool pivoting, F f)
 {
-    const dim3 grid((unsigned)batch);
-    if (det.mant && pivoting)
-        hipLaunchKernelGGL((gj_workgroup_det_kernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
-                           d_status, det.mant, det.exp);
-    else if (det.mant)
-        hipLaunchKernelGGL((gj_workgroup_det_kernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv,
-                           n, d_status, det.mant, det.exp);
-    else if (pivoting)
-        hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
-                           d_status);
-    else
-        hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
-                           d_status);
+    const auto pick = [&](auto rpt) {
+        if (pivoting) f(rpt, std::true_type{});
+        else f(rpt, std::false_type{});
+        return true;
+    };
+    switch (rows_per_thread) {
+        case 40: return pick(std::integral_constant<int, 40>{});
+        case 48: return pick(std::integral_constant<int, 48>{});
+        case 56: return pick(std::integral_constant<int, 56>{});
+        case 64: return pick(std::integral_constant<int, 64>{});
+        default: return false;
+    }
 }
 
 template <typename T>
-static hipError_t workgroup_invert_impl(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream,
-                                        Profiler *prof, bool pivoting, const DetOut det)
+hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, const DetOut det, hipStream_t stream,
+                            Profiler *prof, bool pivoting)
 {
-    const int rpt = workgroup_rows_per_thread(n);
-    if (rpt == 0 || batch <= 0 || !d_status) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream);  // MI32_OK
-    if (e != hipSuccess) return e;
+    const int rows = workgroup_rows_per_thread(n);
+    if (rows == 0 || batch <= 0 || !d_status || !det.valid() || (!d_inv && det.empty())) return hipErrorInvalidValue;
     ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
-    switch (rpt) {
-        case 40: workgroup_launch<T, 40>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        case 48: workgroup_launch<T, 48>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        case 56: workgroup_launch<T, 56>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-        default: workgroup_launch<T, 64>(d_a, d_inv, n, batch, d_status, stream, pivoting, det); break;
-    }
+    workgroup_instance(rows, pivoting, [&](auto rpt, auto pivot) {
+        constexpr int RPT = decltype(rpt)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        const dim3 grid((unsigned)batch);
+        if (det.empty())
+            hipLaunchKernelGGL((gj_workgroup_kernel<T, RPT, PIVOT>), grid, dim3(kWorkgroupThreads), 0, stream, d_a, d_inv, n,
+                               d_status);
+        else
+            hipLaunchKernelGGL((gj_workgroup_det_kernel<T, RPT, PIVOT>), grid, dim3(kWorkgroupThreads), 0, stream, d_a,
+                               d_inv, n, d_status, det.mant, det.exp);
+    });
     return hipGetLastError();
 }
-template <typename T>
-hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_status, hipStream_t stream, Profiler *prof,
-                            bool pivoting)
-{
-    return workgroup_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{nullptr, nullptr});
-}
-template <typename T>
-hipError_t workgroup_invert_det(const T *d_a, T *d_inv, int n, int batch, int *d_status, double *d_det_mant,
-                                int *d_det_exp, hipStream_t stream, Profiler *prof, bool pivoting)
-{
-    if (!d_det_mant || !d_det_exp) return hipErrorInvalidValue;
-    return workgroup_invert_impl(d_a, d_inv, n, batch, d_status, stream, prof, pivoting, DetOut{d_det_mant, d_det_exp});
-}
-template hipError_t workgroup_invert(const float *, float *, int, int, int *, hipStream_t, Profiler *, bool);
-template hipError_t workgroup_invert(const double *, double *, int, int, int *, hipStream_t, Profiler *, bool);
-template hipError_t workgroup_invert_det(const float *, float *, int, int, int *, double *, int *, hipStream_t, Profiler *,
-                                         bool);
-template hipError_t workgroup_invert_det(const double *, double *, int, int, int *, double *, int *, hipStream_t,
-                                         Profiler *, bool);
-
-template <typename T, int RPT>
-static void workgroup_vlaunch(const VbatchArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
-{
-    const dim3 grid((unsigned)count);
-    if (pivoting)
-        hipLaunchKernelGGL((gj_workgroup_vkernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
-    else
-        hipLaunchKernelGGL((gj_workgroup_vkernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
-}
+template hipError_t workgroup_invert(const float *, float *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_invert(const double *, double *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
 
 template <typename T>
-hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, int first, int count, hipStream_t stream,
-                             Profiler *prof, bool pivoting)
+hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, const DetOut det, int first, int count,
+                             hipStream_t stream, Profiler *prof, bool pivoting)
 {
-    if (count <= 0 || first < 0 || !v.status) return hipErrorInvalidValue;
+    if (count <= 0 || first < 0 || !v.status || !det.valid() || (!v.inv && det.empty())) return hipErrorInvalidValue;
+    const VbatchDetArgs<T> vd{v, det.mant, det.exp};
     ProfScope ps(prof, KC_PANEL, stream);
-    switch (rows_per_thread) {
-        case 40: workgroup_vlaunch<T, 40>(v, first, count, stream, pivoting); break;
-        case 48: workgroup_vlaunch<T, 48>(v, first, count, stream, pivoting); break;
-        case 56: workgroup_vlaunch<T, 56>(v, first, count, stream, pivoting); break;
-        case 64: workgroup_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool found = workgroup_instance(rows_per_thread, pivoting, [&](auto rpt, auto pivot) {
+        constexpr int RPT = decltype(rpt)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        const dim3 grid((unsigned)count);
+        if (det.empty())
+            hipLaunchKernelGGL((gj_workgroup_vkernel<T, RPT, PIVOT>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
+        else
+            hipLaunchKernelGGL((gj_workgroup_det_vkernel<T, RPT, PIVOT>), grid, dim3(kWorkgroupThreads), 0, stream, vd,
+                               first);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
-template hipError_t workgroup_vinvert(int, const VbatchArgs<float> &, int, int, hipStream_t, Profiler *, bool);
-template hipError_t workgroup_vinvert(int, const VbatchArgs<double> &, int, int, hipStream_t, Profiler *, bool);
-
-template <typename T, int RPT>
-static void workgroup_det_vlaunch(const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream, bool pivoting)
-{
-    const dim3 grid((unsigned)count);
-    if (pivoting)
-        hipLaunchKernelGGL((gj_workgroup_det_vkernel<T, RPT, true>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
-    else
-        hipLaunchKernelGGL((gj_workgroup_det_vkernel<T, RPT, false>), grid, dim3(kWorkgroupThreads), 0, stream, v, first);
-}
-
-template <typename T>
-hipError_t workgroup_vinvert_det(int rows_per_thread, const VbatchDetArgs<T> &v, int first, int count, hipStream_t stream,
-                                 Profiler *prof, bool pivoting)
-{
-    if (count <= 0 || first < 0 || !v.v.status || !v.det_mant || !v.det_exp) return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_PANEL, stream);
-    switch (rows_per_thread) {
-        case 40: workgroup_det_vlaunch<T, 40>(v, first, count, stream, pivoting); break;
-        case 48: workgroup_det_vlaunch<T, 48>(v, first, count, stream, pivoting); break;
-        case 56: workgroup_det_vlaunch<T, 56>(v, first, count, stream, pivoting); break;
-        case 64: workgroup_det_vlaunch<T, 64>(v, first, count, stream, pivoting); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-template hipError_t workgroup_vinvert_det(int, const VbatchDetArgs<float> &, int, int, hipStream_t, Profiler *, bool);
-template hipError_t workgroup_vinvert_det(int, const VbatchDetArgs<double> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_vinvert(int, const VbatchArgs<float> &, DetOut, int, int, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_vinvert(int, const VbatchArgs<double> &, DetOut, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

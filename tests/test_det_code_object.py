@@ -3,14 +3,10 @@ gj_resident_det_kernel / gj_resident_det_vkernel (T in {float, double} x L in {8
 gj_workgroup_det_kernel / gj_workgroup_det_vkernel (RPT in {40, 48, 56, 64}) -- and none of them touches scratch or
 spills: the three words of the accumulator must not push a register array into memory.  The register counts are
 printed, not asserted (DESIGN.md section 12 has the table)."""
-import os
 import re
-import shutil
-import subprocess
 
-from gpu_matrix_inversion_amd import _lib
+from code_object import kernel_metadata
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 WANT = {(kern, var, t, size, piv) for kern, sizes in (("resident", (8, 16, 32, 64)), ("workgroup", (40, 48, 56, 64)))
         for var in ("kernel", "vkernel") for t in ("f", "d") for size in sizes for piv in (0, 1)}
 
@@ -21,22 +17,7 @@ def _instance(name):
 
 
 def test_det_instances_use_no_scratch(tmp_path):
-    copy = tmp_path / os.path.basename(_lib.LIB_PATH)
-    shutil.copy(_lib.LIB_PATH, copy)
-    subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", str(copy)], check=True, capture_output=True, cwd=tmp_path)
-    meta = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "gfx950" not in f:
-            continue
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for entry in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-            name = re.search(r"\n    \.name:\s+(\S+)", entry)
-            if name and _instance(name.group(1)) is not None:
-                meta[_instance(name.group(1))] = {
-                    key: int(re.search(r"\.%s:\s+(\d+)" % key, entry).group(1))
-                    for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count",
-                                "group_segment_fixed_size")}
+    meta = {_instance(name): m for name, m in kernel_metadata(tmp_path).items() if _instance(name) is not None}
     assert len(WANT) == 64 and set(meta) == WANT, sorted(WANT ^ set(meta))
     print("\n kernel     form     T     size pivot  vgpr  sgpr   lds")
     for (kern, var, t, size, piv), m in sorted(meta.items()):

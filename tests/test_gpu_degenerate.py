@@ -10,6 +10,7 @@ member's dtype), with the generator's written-down inverse or with the oracle's 
 import numpy as np
 import pytest
 
+from batch_helpers import strided
 from conftest import canonical_bytes, gate_matrix
 from degenerate_cases import (OVERFLOW_LIST, block_diagonal, canon, duplicate_rows, exact_families, ones_block, overflow,
                               signed_pow2_permutation, zero_column, zero_row)
@@ -201,28 +202,13 @@ def test_late_singular_members_in_a_workgroup_batch(oracle, inv_wg, n, dtype):
 
 
 # ---- 3. variable-size batch -----------------------------------------------------------------------------------------
-def _strided(mats, pad, fill):
-    """The members one after the other at leading dimension n + pad; the padding columns hold `fill`.  Returns
-    (flat buffer, element offset per member, leading dimensions, padding mask)."""
-    lds = np.array([m.shape[0] + pad for m in mats], np.int32)
-    sizes = np.array([m.shape[0] * ld for m, ld in zip(mats, lds)], np.int64)
-    off = np.concatenate(([0], np.cumsum(sizes)[:-1]))
-    buf = np.full(int(sizes.sum()), fill, mats[0].dtype)
-    is_pad = np.ones(buf.size, bool)
-    for m, o, ld in zip(mats, off, lds):
-        n = m.shape[0]
-        buf[o:o + n * ld].reshape(n, ld)[:, :n] = m
-        is_pad[o:o + n * ld].reshape(n, ld)[:, :n] = False
-    return buf, off, lds, is_pad
-
-
 def _run_strided(inv, mats, sentinel):
     """One inv_pointers call over strided members, the output a sentinel-filled buffer; (members, statuses).  Asserts
     that every output padding element is still the sentinel and that the input is unchanged."""
     tdt = torch.float32 if mats[0].dtype == np.float32 else torch.float64
     es = mats[0].dtype.itemsize
-    a_buf, a_off, lda, _ = _strided(mats, 3, np.nan)            # NaN in the input padding: never read
-    o_buf, o_off, ldo, o_pad = _strided([np.zeros_like(m) for m in mats], 5, sentinel)
+    a_buf, a_off, lda, _ = strided(mats, 3, np.nan)            # NaN in the input padding: never read
+    o_buf, o_off, ldo, o_pad = strided([np.zeros_like(m) for m in mats], 5, sentinel)
     o_buf[:] = sentinel
     ta, to = torch.from_numpy(a_buf).cuda(), torch.from_numpy(o_buf).cuda()
     keep = ta.clone()

@@ -6,12 +6,11 @@ member whose oracle status is 0 must equal the step-by-step CPU oracle bit for b
 status word must equal the oracle's.
 """
 import ctypes
-import statistics
-import time
 
 import numpy as np
 import pytest
 
+from batch_helpers import assert_members_equal, median_ms
 from conftest import gate_matrix
 from resident_cases import (BIG_BATCHES, FP64_ORDERS, TIE_ORDERS, TIMED_SHAPES, big_batch, dist_matrix, dominant,
                             oracle_batch, run, shared_wave_batch, tie_batch)
@@ -45,11 +44,6 @@ def _batch_of_7(kind, n):
     return np.stack([dist_matrix(kind, n, 9000 + 100 * n + b) for b in range(7)])
 
 
-def _assert_members_equal(got, want, tag):
-    for b in range(len(want)):
-        assert np.array_equal(got[b], want[b]), (tag, b, float(np.abs(got[b] - want[b]).max()))
-
-
 @pytest.mark.parametrize("n", range(1, 65))
 def test_fp32_every_order_bit_identical_to_oracle(oracle, inv_res, n):
     assert inv_res.resolved_algo(n, 7) == g.ALGO_RESIDENT
@@ -60,7 +54,7 @@ def test_fp32_every_order_bit_identical_to_oracle(oracle, inv_res, n):
         want, want_st = oracle_batch(oracle.matrix_inv_32, mats, n)
         got, st = run(inv_res, mats)
         assert list(want_st) == [0] * 7 and list(st) == [0] * 7, (kind, n, list(st), list(want_st))
-        _assert_members_equal(got, want, (kind, n))
+        assert_members_equal(got, want, (kind, n))
 
 
 @pytest.mark.parametrize("n", FP64_ORDERS)
@@ -73,7 +67,7 @@ def test_fp64_bit_identical_to_oracle(oracle, inv_res, n):
         got, st = run(inv_res, mats)
         assert got.dtype == np.float64
         assert list(want_st) == [0] * 7 and list(st) == [0] * 7, (kind, n, list(st), list(want_st))
-        _assert_members_equal(got, want, (kind, n))
+        assert_members_equal(got, want, (kind, n))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
@@ -85,7 +79,7 @@ def test_no_pivot_bit_identical_to_oracle(oracle, inv_res_nopivot, n, dtype):
     got, st = run(inv_res_nopivot, mats)
     assert got.dtype == dtype
     assert list(want_st) == [0] * 5 and list(st) == [0] * 5
-    _assert_members_equal(got, want, (n, dtype))
+    assert_members_equal(got, want, (n, dtype))
     if n >= 3:
         h = mats[0].copy()
         h[1, 1] = 0.0
@@ -103,7 +97,7 @@ def test_ties_the_lowest_row_wins(oracle, inv_res, n):
     assert list(want_st) == [0] * 16   # no member is skipped: a singular draw fails here
     got, st = run(inv_res, mats)
     assert list(st) == [0] * 16
-    _assert_members_equal(got, want, n)
+    assert_members_equal(got, want, n)
 
 
 def test_status_inside_a_shared_wave(oracle, inv_res):
@@ -208,18 +202,6 @@ def test_asynchronous_pure_and_deterministic(inv_res):
     assert rc == 0 and torch.equal(out64, w64)
 
 
-def _median_ms(inv, a, out, st, warmup=2, calls=5):
-    ts = []
-    for i in range(warmup + calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        inv.inv(a, out=out, status=st)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
-
-
 @pytest.mark.parametrize("n,batch", TIMED_SHAPES)
 def test_faster_than_the_path_auto_resolves_to(inv_res, n, batch):
     """Only the direction is asserted (no ratio was known before this path existed): for these three batches of
@@ -235,12 +217,12 @@ def test_faster_than_the_path_auto_resolves_to(inv_res, n, batch):
     try:
         assert auto.resolved_algo(n, batch) == (g.ALGO_SWEEP if n < 32 else g.ALGO_BLOCKED)
         auto.reserve(n, batch)
-        t_auto = _median_ms(auto, a, out, st)
+        t_auto = median_ms(lambda: auto.inv(a, out=out, status=st))
         x_auto = out.clone()
         assert not st.any()
     finally:
         auto.close()
-    t_res = _median_ms(inv_res, a, out, st)
+    t_res = median_ms(lambda: inv_res.inv(a, out=out, status=st))
     assert not st.any()
     print(f"\nn={n} batch={batch}: resident {t_res:.3f} ms, auto {t_auto:.3f} ms, ratio {t_auto / t_res:.1f}x")
     assert torch.equal(out, x_auto)      # both evaluate the reference's operation order

@@ -7,12 +7,11 @@ must equal the step-by-step CPU oracle bit for bit (``np.array_equal``) and ever
 oracle's.  The oracle's status is asserted first, so no member is ever left out of a comparison.
 """
 import ctypes
-import statistics
-import time
 
 import numpy as np
 import pytest
 
+from batch_helpers import assert_members_equal, median_ms, strided
 from vbatch_cases import (BENCH_SHAPES, BIG_MEMBERS, bench_members, big_mixed_members, diag_block_orders,
                           dominant_members, every_order_members, invalid_between_valid, oracle_members, pack, unpack)
 
@@ -51,13 +50,6 @@ def _run_packed(inverter, mats):
     return unpack(x.cpu().numpy(), orders), st.cpu().numpy().tolist(), counts
 
 
-def _assert_members_equal(got, want, tag):
-    assert len(got) == len(want)
-    for b in range(len(want)):
-        assert got[b].dtype == want[b].dtype and np.array_equal(got[b], want[b]), \
-            (tag, b, want[b].shape, float(np.abs(got[b] - want[b]).max()))
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
 def test_every_order_in_one_call(oracle, inv, dtype):
     mats = [m.astype(dtype) for m in every_order_members()]
@@ -67,7 +59,7 @@ def test_every_order_in_one_call(oracle, inv, dtype):
     got, st, counts = _run_packed(inv, mats)
     assert all(c > 0 for c in counts) and len(counts) == 8, counts
     assert st == [0] * 511, [b for b, s in enumerate(st) if s]
-    _assert_members_equal(got, want, dtype)
+    assert_members_equal(got, want, dtype)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
@@ -78,7 +70,7 @@ def test_no_pivot(oracle, inv_nopivot, dtype):
     got, st, counts = _run_packed(inv_nopivot, mats)
     assert all(c > 0 for c in counts)
     assert st == [0] * 128
-    _assert_members_equal(got, want, dtype)
+    assert_members_equal(got, want, dtype)
     # one member whose (1,1) entry is, and stays, exactly zero: it alone is reported, its neighbours are untouched
     for victim in (next(b for b, m in enumerate(mats) if 3 <= m.shape[0] <= 64),
                    next(b for b, m in enumerate(mats) if m.shape[0] > 64)):
@@ -129,29 +121,13 @@ def test_invalid_members_between_valid_ones(oracle, inv):
             assert np.array_equal(got[b], want[b]), b
 
 
-def _strided(mats, pad, fill):
-    """The members one after the other at leading dimension n + pad; the padding columns hold `fill`.  Returns
-    (flat buffer, element offset per member, leading dimensions, padding mask)."""
-    lds = np.array([m.shape[0] + pad for m in mats], np.int32)
-    sizes = np.array([m.shape[0] * ld for m, ld in zip(mats, lds)], np.int64)
-    off = np.concatenate(([0], np.cumsum(sizes)[:-1]))
-    buf = np.full(int(sizes.sum()), fill, mats[0].dtype)
-    is_pad = np.ones(buf.size, bool)
-    for m, o, ld in zip(mats, off, lds):
-        n = m.shape[0]
-        view = buf[o:o + n * ld].reshape(n, ld)
-        view[:, :n] = m
-        is_pad[o:o + n * ld].reshape(n, ld)[:, :n] = False
-    return buf, off, lds, is_pad
-
-
 def test_strided_members_and_untouched_padding(oracle, inv):
     mats = every_order_members()
     want, want_st = oracle_members(oracle.matrix_inv_32, mats)
     assert want_st == [0] * 511
-    a_buf, a_off, lda, _ = _strided(mats, 3, np.nan)           # NaN in the input padding: never read
+    a_buf, a_off, lda, _ = strided(mats, 3, np.nan)           # NaN in the input padding: never read
     sentinel = np.float32(-12345.5)
-    o_buf, o_off, ldo, o_pad = _strided([np.zeros_like(m) for m in mats], 5, sentinel)
+    o_buf, o_off, ldo, o_pad = strided([np.zeros_like(m) for m in mats], 5, sentinel)
     o_buf[:] = sentinel
     ta, to = torch.from_numpy(a_buf).cuda(), torch.from_numpy(o_buf).cuda()
     keep = ta.clone()
@@ -226,7 +202,7 @@ def test_more_members_than_a_grid_dimension_holds(oracle, inv):
     _, want_flat = pack(want)
     _, got_flat = pack(got)
     assert np.array_equal(got_flat, want_flat)                  # every member, none sampled
-    _assert_members_equal(got, want, "big")
+    assert_members_equal(got, want, "big")
 
 
 def test_plan_reuse_streams_and_null_status(inv):
@@ -305,18 +281,6 @@ def test_host_side_checks(inv):
             inv.plan_ragged(bad)
 
 
-def _median_ms(fn, warmup=2, calls=5):
-    ts = []
-    for i in range(warmup + calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
-
-
 @pytest.mark.parametrize("members,lo,hi", BENCH_SHAPES[:2])
 def test_one_call_beats_one_call_per_order(inv, members, lo, hi):
     """Only the direction is asserted (no ratio was known before this feature existed): one ``inv_ragged`` call must
@@ -342,8 +306,8 @@ def test_one_call_beats_one_call_per_order(inv, members, lo, hi):
     st = torch.empty(members, dtype=torch.int32, device="cuda")
     plan = inv.plan_ragged(orders)
     try:
-        t_loop = _median_ms(per_order)
-        t_one = _median_ms(lambda: inv.inv_ragged(plan, a, out=out, status=st))
+        t_loop = median_ms(per_order)
+        t_one = median_ms(lambda: inv.inv_ragged(plan, a, out=out, status=st))
     finally:
         plan.close()
     print(f"\n{members} members, orders {lo}..{hi}: one call {t_one:.3f} ms, {len(distinct)} calls {t_loop:.3f} ms, "

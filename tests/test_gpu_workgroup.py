@@ -6,12 +6,11 @@ member whose oracle status is 0 must equal the step-by-step CPU oracle bit for b
 status word must equal the oracle's.
 """
 import ctypes
-import statistics
-import time
 
 import numpy as np
 import pytest
 
+from batch_helpers import assert_members_equal, median_ms
 from conftest import gate_matrix
 from workgroup_cases import (BIG_BATCH, BIG_DISTINCT, BIG_ORDER, FP64_ORDERS, KINDS, MEMBERS, ORDERS, TIE_ORDERS,
                              TIMED_SHAPES, big_distinct, big_index, dominant, dominant_batch, family_batch, mixed_batch,
@@ -38,11 +37,6 @@ def inv_wg_nopivot():
     inv.close()
 
 
-def _assert_members_equal(got, want, tag):
-    for b in range(len(want)):
-        assert np.array_equal(got[b], want[b]), (tag, b, float(np.abs(got[b] - want[b]).max()))
-
-
 @pytest.mark.parametrize("n", ORDERS)
 def test_fp32_every_order_bit_identical_to_oracle(oracle, inv_wg, n):
     assert inv_wg.resolved_algo(n, MEMBERS) == g.ALGO_WORKGROUP == 4
@@ -52,7 +46,7 @@ def test_fp32_every_order_bit_identical_to_oracle(oracle, inv_wg, n):
         want, want_st = oracle_batch(oracle.matrix_inv_32, mats, n)
         got, st = run(inv_wg, mats)
         assert list(want_st) == [0] * MEMBERS and list(st) == [0] * MEMBERS, (kind, n, list(st), list(want_st))
-        _assert_members_equal(got, want, (kind, n))
+        assert_members_equal(got, want, (kind, n))
 
 
 @pytest.mark.parametrize("n", FP64_ORDERS)
@@ -63,7 +57,7 @@ def test_fp64_bit_identical_to_oracle(oracle, inv_wg, n):
         got, st = run(inv_wg, mats)
         assert got.dtype == np.float64
         assert list(want_st) == [0] * MEMBERS and list(st) == [0] * MEMBERS, (kind, n, list(st), list(want_st))
-        _assert_members_equal(got, want, (kind, n))
+        assert_members_equal(got, want, (kind, n))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
@@ -75,7 +69,7 @@ def test_no_pivot_bit_identical_to_oracle(oracle, inv_wg_nopivot, n, dtype):
     got, st = run(inv_wg_nopivot, mats)
     assert got.dtype == dtype
     assert list(want_st) == [0] * MEMBERS and list(st) == [0] * MEMBERS
-    _assert_members_equal(got, want, (n, dtype))
+    assert_members_equal(got, want, (n, dtype))
     h = zero_diagonal_entry(n, dtype)
     want_h = oracle.matrix_inversion_no_pivots(h, n, return_info=True)[1]["status"]
     _, st = run(inv_wg_nopivot, h)
@@ -90,7 +84,7 @@ def test_ties_the_lowest_row_wins(oracle, inv_wg, n):
     assert list(want_st) == [0] * 16   # no member is skipped: a singular draw fails here
     got, st = run(inv_wg, mats)
     assert list(st) == [0] * 16
-    _assert_members_equal(got, want, n)
+    assert_members_equal(got, want, n)
 
 
 def test_invalid_members_among_valid_ones(oracle, inv_wg):
@@ -215,18 +209,6 @@ def test_asynchronous_pure_and_deterministic(inv_wg):
     assert rc == 0 and torch.equal(out64, w64)
 
 
-def _median_ms(inv, a, out, st, warmup=2, calls=5):
-    ts = []
-    for i in range(warmup + calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        inv.inv(a, out=out, status=st)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
-
-
 @pytest.mark.parametrize("n,batch", TIMED_SHAPES)
 def test_faster_than_the_path_auto_resolves_to(inv_wg, n, batch):
     """Only the direction is asserted (no ratio was known before this path existed): for these two batches one
@@ -243,13 +225,13 @@ def test_faster_than_the_path_auto_resolves_to(inv_wg, n, batch):
     try:
         assert auto.resolved_algo(n, batch) == g.ALGO_BLOCKED
         auto.reserve(n, batch)
-        t_auto = _median_ms(auto, a, out, st)
+        t_auto = median_ms(lambda: auto.inv(a, out=out, status=st))
         x_auto = out.clone()
         assert not st.any()
     finally:
         auto.close()
     assert inv_wg.resolved_algo(n, batch) == g.ALGO_WORKGROUP
-    t_wg = _median_ms(inv_wg, a, out, st)
+    t_wg = median_ms(lambda: inv_wg.inv(a, out=out, status=st))
     assert not st.any()
     print(f"\nn={n} batch={batch}: workgroup {t_wg:.3f} ms, auto {t_auto:.3f} ms, ratio {t_auto / t_wg:.2f}x")
     assert torch.equal(out, x_auto)      # both evaluate the reference's operation order

@@ -3,14 +3,10 @@ gj_resident_kernel are there -- T in {float, double} x L in {8, 16, 32, 64} x PI
 touches scratch.  Zero is not a tuned number: a register-resident kernel that touches scratch is indexing its
 registers at run time or spilling, and that is the defect this test is there to catch.  The register counts are
 printed, not asserted (DESIGN.md has the table)."""
-import os
 import re
-import shutil
-import subprocess
 
-from gpu_matrix_inversion_amd import _lib
+from code_object import kernel_metadata
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 WANT = {(t, lanes, piv) for t in ("f", "d") for lanes in (8, 16, 32, 64) for piv in (0, 1)}
 
 
@@ -20,21 +16,7 @@ def _instance(name):
 
 
 def test_resident_instances_use_no_scratch(tmp_path):
-    copy = tmp_path / os.path.basename(_lib.LIB_PATH)
-    shutil.copy(_lib.LIB_PATH, copy)
-    subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", str(copy)], check=True, capture_output=True, cwd=tmp_path)
-    meta = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "gfx950" not in f:
-            continue
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for entry in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-            name = re.search(r"\n    \.name:\s+(\S+)", entry)
-            if name and _instance(name.group(1)) is not None:
-                meta[_instance(name.group(1))] = {
-                    key: int(re.search(r"\.%s:\s+(\d+)" % key, entry).group(1))
-                    for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count")}
+    meta = {_instance(name): m for name, m in kernel_metadata(tmp_path).items() if _instance(name) is not None}
     assert set(meta) == WANT, sorted(WANT ^ set(meta))
     print("\n T   L  pivot  vgpr  sgpr")
     for (t, lanes, piv), m in sorted(meta.items()):

@@ -2,14 +2,10 @@
 (T in {float, double} x L in {8, 16, 32, 64} x PIVOT in {0, 1}) and the 16 of gj_workgroup_vkernel (RPT in {40, 48,
 56, 64}) are there, and none of them touches scratch or spills -- a per-member order must not turn a register index
 into a run-time one.  The register counts are printed, not asserted (DESIGN.md section 11 has the table)."""
-import os
 import re
-import shutil
-import subprocess
 
-from gpu_matrix_inversion_amd import _lib
+from code_object import kernel_metadata
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 WANT = {(kern, t, size, piv) for kern, sizes in (("resident", (8, 16, 32, 64)), ("workgroup", (40, 48, 56, 64)))
         for t in ("f", "d") for size in sizes for piv in (0, 1)}
 
@@ -20,22 +16,7 @@ def _instance(name):
 
 
 def test_variable_size_instances_use_no_scratch(tmp_path):
-    copy = tmp_path / os.path.basename(_lib.LIB_PATH)
-    shutil.copy(_lib.LIB_PATH, copy)
-    subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", str(copy)], check=True, capture_output=True, cwd=tmp_path)
-    meta = {}
-    for f in sorted(os.listdir(tmp_path)):
-        if "gfx950" not in f:
-            continue
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(tmp_path / f)], check=True, capture_output=True,
-                               text=True).stdout
-        for entry in re.split(r"\n  - \.agpr_count:", notes)[1:]:
-            name = re.search(r"\n    \.name:\s+(\S+)", entry)
-            if name and _instance(name.group(1)) is not None:
-                meta[_instance(name.group(1))] = {
-                    key: int(re.search(r"\.%s:\s+(\d+)" % key, entry).group(1))
-                    for key in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count",
-                                "group_segment_fixed_size")}
+    meta = {_instance(name): m for name, m in kernel_metadata(tmp_path).items() if _instance(name) is not None}
     assert len(WANT) == 32 and set(meta) == WANT, sorted(WANT ^ set(meta))
     print("\n kernel     T     size pivot  vgpr  sgpr   lds")
     for (kern, t, size, piv), m in sorted(meta.items()):

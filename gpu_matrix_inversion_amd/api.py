@@ -540,10 +540,21 @@ class Inverter:
         return {name: (ms[i], int(cnt[i])) for i, name in enumerate(_lib.KERNEL_CLASSES)}
 
     def residual(self, a, x):
-        """Device-side check: returns a (B,3) float64 tensor [||AX-I||_inf, ||XA-I||_inf, sqrt(N)-||AX||_F]."""
+        """Device-side check: returns a (B,3) float64 tensor [||AX-I||_inf, ||XA-I||_inf, sqrt(N)-||AX||_F].
+        a, x: float32 tensors on this device of one shape, (N,N) or (B,N,N), any B; anything else raises ValueError.
+        A member with a NaN entry gives NaN in its three outputs; the other members are not affected."""
         torch = self._torch
+        for t, what in ((a, "a"), (x, "x")):
+            if t.dtype != torch.float32 or not t.is_cuda:
+                raise ValueError(f"{what}: expected a float32 tensor on the GPU")
+            if t.device != self.device:
+                raise ValueError(f"{what} is on {t.device}, expected {self.device}")
         a3 = (a.unsqueeze(0) if a.dim() == 2 else a).contiguous()
         x3 = (x.unsqueeze(0) if x.dim() == 2 else x).contiguous()
+        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
+            raise ValueError("expected (N,N) or (B,N,N)")
+        if x3.shape != a3.shape:
+            raise ValueError(f"x has shape {tuple(x.shape)}, a {tuple(a.shape)}")
         b, n = a3.shape[0], a3.shape[1]
         out = torch.empty(b, 3, dtype=torch.float64, device=a3.device)
         self._bind_stream()

@@ -155,9 +155,16 @@ hipError_t residual_launch(const float *d_a, const float *d_x, int n, int batch,
 {
     hipError_t e = hipMemsetAsync(ws, 0, ((size_t)2 * n + 2) * sizeof(double) * batch, stream);
     if (e != hipSuccess) return e;
-    const dim3 grid((n + 63) / 64, (n + 63) / 64, batch);
-    hipLaunchKernelGGL(residual_tile_kernel<float>, grid, dim3(256), 0, stream, d_a, d_x, n, (double *)ws, 0);
-    hipLaunchKernelGGL(residual_tile_kernel<float>, grid, dim3(256), 0, stream, d_x, d_a, n, (double *)ws, 1);
+    // the member index is blockIdx.z, which the grid limits to 65535: the tile launches go in chunks of members
+    const int chunk_members = 32768;
+    for (int b0 = 0; b0 < batch; b0 += chunk_members) {
+        const int nb = batch - b0 < chunk_members ? batch - b0 : chunk_members;
+        const dim3 grid((n + 63) / 64, (n + 63) / 64, nb);
+        const float *a = d_a + (size_t)b0 * n * n, *x = d_x + (size_t)b0 * n * n;
+        double *w = (double *)ws + (size_t)b0 * (2 * (size_t)n + 2);
+        hipLaunchKernelGGL(residual_tile_kernel<float>, grid, dim3(256), 0, stream, a, x, n, w, 0);
+        hipLaunchKernelGGL(residual_tile_kernel<float>, grid, dim3(256), 0, stream, x, a, n, w, 1);
+    }
     hipLaunchKernelGGL(residual_finalize_kernel, dim3(batch), dim3(256), 0, stream, (const double *)ws, n, d_out);
     return hipGetLastError();
 }

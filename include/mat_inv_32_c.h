@@ -215,7 +215,10 @@ int mi32_inv_det_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const dou
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all
- * accumulated in fp64.  d_out: device double[3*batch].  Asynchronous. */
+ * accumulated in fp64.  d_out: device double[3*batch].  Any batch size.  A NaN operand
+ * entry gives NaN in all three outputs of that member (and of no other); an infinite one
+ * gives +inf in the norms it reaches (NaN where it meets a zero) and -inf or NaN in the
+ * third.  Asynchronous. */
 int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out);
 
 /* ---- per-phase timing (the reference's FP32_bench.cpp:256-443 timing slots) ---------- */

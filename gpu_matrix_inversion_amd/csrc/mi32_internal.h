@@ -35,7 +35,7 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
 }
 
 // Blocked fp32 plans with shared panels only: true when matrix b was given up (see SubpanelArgs::guard in
-// mi32_blocked.hip; guard may be null).  Wave-uniform.
+// mi32_blocked_internal.h; guard may be null).  Wave-uniform.
 __device__ __forceinline__ bool matrix_given_up(const int *guard, int b)
 {
     return guard != nullptr && __builtin_amdgcn_readfirstlane(guard[b]) == MI32_RUNTIME_ERROR;

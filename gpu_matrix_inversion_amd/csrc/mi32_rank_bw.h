@@ -5,7 +5,7 @@
 // i.e. fixColumnKernel (/root/reference/Matlab/mat_inv_32/mat_inv_32/mat_inv_32.cpp:13-57) for all columns outside
 // the current block of kdim pivots, with the block's kdim eliminations applied at once on the fp32 matrix cores, in
 // the reference's own order: f_m[i] = the entry row i had in the pivot column when step m ran (the block's
-// multipliers), u_m[j] = the pivot row of step m as fixColumn saw it (the block's strip, mi32_blocked.hip), C = the
+// multipliers), u_m[j] = the pivot row of step m as fixColumn saw it (the block's strip, mi32_strip.h), C = the
 // element's old value -- a v_mfma_f32_32x32x2_f32 chain with C as its accumulator is exactly that fmaf chain.
 //
 //  * both operand tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4): no staging registers, no
@@ -15,40 +15,11 @@
 //    an A tile is [BK][128] contiguous rows exactly like a B tile -- the LDS image of an LDS-DMA is lane-linear, it
 //    cannot transpose; the B operand ub[k][col] is compact and k-major as the strip leaves it.
 #pragma once
-#include "mi32_internal.h"
+#include "mi32_blocked_internal.h"
 #include <type_traits>
 #include <utility>
 
 namespace mi32 {
-
-// Where a wide kernel exports freshly computed columns for the panel workgroup: columns
-// [col, col + w * count) go to `count` consecutive compact panels (w columns each) starting at `base`.
-struct PanelExport {
-    float *base;     // first compact panel, matrix 0
-    size_t bstride;  // floats between consecutive compact panels
-    int col, w, count;
-};
-__device__ __forceinline__ void panel_export_store(const PanelExport &e, size_t tstride, int b, int np, int col, int grow,
-                                                   float v)
-{
-    const int idx = col - e.col;
-    if ((unsigned)idx < (unsigned)(e.w * e.count))
-        e.base[(size_t)(idx / e.w) * e.bstride + (size_t)b * tstride + (size_t)(idx % e.w) * np + grow] = v;
-}
-
-// four consecutive rows (grow4 a multiple of 4) of one exported column: one 16-byte store
-__device__ __forceinline__ void panel_export_store4(const PanelExport &e, size_t tstride, int b, int np, int col,
-                                                    int grow4, float v0, float v1, float v2, float v3)
-{
-    const int idx = col - e.col;
-    if ((unsigned)idx < (unsigned)(e.w * e.count)) {
-        typedef float pe_f4v __attribute__((ext_vector_type(4)));
-        pe_f4v v;
-        v[0] = v0; v[1] = v1; v[2] = v2; v[3] = v3;
-        *reinterpret_cast<pe_f4v *>(e.base + (size_t)(idx / e.w) * e.bstride + (size_t)b * tstride +
-                                    (size_t)(idx % e.w) * np + grow4) = v;
-    }
-}
 
 typedef float rb_float16v __attribute__((ext_vector_type(16)));
 typedef float rb_f4v __attribute__((ext_vector_type(4)));
@@ -68,7 +39,7 @@ constexpr size_t rank_bw2_lds_bytes(int kdim)
     return (size_t)(2 * BK * (128 + BN)) * sizeof(float) + (size_t)(128 + kdim) * sizeof(int);
 }
 
-// XCD-aware tile order (see mi32_blocked.hip): workgroups that share an XCD (= an L2) cover a compact sub-grid of
+// XCD-aware tile order: workgroups that share an XCD (= an L2) cover a compact sub-grid of
 // TR/2 x TC/4 tiles, and walk it in column strips of `sw` tiles, row by row inside a strip: the strip's B operand
 // (sw x 128 columns x kdim steps) stays in the XCD's 4 MB L2 while the rows go by, and every A row tile is fetched once
 // per strip.  Row-major over the whole sub-grid (rounds 1-2) re-fetched the sub-grid's B panel for every few tile rows
@@ -101,19 +72,6 @@ __device__ __forceinline__ void rb_tile_of(int id, int TR, int TC, int sw, int &
         ct = id % TC;
     }
 }
-
-// Diagnostic builds (-DMI32_RB_STAMPS) record s_memtime at the phase boundaries of
-// every workgroup; in the product build the macro expands to nothing.
-#ifdef MI32_RB_STAMPS
-__device__ unsigned long long *g_rb_stamps;  // [workgroup][8]
-#define MI32_RB_STAMP(slot_)                                                                          \
-    do {                                                                                              \
-        if (g_rb_stamps && threadIdx.x == 0)                                                          \
-            g_rb_stamps[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (slot_)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define MI32_RB_STAMP(slot_) do { } while (0)
-#endif
 
 // One 128 x BN output tile (rt, ct) of matrix b (BN = 128 or 64: 4 waves as 2 x 2, 64 x BN/2 each).
 // rb_smem: rank_bw2_lds_bytes<BK, BN>(kdim) bytes of LDS.
@@ -166,7 +124,6 @@ __device__ __forceinline__ void rank_bw2_tile(
     // later sub-panels' steps: gj_mult_transpose_kernel has zeroed their other multipliers.
     const bool tile_in_block = (row0 >= c0 && row0 < c0 + kdim);
 
-    MI32_RB_STAMP(0);
     if (tid < BM) s_map[tid] = map[row0 + tid];
     __syncthreads();
 
@@ -229,7 +186,6 @@ __device__ __forceinline__ void rank_bw2_tile(
             }
         }
     }
-    MI32_RB_STAMP(1);
     MI32_RB_ISSUE(0, 0)
     for (int t = 0; t < nk; ++t) {
         const int buf = t & 1;
@@ -265,7 +221,6 @@ __device__ __forceinline__ void rank_bw2_tile(
         }
     }
 #undef MI32_RB_ISSUE
-    MI32_RB_STAMP(2);
 
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
@@ -286,15 +241,6 @@ __device__ __forceinline__ void rank_bw2_tile(
                                     acc[tm][tn][4 * q], acc[tm][tn][4 * q + 1], acc[tm][tn][4 * q + 2],
                                     acc[tm][tn][4 * q + 3]);
         }
-    MI32_RB_STAMP(3);
-#ifdef MI32_RB_STAMPS
-    if (g_rb_stamps && threadIdx.x == 0) {
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_rb_stamps[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + 4] = ((unsigned long long)xcc << 32) | hwid;
-    }
-#endif
 }
 
 template <int BK, int WPS, int BN = 128>

@@ -57,7 +57,7 @@ def main():
             ms = [float(l.split()[1]) for l in out.stdout.splitlines() if l.startswith("MS")]
             if not ms:
                 print(lib, "FAILED", out.stderr[-400:])
-                continue
+                sys.exit(1)  # nothing more is started on a GPU a build has just failed on
             res[lib].append(ms[0])
     for lib, v in res.items():
         v = sorted(v)

@@ -73,6 +73,9 @@ C_ABI_SYMBOLS = (
     "mi32_inv_det_device_f64",
     "mi32_inv_det_device_vbatched",
     "mi32_inv_det_device_vbatched_f64",
+    "mi32_solve_device",
+    "mi32_solve_device_f64",
+    "mi32_resolve_solve",
     "mi32_dominant_kernel",
     "mi32_last_error",
     "mi32_version",
@@ -211,6 +214,11 @@ def load() -> ctypes.CDLL:
     for fn in (lib.mi32_inv_det_device_vbatched, lib.mi32_inv_det_device_vbatched_f64):
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for fn in (lib.mi32_solve_device, lib.mi32_solve_device_f64):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp]
+    lib.mi32_resolve_solve.restype = ctypes.c_int
+    lib.mi32_resolve_solve.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip, ip, ip]
     lib.mi32_dominant_kernel.restype = ctypes.c_char_p
     lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
     lib.mi32_last_error.restype = ctypes.c_char_p

@@ -412,6 +412,62 @@ class Inverter:
                       ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())), "mi32_inv_det_device")
         return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
 
+    def resolved_solve(self, n: int, nrhs: int, elem_bytes: int = 4):
+        """(columns per launch, launches, lanes per member, register rows per thread) of ``solve`` for this shape: a
+        call's ``nrhs`` columns are cut into chunks of at most ``64 - n`` (``n <= 32``) or ``128 - n`` columns, one
+        launch each.  The last two describe the first chunk's kernel: 8 / 16 / 32 / 64 lanes and 0 rows where
+        ``n`` plus the chunk fits 64 lanes (the register-resident kernel), 0 lanes and 40 / 48 / 56 / 64 rows where
+        it takes the workgroup-resident one.  ``n > 127`` or ``nrhs < 1`` raises ValueError."""
+        cols, launches, lanes, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._lib.mi32_resolve_solve(self._h, int(n), int(nrhs), int(elem_bytes), ctypes.byref(cols),
+                                                ctypes.byref(launches), ctypes.byref(lanes), ctypes.byref(rows)),
+                   "mi32_resolve_solve")
+        return cols.value, launches.value, lanes.value, rows.value
+
+    def solve(self, a, b, out=None, status=None):
+        """X with A X = B for every member, without forming the inverse: Gauss-Jordan on [A | B] in the one-launch
+        batch kernels.  a: (N,N) or (B,N,N) float32 / float64 on this device, N <= 127 (a larger N raises ValueError).
+        b: a's dtype and device and a's batch dimension, then (N,) -- one vector per member, the result keeps that
+        shape -- or (N,K).  ``out`` may be ``b`` itself (in place) or a contiguous tensor of b's shape; it must not
+        alias ``a``.  Returns ``(x, status int32[B])``; x of a member whose status is not 0 is unspecified.  With
+        ``b`` the identity, x is ``inv``'s result bit for bit.  More than ``resolved_solve(N, K)[0]`` columns take one
+        launch per chunk, and every launch repeats the elimination of A.  Always runs on the register-resident or
+        workgroup-resident kernels, whatever ``algo`` is.  Asynchronous on torch's current stream."""
+        torch = self._torch
+        if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
+            raise ValueError("expected a float32 or float64 tensor on the GPU")
+        squeeze = a.dim() == 2
+        a3 = a.unsqueeze(0) if squeeze else a
+        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
+            raise ValueError("expected (N,N) or (B,N,N)")
+        bsz, n = a3.shape[0], a3.shape[1]
+        if n > 127:
+            raise ValueError("solve takes orders up to 127")
+        if b.dtype != a.dtype or b.device != a.device:
+            raise ValueError(f"b is {b.dtype} on {b.device}, expected a's {a.dtype} on {a.device}")
+        b3 = b.unsqueeze(-1) if b.dim() == a.dim() - 1 else b
+        if squeeze:
+            b3 = b3.unsqueeze(0)
+        if b3.dim() != 3 or b3.shape[0] != bsz or b3.shape[1] != n or b3.shape[2] == 0:
+            raise ValueError("b: expected a's batch dimension, then (N,) or (N,K)")
+        a3 = a3.contiguous()
+        if out is None:
+            rhs, out3 = b3.contiguous(), torch.empty(b3.shape, dtype=b.dtype, device=b.device)
+        else:
+            if out.shape != b.shape or out.dtype != b.dtype or out.device != b.device or not out.is_contiguous():
+                raise ValueError("out: b itself or a contiguous tensor of b's shape, dtype and device")
+            out3 = out.view(b3.shape)
+            rhs = out3 if out is b else b3.contiguous()
+            if out3.data_ptr() == a3.data_ptr():
+                raise ValueError("out must not alias a")
+        if status is None:
+            status = torch.empty(bsz, dtype=torch.int32, device=a3.device)
+        self._bind_stream()
+        fn = self._lib.mi32_solve_device if a.dtype == torch.float32 else self._lib.mi32_solve_device_f64
+        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, bsz, ctypes.c_void_p(rhs.data_ptr()), b3.shape[2],
+                      ctypes.c_void_p(out3.data_ptr()), ctypes.c_void_p(status.data_ptr())), "mi32_solve_device")
+        return out3.view(b.shape), status
+
     # ---- variable-size batches: mixed orders 1 ... 128, each member at its own pointer and leading dimension ----
     def plan_ragged(self, orders) -> RaggedPlan:
         """Bin a batch of members of the given orders (a sequence or an int array, each 1 ... 128) once."""

@@ -419,9 +419,47 @@ static int one_launch_device(mi32_context *h, const T *d_a, int n, int batch, T 
     return MI32_OK;
 }
 
+// A X = B on the one-launch paths.  A call's nrhs columns are cut into chunks of at most solve_chunk_cols(n): what is
+// left of one 64-lane group beside an order up to 32, of the workgroup's 128 columns above (0: no order of these
+// kernels, or no spare column).  A chunk whose width n + cols fits a 64-lane group runs on the register-resident
+// kernels, a wider one on the workgroup-resident ones.
+static int solve_chunk_cols(int n)
+{
+    return n < 1 || n >= kWorkgroupMaxOrder ? 0 : n <= 32 ? kResidentMaxOrder - n : kWorkgroupMaxOrder - n;
+}
+
+// One launch per chunk, full chunks first; every launch repeats the elimination of A, and the status words are zeroed
+// once: a launch only ever raises a member's flag.  The caller holds h->mu and has set the device.
+template <typename T>
+static int one_launch_solve(mi32_context *h, const T *d_a, int n, int batch, const T *d_b, int nrhs, T *d_x, int *d_status)
+{
+    const int rc = status_buffer(h, d_status, batch, &d_status);
+    if (rc != MI32_OK) return rc;
+    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, h->stream);  // MI32_OK
+    const int cap = solve_chunk_cols(n);
+    for (int col0 = 0; e == hipSuccess && col0 < nrhs; col0 += cap) {
+        const int cols = nrhs - col0 < cap ? nrhs - col0 : cap;
+        const SolveArgs<T> s{d_a, d_b, d_x, d_status, n, batch, nrhs, col0, cols};
+        e = n + cols <= kResidentMaxOrder ? resident_solve(s, h->stream, h->prof, h->pivoting)
+                                          : workgroup_solve(s, h->stream, h->prof, h->pivoting);
+    }
+    if (e != hipSuccess) return fail(e, "kernel launch");
+    return MI32_OK;
+}
+
+// the arguments are checked before the context is touched
+template <typename T>
+static int solve_device(mi32_context *h, const T *d_a, int n, int batch, const T *d_b, int nrhs, T *d_x, int *d_status)
+{
+    if (!h || !d_a || !d_b || !d_x || solve_chunk_cols(n) == 0 || batch <= 0 || nrhs <= 0 || d_x == d_a) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    return one_launch_solve(h, d_a, n, batch, d_b, nrhs, d_x, d_status);
+}
+
 extern "C" {
 
-int mi32_version(void) { return 140; }
+int mi32_version(void) { return 141; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)
@@ -587,6 +625,22 @@ int mi32_resolve_workgroup(mi32_handle_t /*h*/, int n, int elem_bytes, int *thre
     if (threads_per_matrix) *threads_per_matrix = rpt ? 256 : 0;
     if (rows_per_thread) *rows_per_thread = rpt;
     if (max_order) *max_order = kWorkgroupMaxOrder;
+    return MI32_OK;
+}
+
+int mi32_resolve_solve(mi32_handle_t /*h*/, int n, int nrhs, int elem_bytes, int *chunk_cols, int *launches, int *lanes,
+                       int *rows_per_thread)
+{
+    const int cap = solve_chunk_cols(n);
+    if (cap == 0 || nrhs <= 0 || (elem_bytes != 4 && elem_bytes != 8) || !chunk_cols || !launches || !lanes ||
+        !rows_per_thread)
+        return MI32_BAD_SHAPE;
+    const int width = n + (nrhs < cap ? nrhs : cap);  // the first chunk's
+    const bool resident = width <= kResidentMaxOrder;
+    *chunk_cols = cap;
+    *launches = (int)(((long long)nrhs + cap - 1) / cap);
+    *lanes = resident ? resident_lanes(width) : 0;
+    *rows_per_thread = resident ? 0 : workgroup_solve_rows_per_thread(n);
     return MI32_OK;
 }
 
@@ -879,6 +933,18 @@ int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch
                             double *d_det_mant, int *d_det_exp)
 {
     return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const float *d_b, int nrhs, float *d_x,
+                      int *d_status)
+{
+    return solve_device(h, d_a, n, batch, d_b, nrhs, d_x, d_status);
+}
+
+int mi32_solve_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, const double *d_b, int nrhs, double *d_x,
+                          int *d_status)
+{
+    return solve_device(h, d_a, n, batch, d_b, nrhs, d_x, d_status);
 }
 
 int mi32_inv_det_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,

@@ -259,6 +259,31 @@ template <typename T>
 hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, DetOut det, int first, int count,
                              hipStream_t stream, Profiler *prof, bool pivoting);
 
+// ---- A X = B on the two paths above, without the inverse (mi32_solve_device*) ----------------------------------------
+// A lane (register-resident) or column (workgroup-resident) j >= n of a member holds zeros, is read by no step and never
+// stores: the solve kernels (gj_resident_solve_kernel / gj_workgroup_solve_kernel) put a column of B there, and the
+// unchanged pivot step performs Gauss-Jordan on the augmented column -- the row exchange, prn = b[p] / piv, b[i] =
+// fma(-f, prn, b[i]) unless f == 0, b[r] = prn.  One launch takes the `cols` columns of B from `col0` on; n + cols is
+// the launch's WIDTH: at most kResidentMaxOrder for the register-resident kernel (resident_lanes(n + cols) lanes per
+// member), at most kWorkgroupMaxOrder for the workgroup-resident one.  The lanes / columns < n store nothing.
+template <typename T>
+struct SolveArgs {
+    const T *a;   // (batch, n, n) contiguous
+    const T *b;   // (batch, n, nrhs) contiguous
+    T *x;         // (batch, n, nrhs) contiguous; may be b: a member's loads all precede its stores
+    int *status;  // int[batch], zeroed by the host before the first launch of the call
+    int n, batch, nrhs;
+    int col0, cols;  // this launch's columns of B and X
+};
+// rows per thread of the workgroup-resident solve kernel: 40 up to order 80 (an order <= 64 whose width exceeds 64
+// lanes included), then as workgroup_rows_per_thread; 0 outside 1 ... kWorkgroupMaxOrder - 1
+int workgroup_solve_rows_per_thread(int n);
+// hipErrorInvalidValue for a width without an instance, no columns, or a null pointer
+template <typename T>
+hipError_t resident_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting);
+template <typename T>
+hipError_t workgroup_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

@@ -298,6 +298,56 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_det_vkernel(cons
     resident_vmember<T, L, PIVOT, true>(v.v, first, count, v.det_mant, v.det_exp);
 }
 
+// A X = B: group m of the launch takes member m; its lanes j < n hold the columns of A as above, its lanes n ... n +
+// cols - 1 the columns col0 ... of the member's B, and the steps are resident_step's, unchanged: a lane >= n is never
+// column r, so it takes the row exchange, prn = b[p] / piv, the update by column r's multipliers and b[r] = prn.  The
+// rows are exchanged physically, so register row i of such a lane is row i of X; the lanes < n store nothing and the
+// column bookkeeping (`orig`) is dead.  B and X carry no __restrict__: X may be B (a lane stores the column it loaded).
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_kernel(const SolveArgs<T> s)
+{
+    constexpr int kGroups = kResidentThreads / L;  // members per workgroup
+    const int j = threadIdx.x & (L - 1);
+    const long long m = (long long)blockIdx.x * kGroups + threadIdx.x / L;
+    const int n = s.n;
+    // a group past the end of the batch, and a lane past the launch's width, run the steps on zeros
+    const bool mine = m < (long long)s.batch && j < n + s.cols;
+    const bool rhs = j >= n;
+    const size_t member = mine ? (size_t)m : 0;
+    const size_t rhs_at = member * (size_t)n * (size_t)s.nrhs + (size_t)(s.col0 + (rhs ? j - n : 0));
+    const T *in = rhs ? s.b + rhs_at : s.a + (member * (size_t)n * (size_t)n + (size_t)j);
+    const int ld = rhs ? s.nrhs : n;
+    T a[L];
+    bool bad = false;  // boundary rule: a NaN / inf anywhere in A or B is an invalid member
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        if (i < n) {
+            a[i] = mine ? in[(size_t)i * ld] : T(0);
+            bad = bad || (a[i] - a[i] != T(0));
+        } else {
+            a[i] = not_a_candidate(T(0));
+        }
+    }
+    int orig = j;
+    DetAcc det = det_start(false);
+    if constexpr (L <= 16) {
+#pragma unroll
+        for (int r = 0; r < L; ++r)
+            if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);  // n is wave-uniform: a scalar branch
+    } else {
+#pragma unroll 1
+        for (int r = 0; r < n; ++r) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
+    }
+    if (!mine) return;
+    if (rhs) {
+        T *out = s.x + rhs_at;
+#pragma unroll
+        for (int i = 0; i < L; ++i)
+            if (i < n) out[(size_t)i * s.nrhs] = a[i];
+    }
+    if (bad) s.status[member] = MI32_SINGULAR;
+}
+
 // f(lanes, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time pair picks
 // a kernel instance.  false: no instance has that many lanes per matrix.
 template <typename F>
@@ -363,5 +413,24 @@ hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, const DetOut det,
 }
 template hipError_t resident_vinvert(int, const VbatchArgs<float> &, DetOut, int, int, hipStream_t, Profiler *, bool);
 template hipError_t resident_vinvert(int, const VbatchArgs<double> &, DetOut, int, int, hipStream_t, Profiler *, bool);
+
+template <typename T>
+hipError_t resident_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting)
+{
+    const int lanes = s.n >= 1 && s.cols >= 1 ? resident_lanes(s.n + s.cols) : 0;
+    if (lanes == 0 || s.batch <= 0 || s.col0 < 0 || s.col0 + s.cols > s.nrhs || !s.a || !s.b || !s.x || !s.status)
+        return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+        constexpr int L = decltype(l)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        constexpr int kGroups = kResidentThreads / L;
+        const dim3 grid((unsigned)(((long long)s.batch + kGroups - 1) / kGroups));
+        hipLaunchKernelGGL((gj_resident_solve_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, s);
+    });
+    return hipGetLastError();
+}
+template hipError_t resident_solve(const SolveArgs<float> &, hipStream_t, Profiler *, bool);
+template hipError_t resident_solve(const SolveArgs<double> &, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

@@ -46,6 +46,11 @@ int workgroup_rows_per_thread(int n)
     return n <= kResidentMaxOrder || n > kWorkgroupMaxOrder ? 0 : n <= 80 ? 40 : n <= 96 ? 48 : n <= 112 ? 56 : 64;
 }
 
+int workgroup_solve_rows_per_thread(int n)
+{
+    return n < 1 || n >= kWorkgroupMaxOrder ? 0 : n <= 80 ? 40 : workgroup_rows_per_thread(n);
+}
+
 // `X(i)` for i = 0 ... 63 as the cases of a switch; slots >= RPT are discarded at compile time
 #define MI32_WG_CASES8(X, b) X(b + 0) X(b + 1) X(b + 2) X(b + 3) X(b + 4) X(b + 5) X(b + 6) X(b + 7)
 #define MI32_WG_CASES64(X)                                                                                      \
@@ -84,11 +89,16 @@ __device__ __forceinline__ void wg_put(T (&a)[RPT], int slot, T v)
 // between the instances, see the variable-size kernel).  DET: every thread also multiplies each step's pivot into the
 // determinant (det_accumulate of mi32_internal.h; the pivot and the swap predicate are workgroup-uniform, so the
 // accumulator lives in scalar registers), thread 0 stores it to *det_mant / *det_exp, and a null `out` skips the
-// inverse's stores.
-template <typename T, int RPT, bool PIVOT, bool ROW_POINTER, bool DET>
+// inverse's stores.  SOLVE (A X = B, never with DET): the columns n ... n + cols - 1 hold the member's B columns `rhs`
+// + 0 ... cols - 1 (rows ldb elements apart) and take the steps as any column >= n would -- they are never column r, so
+// that is the row exchange, prn = b[p] / piv, the update by the published multipliers and b[r] = prn; slot s of such a
+// column is row label[s] of X, stored to `out` + its column (rows ldo apart), and the columns < n store nothing.
+template <typename T, int RPT, bool PIVOT, bool ROW_POINTER, bool DET, bool SOLVE = false>
 __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int n, const int lda, const int ldo,
-                                                 int *status_word, double *det_mant = nullptr, int *det_exp = nullptr)
+                                                 int *status_word, double *det_mant = nullptr, int *det_exp = nullptr,
+                                                 const T *rhs = nullptr, const int ldb = 0, const int cols = 0)
 {
+    static_assert(!(SOLVE && (DET || ROW_POINTER)), "the solve body loads by index and has no determinant");
     static_assert(RPT % 8 == 0 && RPT >= 40 && RPT <= 64, "rows per thread");
     constexpr int P = 2 * RPT;  // padded rows
     __shared__ __attribute__((aligned(32))) T s_col[2][kWorkgroupColumns];   // published column r, by step parity
@@ -100,7 +110,14 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
     const int h = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 7);  // wave-uniform
     const int lane = threadIdx.x & 63;
     const int slot0 = h * RPT;
-    const bool mine = j < n;
+    const bool mine = j < (SOLVE ? n + cols : n);
+    // SOLVE: this thread's column of [A | B], its first element and row stride
+    const T *colp0 = in;
+    int ldc = lda;
+    if constexpr (SOLVE) {
+        colp0 = j < n ? in + j : mine ? rhs + (j - n) : in;  // (a column past the width reads A's first element)
+        ldc = j < n ? lda : ldb;
+    }
 
     T a[RPT];
     const T *rowp = in + ((size_t)slot0 * (size_t)lda + (size_t)j);  // this thread's entry of its slab's first row
@@ -109,7 +126,9 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
     for (int i = 0; i < RPT; ++i) {
         const bool live = mine && slot0 + i < n;
         T v;  // loaded unconditionally (a dead slot reads the member's first element): the loads stay in flight together
-        if constexpr (ROW_POINTER) {
+        if constexpr (SOLVE) {
+            v = colp0[live ? (size_t)(slot0 + i) * ldc : 0];
+        } else if constexpr (ROW_POINTER) {
             v = *(live ? rowp : in);
             rowp += lda;
         } else {
@@ -180,13 +199,30 @@ __device__ __forceinline__ void workgroup_member(const T *in, T *out, const int 
         if (threadIdx.x < 64) {
             s_label[lane] = lab0;
             s_label[lane + 64] = lab1;
-            s_slot_of[lab0] = lane;
-            s_slot_of[lab1] = lane + 64;
+            if constexpr (!SOLVE) {
+                s_slot_of[lab0] = lane;
+                s_slot_of[lab1] = lane + 64;
+            }
         }
         __syncthreads();
-        oc = s_slot_of[j];
+        if constexpr (!SOLVE) oc = s_slot_of[j];
     }
     if (!mine) return;
+    if constexpr (SOLVE) {
+        // X has no column permutation: the B column keeps its place, only the rows follow the labels
+        if (j >= n) {
+#pragma unroll
+            for (int i = 0; i < RPT; ++i) {
+                if (slot0 + i < n) {
+                    const int row = PIVOT ? s_label[slot0 + i] : slot0 + i;
+                    // (< n by construction, like the inverse's rows below)
+                    if (row < n) out[(size_t)row * ldo + (j - n)] = a[i];
+                }
+            }
+        }
+        if (bad) *status_word = MI32_SINGULAR;
+        return;
+    }
     if constexpr (DET) {
         if (threadIdx.x == 0) {
             *det_mant = det.m;
@@ -227,6 +263,17 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_kernel(con
     const size_t mat = (size_t)blockIdx.x * (size_t)n * (size_t)n;
     workgroup_member<T, RPT, PIVOT, false, true>(in + mat, out ? out + mat : nullptr, n, n, n, status + blockIdx.x,
                                                  det_mant + blockIdx.x, det_exp + blockIdx.x);
+}
+
+// A X = B: workgroup m of the launch takes member m and the columns col0 ... col0 + cols - 1 of its B.  B and X carry
+// no __restrict__: X may be B (every element is in registers before the first store).
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_solve_kernel(const SolveArgs<T> s)
+{
+    const size_t m = blockIdx.x;
+    const size_t at = m * (size_t)s.n * (size_t)s.nrhs + (size_t)s.col0;
+    workgroup_member<T, RPT, PIVOT, false, false, true>(s.a + m * (size_t)s.n * (size_t)s.n, s.x + at, s.n, s.n, s.nrhs,
+                                                        s.status + m, nullptr, nullptr, s.b + at, s.nrhs, s.cols);
 }
 
 // The variable-size kernels: workgroup g of the launch takes member members[first + g] of the plan's sorted list; its
@@ -333,5 +380,24 @@ hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, const 
 }
 template hipError_t workgroup_vinvert(int, const VbatchArgs<float> &, DetOut, int, int, hipStream_t, Profiler *, bool);
 template hipError_t workgroup_vinvert(int, const VbatchArgs<double> &, DetOut, int, int, hipStream_t, Profiler *, bool);
+
+template <typename T>
+hipError_t workgroup_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting)
+{
+    const int rows = workgroup_solve_rows_per_thread(s.n);
+    if (rows == 0 || s.batch <= 0 || s.cols < 1 || s.n + s.cols > kWorkgroupColumns || s.col0 < 0 ||
+        s.col0 + s.cols > s.nrhs || !s.a || !s.b || !s.x || !s.status)
+        return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    workgroup_instance(rows, pivoting, [&](auto rpt, auto pivot) {
+        constexpr int RPT = decltype(rpt)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        hipLaunchKernelGGL((gj_workgroup_solve_kernel<T, RPT, PIVOT>), dim3((unsigned)s.batch), dim3(kWorkgroupThreads), 0,
+                           stream, s);
+    });
+    return hipGetLastError();
+}
+template hipError_t workgroup_solve(const SolveArgs<float> &, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_solve(const SolveArgs<double> &, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

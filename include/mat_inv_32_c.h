@@ -212,6 +212,32 @@ int mi32_inv_det_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const dou
                                      double *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
                                      int *d_det_exp);
 
+/* ---- A X = B without the inverse (orders 1 ... 127) ------------------------------------------------------------------ */
+/* The one-launch batch paths solve A X = B for every member by Gauss-Jordan on [A | B]: in those kernels a lane or
+ * column past the order is idle, and a column of B placed there takes exactly the steps an augmented column takes --
+ * the row exchange with the pivot row, prn = b[p] / piv, b[i] = fma(-f, prn, b[i]) for every other row (skipped when the
+ * multiplier f == 0), b[r] = prn -- with the pivot row p, pivot piv and multipliers f of the elimination of A, whose
+ * arithmetic is that of mi32_inv_device.  X is B's final content; no inverse is formed or stored.  With B = I, X is
+ * mi32_inv_device's inverse bit for bit; its accuracy is that of inverse-times-B, not better.
+ *
+ * d_a: (batch, n, n) contiguous; d_b, d_x: (batch, n, nrhs) contiguous, row-major; d_x == d_b is allowed (a member's
+ * loads all precede its stores), d_x must not be d_a.  d_status: device int[batch] or NULL as for mi32_inv_device;
+ * MI32_SINGULAR for a zero, NaN or infinite pivot or a non-finite entry of A or of B -- the elimination goes on
+ * regardless and that member's X is unspecified.  1 <= n <= 127: order 128 has no spare column, and it, larger orders,
+ * a null pointer, batch <= 0 or nrhs <= 0 are MI32_BAD_SHAPE.
+ *
+ * One launch holds at most 64 - n columns beside an order n <= 32 (the member stays in one 64-lane group) and
+ * 128 - n beside a larger one; more columns are cut into such chunks, full ones first, one launch each, and EVERY launch
+ * repeats the elimination of A.  A chunk whose width n + columns is at most 64 runs on the register-resident kernels
+ * (8 / 16 / 32 / 64 lanes by the width), a wider one on the workgroup-resident ones (40 rows per thread up to order
+ * 80, then 48 / 56 / 64): an order 33 ... 64 with n + nrhs > 64 moves from a 64-lane group to a 256-thread workgroup.
+ * Always these kernels, whatever mi32_set_algo says; the context's pivoting setting, stream and mutex as for
+ * mi32_inv_device; asynchronous; the launches are recorded under profiling class 2. */
+int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const float *d_b, int nrhs, float *d_x,
+                      int *d_status);
+int mi32_solve_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, const double *d_b, int nrhs, double *d_x,
+                          int *d_status);
+
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all
@@ -275,6 +301,14 @@ int mi32_resolve_resident(mi32_handle_t h, int n, int elem_bytes, int *lanes_per
  * anything else, or n <= 0, is MI32_BAD_SHAPE.  The output pointers are optional. */
 int mi32_resolve_workgroup(mi32_handle_t h, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
                            int *max_order);
+/* How mi32_solve_device* would run this shape, answered without a device (h may be NULL): *chunk_cols = the most columns
+ * one launch takes (64 - n for n <= 32, 128 - n for 33 <= n <= 127), *launches = ceil(nrhs / *chunk_cols), and the
+ * first chunk's kernel: *lanes = lanes per member (8 / 16 / 32 / 64) of the register-resident instance, 0 when the chunk
+ * takes the workgroup-resident one; *rows_per_thread = that one's register rows per thread (40 / 48 / 56 / 64), 0 when
+ * the chunk takes the register-resident instance.  n outside 1 ... 127, nrhs <= 0, elem_bytes other than 4 or 8, or a
+ * NULL output is MI32_BAD_SHAPE. */
+int mi32_resolve_solve(mi32_handle_t h, int n, int nrhs, int elem_bytes, int *chunk_cols, int *launches, int *lanes,
+                       int *rows_per_thread);
 /* name of the dominant device kernel of that algorithm (for rocprof filtering) */
 const char *mi32_dominant_kernel(int algo);
 /* thread-local description of the last MI32_RUNTIME_ERROR */

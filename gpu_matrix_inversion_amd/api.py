@@ -239,6 +239,10 @@ class RaggedPlan:
         # element offset of every member in the packed layout: member b at sum_{i<b} n_i^2
         self._offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(sq)[:-1]))).to(self.device)
         self._ptrs = {}  # (base address, dtype) -> int64 device tensor of member addresses in the packed layout
+        # the packed right-hand side of solve_ragged: member b's rows start at sum_{i<b} n_i
+        rows = self.orders.astype(np.int64)
+        self.total_rows = int(rows.sum())
+        self._row_offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(rows)[:-1]))).to(self.device)
 
     def packed_pointers(self, flat):
         """int64 device tensor of the member addresses inside the packed tensor ``flat`` (cached per base and dtype)."""
@@ -546,12 +550,112 @@ class Inverter:
                               status=status, det=det)
         return (out, r[0], r[1]) if det else (out, r)
 
-    def inv_diag_blocks(self, m, block_orders, out=None, *, det=False):
-        """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
-        orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
-        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``; with
-        ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block (the determinant of the block-diagonal
-        matrix is their product: add the logarithms of ``slogdet_from_frexp``)."""
+    def resolved_solve_ragged(self, orders, nrhs: int):
+        """The launches of one ``solve_pointers`` / ``solve_ragged`` / ``solve_diag_blocks`` call on members of these
+        orders (each 1 ... 127) with ``nrhs`` columns, host only: a list of ``(first, count, col0, cols, lanes, rows)``
+        -- a range of the member list sorted by order, the columns of B, and the kernel instance as ``resolved_solve``
+        names it (lanes per member, or 0 and the workgroup-resident kernel's rows per thread).  Every member runs as
+        ``solve`` would run a uniform batch of its order; members whose chunks agree share their launches, so
+        ``nrhs = 1`` takes at most eight.  An order outside 1 ... 127 or ``nrhs < 1`` raises ValueError."""
+        o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        count = ctypes.c_int()
+        _lib.check(self._lib.mi32_vbatch_solve_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs), None, 0,
+                                                        ctypes.byref(count)), "mi32_vbatch_solve_launches")
+        out = np.empty((count.value, 6), np.int32)
+        _lib.check(self._lib.mi32_vbatch_solve_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs),
+                                                        out.ctypes.data_as(ip), count.value, ctypes.byref(count)),
+                   "mi32_vbatch_solve_launches")
+        return [tuple(int(v) for v in row) for row in out]
+
+    def solve_pointers(self, plan, a_ptrs, b_ptrs, x_ptrs, dtype, nrhs, lda=None, ldb=None, ldx=None, status=None):
+        """A X = B for every member of the plan in one call, the low-level form: ``a_ptrs`` / ``b_ptrs`` / ``x_ptrs``
+        are int64 device tensors of ``plan.batch`` member addresses (row-major members of ``dtype`` float32 / float64:
+        A is n x n, B and X are n x ``nrhs``), ``lda`` / ``ldb`` / ``ldx`` int32 device tensors of leading dimensions
+        in elements (None: the member's order for ``lda``, ``nrhs`` for the other two).  A member may be solved in
+        place (the same address and leading dimension for B and X); X over A, or members that overlap otherwise, are
+        undefined.  ``nrhs < 1`` or a plan that holds an order-128 member raises ValueError.  Every member is
+        ``solve``'s result for its order bit for bit; ``resolved_solve_ragged`` lists the launches.  Asynchronous on
+        torch's current stream.  Returns the status tensor (int32[batch], the caller's member order)."""
+        torch = self._torch
+        self._check_plan(plan)
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype: torch.float32 or torch.float64")
+        if int(nrhs) != nrhs or nrhs < 1:
+            raise ValueError("nrhs: at least one column")
+        if int(plan.orders.max()) > 127:
+            raise ValueError("solve takes orders up to 127: the plan holds an order-128 member")
+        for t, what in ((a_ptrs, "a_ptrs"), (b_ptrs, "b_ptrs"), (x_ptrs, "x_ptrs")):
+            self._check_tensor(t, torch.int64, what, plan.batch)
+        for ld, what in ((lda, "lda"), (ldb, "ldb"), (ldx, "ldx")):
+            if ld is not None:
+                self._check_tensor(ld, torch.int32, what, plan.batch)
+        if status is None:
+            status = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
+        else:
+            self._check_tensor(status, torch.int32, "status", plan.batch)
+        self._bind_stream()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        fn = self._lib.mi32_solve_device_vbatched if dtype == torch.float32 else self._lib.mi32_solve_device_vbatched_f64
+        _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(b_ptrs), ptr(ldb), int(nrhs), ptr(x_ptrs), ptr(ldx),
+                      ptr(status)), "mi32_solve_device_vbatched")
+        return status
+
+    def _packed_rhs(self, plan, a_dtype, a_device, b, out, what):
+        """The right-hand side handling ``solve_ragged`` and ``solve_diag_blocks`` share: ``b`` is (plan.total_rows,)
+        or (plan.total_rows, K), member i's rows starting at ``sum_{k<i} n_k``.  Returns ``(rhs, out, nrhs)`` with
+        ``rhs`` contiguous and ``out`` a contiguous tensor of b's shape (``b`` itself for the in-place form)."""
+        torch = self._torch
+        if b.dtype != a_dtype or b.device != a_device:
+            raise ValueError(f"{what} is {b.dtype} on {b.device}, expected {a_dtype} on {a_device}")
+        if b.dim() not in (1, 2) or b.shape[0] != plan.total_rows or b.numel() == 0:
+            raise ValueError(f"{what}: expected ({plan.total_rows},) or ({plan.total_rows}, K)")
+        nrhs = 1 if b.dim() == 1 else int(b.shape[1])
+        if out is None:
+            return b.contiguous(), torch.empty(b.shape, dtype=b.dtype, device=b.device), nrhs
+        if out.shape != b.shape or out.dtype != b.dtype or out.device != b.device or not out.is_contiguous():
+            raise ValueError(f"out: {what} itself or a contiguous tensor of its shape, dtype and device")
+        return (out if out is b else b.contiguous()), out, nrhs
+
+    def solve_ragged(self, plan, a_flat, b, out=None, status=None):
+        """A X = B for members of mixed orders 1 ... 127 in one call.  ``a_flat`` is the packed layout of
+        ``inv_ragged``; ``b`` is a contiguous ``(plan.total_rows,)`` or ``(plan.total_rows, K)`` tensor of a_flat's
+        dtype and device in which member i's rows start at ``sum_{k<i} n_k`` (a vector keeps its shape).  ``out`` may
+        be ``b`` itself (in place) or a contiguous tensor of its shape; it must not be ``a_flat``.  Returns
+        ``(x, status)``; x of a member whose status is not 0 is unspecified.  A plan that holds an order-128 member
+        raises ValueError."""
+        torch = self._torch
+        self._check_plan(plan)
+        if a_flat.dtype not in (torch.float32, torch.float64):
+            raise ValueError("expected a float32 or float64 tensor")
+        self._check_tensor(a_flat, a_flat.dtype, "a_flat")
+        if a_flat.numel() != plan.flat_size:
+            raise ValueError(f"a_flat holds {a_flat.numel()} elements, the plan's members {plan.flat_size}")
+        if out is a_flat or (out is not None and out.data_ptr() == a_flat.data_ptr()):
+            raise ValueError("out must not alias a_flat")
+        rhs, out, nrhs = self._packed_rhs(plan, a_flat.dtype, a_flat.device, b, out, "b")
+        step = nrhs * rhs.element_size()
+        st = self.solve_pointers(plan, plan.packed_pointers(a_flat), plan._row_offsets * step + rhs.data_ptr(),
+                                 plan._row_offsets * step + out.data_ptr(), a_flat.dtype, nrhs, status=status)
+        return out, st
+
+    def solve_diag_blocks(self, m, block_orders, r, out=None):
+        """``z = blockdiag(m)^-1 r``, the application of a block-Jacobi preconditioner, in one call: the consecutive
+        diagonal blocks of the square device matrix ``m`` have the orders ``block_orders`` (each 1 ... 127, summing to
+        ``m.shape[0]``), ``r`` is ``(N,)`` or ``(N, K)`` of m's dtype and device.  Only the block entries of ``m`` are
+        read and no inverse is formed.  ``out`` may be ``r`` itself.  Returns ``(z, status)`` with one status word per
+        block.  The plan of the last block structure is kept (shared with ``inv_diag_blocks``)."""
+        plan, elem_off, lds = self._diag_blocks_plan(m, block_orders)
+        rhs, out, nrhs = self._packed_rhs(plan, m.dtype, m.device, r, out, "r")
+        step = nrhs * rhs.element_size()
+        st = self.solve_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
+                                 plan._row_offsets * step + rhs.data_ptr(), plan._row_offsets * step + out.data_ptr(),
+                                 m.dtype, nrhs, lda=lds)
+        return out, st
+
+    def _diag_blocks_plan(self, m, block_orders):
+        """``(plan, element offsets of the blocks in m, leading dimensions)`` for the diagonal blocks of ``m``, from
+        the one-entry cache ``_diag_plan`` where the block structure is that of the last call."""
         torch = self._torch
         if m.dtype not in (torch.float32, torch.float64):
             raise ValueError("expected a float32 or float64 matrix")
@@ -562,10 +666,6 @@ class Inverter:
         orders = np.asarray(block_orders)
         if orders.ndim != 1 or orders.size == 0 or int(orders.sum()) != m.shape[0]:
             raise ValueError("block_orders must sum to the matrix order")
-        if out is None:
-            out = torch.zeros_like(m)
-        elif out.shape != m.shape or out.dtype != m.dtype or out.device != m.device or not out.is_contiguous():
-            raise ValueError("out: a contiguous matrix of m's shape, dtype and device")
         ld = m.shape[0]
         key = orders.astype(np.int32).tobytes()
         if self._diag_plan is None or self._diag_plan[0] != key:
@@ -576,7 +676,20 @@ class Inverter:
             # block b starts at row off_b, column off_b: element off_b * (ld + 1)
             self._diag_plan = (key, plan, torch.from_numpy(off * (ld + 1)).to(self.device),
                                torch.full((orders.size,), ld, dtype=torch.int32, device=self.device))
-        _, plan, elem_off, lds = self._diag_plan
+        return self._diag_plan[1:]
+
+    def inv_diag_blocks(self, m, block_orders, out=None, *, det=False):
+        """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
+        orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
+        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``; with
+        ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block (the determinant of the block-diagonal
+        matrix is their product: add the logarithms of ``slogdet_from_frexp``)."""
+        torch = self._torch
+        plan, elem_off, lds = self._diag_blocks_plan(m, block_orders)
+        if out is None:
+            out = torch.zeros_like(m)
+        elif out.shape != m.shape or out.dtype != m.dtype or out.device != m.device or not out.is_contiguous():
+            raise ValueError("out: a contiguous matrix of m's shape, dtype and device")
         r = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
                               elem_off * out.element_size() + out.data_ptr(), m.dtype, lda=lds, ldout=lds, det=det)
         return (out, r[0], r[1]) if det else (out, r)

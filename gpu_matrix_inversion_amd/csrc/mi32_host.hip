@@ -253,6 +253,9 @@ struct mi32_vbatch {
     int device = 0;
     int batch = 0;
     int class_begin[kVbatchClasses + 1] = {};  // class k takes d_members[class_begin[k] .. class_begin[k + 1])
+    // the members of order n are d_members[order_begin[n] .. order_begin[n + 1]), n = 1 ... 128 (host only: the solve's
+    // launches follow the width n + columns, not the order's class)
+    int order_begin[kWorkgroupMaxOrder + 2] = {};
     int *d_orders = nullptr;   // int[batch], the caller's member order
     int *d_members = nullptr;  // int[batch], member indices in ascending order of their orders (stable)
 };
@@ -459,7 +462,7 @@ static int solve_device(mi32_context *h, const T *d_a, int n, int batch, const T
 
 extern "C" {
 
-int mi32_version(void) { return 141; }
+int mi32_version(void) { return 142; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)
@@ -798,24 +801,36 @@ static int vbatch_class(int n)
 static const int kVbatchLanes[4] = {8, 16, 32, 64};
 static const int kVbatchRows[4] = {40, 48, 56, 64};
 
-int mi32_vbatch_bin(const int *orders, int batch, int *perm, int *class_begin)
+// The counting sort behind mi32_vbatch_bin, O(batch) and stable; order_begin (may be null; int[kWorkgroupMaxOrder + 2]):
+// the members of order n are perm[order_begin[n] .. order_begin[n + 1]).  perm and class_begin may be null too.
+static int vbatch_sort(const int *orders, int batch, int *perm, int *class_begin, int *order_begin)
 {
-    if (!orders || !perm || !class_begin || batch <= 0) return MI32_BAD_SHAPE;
-    // a counting sort: O(batch), stable
+    if (!orders || batch <= 0) return MI32_BAD_SHAPE;
     int start[kWorkgroupMaxOrder + 2] = {};
     for (int b = 0; b < batch; ++b) {
         const int n = orders[b];
         if (n < 1 || n > kWorkgroupMaxOrder) return MI32_BAD_SHAPE;
         ++start[n + 1];
     }
-    for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = 0;
+    int cls[kVbatchClasses + 1] = {};
     for (int n = 1; n <= kWorkgroupMaxOrder; ++n) {
-        class_begin[vbatch_class(n) + 1] += start[n + 1];  // the members of order n (every order 1 ... 128 has a class)
-        start[n + 1] += start[n];                          // start[n]: where the members of order n begin
+        cls[vbatch_class(n) + 1] += start[n + 1];  // the members of order n (every order 1 ... 128 has a class)
+        start[n + 1] += start[n];                  // start[n]: where the members of order n begin
     }
-    for (int k = 0; k < kVbatchClasses; ++k) class_begin[k + 1] += class_begin[k];
-    for (int b = 0; b < batch; ++b) perm[start[orders[b]]++] = b;
+    for (int k = 0; k < kVbatchClasses; ++k) cls[k + 1] += cls[k];
+    if (class_begin)
+        for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = cls[k];
+    if (order_begin)
+        for (int n = 0; n <= kWorkgroupMaxOrder + 1; ++n) order_begin[n] = start[n];
+    if (perm)
+        for (int b = 0; b < batch; ++b) perm[start[orders[b]]++] = b;
     return MI32_OK;
+}
+
+int mi32_vbatch_bin(const int *orders, int batch, int *perm, int *class_begin)
+{
+    if (!perm || !class_begin) return MI32_BAD_SHAPE;
+    return vbatch_sort(orders, batch, perm, class_begin, nullptr);
 }
 
 int mi32_vbatch_create(mi32_handle_t h, const int *orders, int batch, mi32_vbatch_t *out)
@@ -826,7 +841,7 @@ int mi32_vbatch_create(mi32_handle_t h, const int *orders, int batch, mi32_vbatc
     std::vector<int> perm((size_t)batch);
     mi32_vbatch *p = new (std::nothrow) mi32_vbatch();
     if (!p) return MI32_RUNTIME_ERROR;
-    const int rc = mi32_vbatch_bin(orders, batch, perm.data(), p->class_begin);
+    const int rc = vbatch_sort(orders, batch, perm.data(), p->class_begin, p->order_begin);
     if (rc != MI32_OK) {
         delete p;
         return rc;
@@ -909,7 +924,125 @@ static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *c
     return MI32_OK;
 }
 
+// ---- A X = B for a variable-size batch ------------------------------------------------------------------------------
+// Every member is treated as one_launch_solve treats a uniform batch of its order: the nrhs columns in chunks of
+// solve_chunk_cols(n), full ones first, a chunk of width n + cols <= kResidentMaxOrder on the register-resident kernel
+// (resident_lanes of the width), a wider one on the workgroup-resident kernel.  How an order's chunks run:
+struct VsolveChunks {
+    int cols;            // columns of a full chunk (of the only chunk, when nrhs fits one)
+    long long chunks;    // ceil(nrhs / cap)
+    int first_instance;  // the kernel of the full chunks, last_instance: of the remainder (the same when there is none)
+    int last_instance;   // an instance: lanes per member (8 ... 64), or -(rows per thread) for the workgroup kernel
+    bool operator==(const VsolveChunks &o) const
+    {
+        return cols == o.cols && chunks == o.chunks && first_instance == o.first_instance && last_instance == o.last_instance;
+    }
+};
+static int vsolve_instance(int n, int cols)
+{
+    return n + cols <= kResidentMaxOrder ? resident_lanes(n + cols) : -workgroup_solve_rows_per_thread(n);
+}
+static VsolveChunks vsolve_chunks(int n, int nrhs)
+{
+    const int cap = solve_chunk_cols(n);
+    VsolveChunks c;
+    c.cols = nrhs < cap ? nrhs : cap;
+    c.chunks = ((long long)nrhs + cap - 1) / cap;
+    c.first_instance = vsolve_instance(n, c.cols);
+    c.last_instance = vsolve_instance(n, (int)(nrhs - (c.chunks - 1) * cap));
+    return c;
+}
+// The launches of a call, in the order they are enqueued: f(first, count, col0, cols, lanes, rows_per_thread) -> bool
+// (false ends the walk) for every chunk of every maximal run of consecutive sorted members whose chunk sequences agree
+// -- two orders' sequences agree when c.cols, the number of chunks and the two instances do: col0 and cols of every
+// chunk follow from these.  order_begin as in mi32_vbatch (no member of order 128: the caller's business).  The one
+// place the rule lives: mi32_vbatch_solve_launches reports this list and mi32_solve_device_vbatched* walks it.
+template <typename F>
+static void vsolve_walk(const int *order_begin, int nrhs, F f)
+{
+    int n = 1;
+    while (n < kWorkgroupMaxOrder) {
+        if (order_begin[n + 1] == order_begin[n]) {  // no member of this order
+            ++n;
+            continue;
+        }
+        const VsolveChunks c = vsolve_chunks(n, nrhs);
+        int end = n + 1;  // the run takes the orders n ... end - 1
+        while (end < kWorkgroupMaxOrder && (order_begin[end + 1] == order_begin[end] || vsolve_chunks(end, nrhs) == c)) ++end;
+        // (orders without members at the run's end belong to no launch: the range below does not see them)
+        const int first = order_begin[n], count = order_begin[end] - first;
+        for (long long k = 0; k < c.chunks; ++k) {
+            const long long col0 = k * c.cols;
+            const int cols = (int)(nrhs - col0 < c.cols ? nrhs - col0 : c.cols);
+            const int inst = k + 1 < c.chunks ? c.first_instance : c.last_instance;
+            if (!f(first, count, (int)col0, cols, inst > 0 ? inst : 0, inst > 0 ? 0 : -inst)) return;
+        }
+        n = end;
+    }
+}
+
+// the arguments are checked before the context is touched
+template <typename T>
+static int solve_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
+                                 const T *const *d_b, const int *d_ldb, int nrhs, T *const *d_x, const int *d_ldx,
+                                 int *d_status)
+{
+    if (!h || !p || !d_a || !d_b || !d_x || nrhs <= 0) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    // order 128 has no spare column
+    if (p->order_begin[kWorkgroupMaxOrder + 1] != p->order_begin[kWorkgroupMaxOrder]) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const int rc = status_buffer(h, d_status, p->batch, &d_status);
+    if (rc != MI32_OK) return rc;
+    // zeroed once: a launch only ever raises a member's flag
+    hipError_t e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)p->batch, h->stream);  // MI32_OK
+    if (e == hipSuccess)
+        vsolve_walk(p->order_begin, nrhs, [&](int first, int count, int col0, int cols, int lanes, int rows) {
+            const VsolveArgs<T> v{p->d_orders, p->d_members, d_a, d_b, d_x, d_lda, d_ldb, d_ldx, d_status, nrhs, col0, cols};
+            e = lanes ? resident_vsolve(lanes, v, first, count, h->stream, h->prof, h->pivoting)
+                      : workgroup_vsolve(rows, v, first, count, h->stream, h->prof, h->pivoting);
+            return e == hipSuccess;
+        });
+    if (e != hipSuccess) return fail(e, "kernel launch");
+    return MI32_OK;
+}
+
 extern "C" {
+
+int mi32_vbatch_solve_launches(const int *orders, int batch, int nrhs, int *launches, int capacity, int *count)
+{
+    if (!orders || !count || batch <= 0 || nrhs <= 0 || capacity < 0 || (capacity > 0 && !launches)) return MI32_BAD_SHAPE;
+    int order_begin[kWorkgroupMaxOrder + 2];
+    if (vbatch_sort(orders, batch, nullptr, nullptr, order_begin) != MI32_OK) return MI32_BAD_SHAPE;
+    if (order_begin[kWorkgroupMaxOrder + 1] != order_begin[kWorkgroupMaxOrder]) return MI32_BAD_SHAPE;  // an order 128
+    long long total = 0;
+    vsolve_walk(order_begin, nrhs, [&](int first, int cnt, int col0, int cols, int lanes, int rows) {
+        if (total < capacity) {
+            int *l = launches + 6 * total;
+            l[0] = first, l[1] = cnt, l[2] = col0, l[3] = cols, l[4] = lanes, l[5] = rows;
+        }
+        ++total;
+        return true;
+    });
+    if (total > 0x7fffffffLL) return MI32_BAD_SHAPE;
+    *count = (int)total;
+    return MI32_OK;
+}
+
+int mi32_solve_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                               const float *const *d_b, const int *d_ldb, int nrhs, float *const *d_x, const int *d_ldx,
+                               int *d_status)
+{
+    return solve_device_vbatched(h, p, d_a, d_lda, d_b, d_ldb, nrhs, d_x, d_ldx, d_status);
+}
+
+int mi32_solve_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                   const double *const *d_b, const int *d_ldb, int nrhs, double *const *d_x,
+                                   const int *d_ldx, int *d_status)
+{
+    return solve_device_vbatched(h, p, d_a, d_lda, d_b, d_ldb, nrhs, d_x, d_ldx, d_status);
+}
 
 int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
                              float *const *d_inv, const int *d_ldinv, int *d_status)

@@ -284,6 +284,33 @@ hipError_t resident_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *p
 template <typename T>
 hipError_t workgroup_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting);
 
+// ---- A X = B for a variable-size batch (mi32_solve_device_vbatched*) -------------------------------------------------
+// The solve kernels' variable-size twins (gj_resident_solve_vkernel / gj_workgroup_solve_vkernel): a launch takes the
+// `count` members from `first` on of the plan's sorted list, which all run the columns col0 ... col0 + cols - 1 of their
+// B on one kernel instance (lanes per member by the width n + cols, or rows per thread by the order), and looks up the
+// member's order, pointers and leading dimensions by the member index.  Everything here is device memory.
+template <typename T>
+struct VsolveArgs {
+    const int *orders;   // int[batch], in the caller's member order
+    const int *members;  // int[batch], the member indices in ascending order of their orders (stable)
+    const T *const *a;   // member pointers, row-major: A is n x n, rows lda[b] elements apart
+    const T *const *b;   // B is n x nrhs, rows ldb[b] elements apart
+    T *const *x;         // X is n x nrhs, rows ldx[b] elements apart; x[b] may be b[b] with ldx[b] == ldb[b]
+    const int *lda;      // null: orders[b]
+    const int *ldb;      // null: nrhs
+    const int *ldx;      // null: nrhs
+    int *status;         // int[batch], zeroed by the host before the first launch of the call
+    int nrhs;
+    int col0, cols;      // this launch's columns of B and X
+};
+// hipErrorInvalidValue for a class without an instance, an empty or negative range, no columns, or a null pointer
+template <typename T>
+hipError_t resident_vsolve(int lanes, const VsolveArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
+                           bool pivoting);
+template <typename T>
+hipError_t workgroup_vsolve(int rows_per_thread, const VsolveArgs<T> &v, int first, int count, hipStream_t stream,
+                            Profiler *prof, bool pivoting);
+
 // streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
 // of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
 struct BlockedExec {

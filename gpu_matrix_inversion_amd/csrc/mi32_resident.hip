@@ -348,6 +348,85 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_kernel(con
     if (bad) s.status[member] = MI32_SINGULAR;
 }
 
+// A X = B for a variable-size batch: group g of the launch takes member members[first + g] of the plan's sorted list
+// and the columns col0 ... col0 + cols - 1 of its B; every member of the launch has a width n + cols of this lane class.
+// A sibling of gj_resident_solve_kernel, not a rewrite of it (sharing the step loop moved the registers of the uniform
+// instances).  The groups of a wave may differ in order, so B sits in a different lane in each, and a group sits out
+// the steps past its own order: here that guard carries the result, because lane n of a finished group holds a column
+// of B and would otherwise become a pivot column.  For L = 64 the group is the wave and the member index, the order,
+// the pointers and the leading dimensions are scalar values.  No pointer carries __restrict__: X may be B.
+template <typename T, int L, bool PIVOT>
+__global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_vkernel(const VsolveArgs<T> v, const int first,
+                                                                              const int count)
+{
+    constexpr int kGroups = kResidentThreads / L;  // members per workgroup
+    const int j = threadIdx.x & (L - 1);
+    int grp = threadIdx.x / L;
+    if constexpr (L == 64) grp = __builtin_amdgcn_readfirstlane(grp);  // the group is the wave
+    const long long g = (long long)blockIdx.x * kGroups + grp;
+    const bool valid = g < (long long)count;
+    int m = valid ? v.members[(size_t)first + (size_t)g] : 0;
+    if constexpr (L == 64) m = __builtin_amdgcn_readfirstlane(m);
+    int n = valid ? v.orders[m] : 0;
+    if constexpr (L == 64) n = __builtin_amdgcn_readfirstlane(n);
+    int nmax = n;  // the largest order in the wave
+    if constexpr (L < 64) {
+#pragma unroll
+        for (int off = L; off < 64; off <<= 1) {
+            const int o = __shfl_xor(nmax, off, 64);
+            nmax = o > nmax ? o : nmax;
+        }
+        nmax = __builtin_amdgcn_readfirstlane(nmax);
+    }
+    // a group past the end of the range, and a lane past the member's width, hold zeros and neither load nor store
+    const bool mine = valid && j < n + v.cols;
+    const bool rhs = j >= n;
+    const int col = v.col0 + (rhs ? j - n : 0);  // this lane's column of B and X
+    const T *in = nullptr;
+    int ld = 0;
+    if (mine) {
+        const int lda = v.lda ? v.lda[m] : n;
+        const int ldb = v.ldb ? v.ldb[m] : v.nrhs;
+        in = rhs ? v.b[m] + col : v.a[m] + j;
+        ld = rhs ? ldb : lda;
+    }
+    T a[L];
+    bool bad = false;  // boundary rule: a NaN / inf anywhere in A or B is an invalid member
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        if (i < n) {
+            a[i] = mine ? in[(size_t)i * ld] : T(0);
+            bad = bad || (a[i] - a[i] != T(0));
+        } else {
+            a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
+        }
+    }
+    int orig = j;
+    DetAcc det = det_start(false);
+    if constexpr (L <= 16) {
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            if (r < nmax) {  // wave-uniform: no wave walks through the steps none of its groups takes
+                if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
+            }
+        }
+    } else {
+#pragma unroll 1
+        for (int r = 0; r < nmax; ++r)
+            if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
+    }
+    if (!mine) return;
+    if (rhs) {
+        T *out = v.x[m] + col;
+        const int ldx = v.ldx ? v.ldx[m] : v.nrhs;
+#pragma unroll
+        for (int i = 0; i < L; ++i)
+            if (i < n) out[(size_t)i * ldx] = a[i];
+    }
+    // the status word was zeroed (MI32_OK) by the host before the call's first launch; every writer stores the same value
+    if (bad) v.status[m] = MI32_SINGULAR;
+}
+
 // f(lanes, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time pair picks
 // a kernel instance.  false: no instance has that many lanes per matrix.
 template <typename F>
@@ -432,5 +511,26 @@ hipError_t resident_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *p
 }
 template hipError_t resident_solve(const SolveArgs<float> &, hipStream_t, Profiler *, bool);
 template hipError_t resident_solve(const SolveArgs<double> &, hipStream_t, Profiler *, bool);
+
+template <typename T>
+hipError_t resident_vsolve(int lanes, const VsolveArgs<T> &v, int first, int count, hipStream_t stream, Profiler *prof,
+                           bool pivoting)
+{
+    if (count <= 0 || first < 0 || v.cols < 1 || v.cols >= lanes || v.col0 < 0 || v.col0 + v.cols > v.nrhs || !v.orders ||
+        !v.members || !v.a || !v.b || !v.x || !v.status)
+        return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    const bool found = resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+        constexpr int L = decltype(l)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        constexpr int kGroups = kResidentThreads / L;
+        const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
+        hipLaunchKernelGGL((gj_resident_solve_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, v, first,
+                           count);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+template hipError_t resident_vsolve(int, const VsolveArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t resident_vsolve(int, const VsolveArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

@@ -314,6 +314,33 @@ __global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_det_vkernel(co
                                                        d.v.status + s.m, d.det_mant + s.m, d.det_exp + s.m);
 }
 
+// A X = B for a variable-size batch: workgroup g of the launch takes member members[first + g] of the plan's sorted
+// list and the columns col0 ... col0 + cols - 1 of its B; the member's order and its three leading dimensions (a null
+// lda: the order, a null ldb / ldx: nrhs) are workgroup-uniform values.
+struct WorkgroupSolveSlot {
+    int m, n, lda, ldb, ldx;
+};
+template <typename T>
+__device__ __forceinline__ WorkgroupSolveSlot workgroup_slot(const VsolveArgs<T> v, const int first)
+{
+    WorkgroupSolveSlot s;
+    s.m = __builtin_amdgcn_readfirstlane(v.members[(size_t)first + blockIdx.x]);
+    s.n = __builtin_amdgcn_readfirstlane(v.orders[s.m]);
+    s.lda = v.lda ? __builtin_amdgcn_readfirstlane(v.lda[s.m]) : s.n;
+    s.ldb = v.ldb ? __builtin_amdgcn_readfirstlane(v.ldb[s.m]) : v.nrhs;
+    s.ldx = v.ldx ? __builtin_amdgcn_readfirstlane(v.ldx[s.m]) : v.nrhs;
+    return s;
+}
+
+// B and X carry no __restrict__: X may be B (every element is in registers before the first store)
+template <typename T, int RPT, bool PIVOT>
+__global__ __launch_bounds__(kWorkgroupThreads) void gj_workgroup_solve_vkernel(const VsolveArgs<T> v, const int first)
+{
+    const WorkgroupSolveSlot s = workgroup_slot(v, first);
+    workgroup_member<T, RPT, PIVOT, false, false, true>(v.a[s.m], v.x[s.m] + v.col0, s.n, s.lda, s.ldx, v.status + s.m,
+                                                        nullptr, nullptr, v.b[s.m] + v.col0, s.ldb, v.cols);
+}
+
 #undef MI32_WG_CASES8
 #undef MI32_WG_CASES64
 
@@ -399,5 +426,26 @@ hipError_t workgroup_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *
 }
 template hipError_t workgroup_solve(const SolveArgs<float> &, hipStream_t, Profiler *, bool);
 template hipError_t workgroup_solve(const SolveArgs<double> &, hipStream_t, Profiler *, bool);
+
+// every member of the range has an order of this rows-per-thread class and a width n + cols of at most 128 columns:
+// the caller's business, like the leading dimensions
+template <typename T>
+hipError_t workgroup_vsolve(int rows_per_thread, const VsolveArgs<T> &v, int first, int count, hipStream_t stream,
+                            Profiler *prof, bool pivoting)
+{
+    if (count <= 0 || first < 0 || v.cols < 1 || v.cols >= kWorkgroupColumns || v.col0 < 0 || v.col0 + v.cols > v.nrhs ||
+        !v.orders || !v.members || !v.a || !v.b || !v.x || !v.status)
+        return hipErrorInvalidValue;
+    ProfScope ps(prof, KC_PANEL, stream);
+    const bool found = workgroup_instance(rows_per_thread, pivoting, [&](auto rpt, auto pivot) {
+        constexpr int RPT = decltype(rpt)::value;
+        constexpr bool PIVOT = decltype(pivot)::value;
+        hipLaunchKernelGGL((gj_workgroup_solve_vkernel<T, RPT, PIVOT>), dim3((unsigned)count), dim3(kWorkgroupThreads), 0,
+                           stream, v, first);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+template hipError_t workgroup_vsolve(int, const VsolveArgs<float> &, int, int, hipStream_t, Profiler *, bool);
+template hipError_t workgroup_vsolve(int, const VsolveArgs<double> &, int, int, hipStream_t, Profiler *, bool);
 
 }  // namespace mi32

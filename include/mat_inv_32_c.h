@@ -238,6 +238,39 @@ int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const
 int mi32_solve_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, const double *d_b, int nrhs, double *d_x,
                           int *d_status);
 
+/* The same for a variable-size batch (a plan of mi32_vbatch_create): one call solves A_b X_b = B_b for members of mixed
+ * orders 1 ... 127, each at its own pointers and leading dimensions, with ONE nrhs for the call -- what applying a
+ * block-Jacobi preconditioner needs, z = blockdiag(A)^-1 r.  d_a, d_b, d_x: DEVICE arrays of `batch` device pointers;
+ * member b's A is n_b x n_b with rows d_lda[b] elements apart, its B and X are n_b x nrhs with rows d_ldb[b] / d_ldx[b]
+ * elements apart.  d_lda, d_ldb, d_ldx: device int[batch]; a NULL d_lda means the member's order, a NULL d_ldb or
+ * d_ldx means nrhs.  Padding is never read and never written.  A member may be solved in place, d_x[b] == d_b[b] with
+ * d_ldx[b] == d_ldb[b] (a member's loads all precede its stores); X over A, and members that overlap in any other way,
+ * with themselves or with one another, are undefined.  d_status as for mi32_inv_device_vbatched.
+ *
+ * Every member is treated exactly as mi32_solve_device treats a uniform batch of its order with the same nrhs: the same
+ * chunks, the same kernel class per chunk, the same arithmetic, hence the same bits.  The plan's member list is sorted
+ * by order; a call enqueues one status memset and, per maximal run of consecutive sorted members whose chunk sequences
+ * agree (the same first column, column count and kernel instance for every chunk), one launch per chunk.  For nrhs = 1
+ * that is at most eight launches whatever the orders -- the runs are the orders 1 ... 7, 8 ... 15, 16 ... 31, 32 ... 63,
+ * 64 ... 80, 81 ... 96, 97 ... 112 and 113 ... 127 -- and an order with more columns than one launch holds takes launches
+ * of its own, one per chunk; every launch of a member repeats the elimination of its A.  The context's pivoting setting;
+ * the algorithm setting is ignored.  A NULL h, p, d_a, d_b or d_x, nrhs <= 0, a plan of another device or a plan that
+ * holds a member of order 128 (no spare column; the plan stays valid for mi32_inv_device_vbatched) is MI32_BAD_SHAPE,
+ * decided before the context is touched.  Asynchronous on the context's stream under profiling class 2. */
+int mi32_solve_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                               const float *const *d_b, const int *d_ldb, int nrhs, float *const *d_x, const int *d_ldx,
+                               int *d_status);
+int mi32_solve_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                   const double *const *d_b, const int *d_ldb, int nrhs, double *const *d_x,
+                                   const int *d_ldx, int *d_status);
+/* The launches of such a call, pure host code (no device; the call itself walks this very list): launches[6 * i ...]
+ * <- first, count (a range of the sorted member list), col0, cols (the columns of B), lanes per member of the
+ * register-resident instance (0: the workgroup-resident kernel), its rows per thread (0: the register-resident kernel),
+ * ordered by first, then by col0.  At most `capacity` launches are written (launches may be NULL when capacity is 0);
+ * *count is always the full number.  MI32_BAD_SHAPE: a NULL orders or count, batch <= 0, nrhs <= 0, capacity < 0, an
+ * order outside 1 ... 127. */
+int mi32_vbatch_solve_launches(const int *orders, int batch, int nrhs, int *launches, int capacity, int *count);
+
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all

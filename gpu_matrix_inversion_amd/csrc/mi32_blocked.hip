@@ -317,6 +317,13 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
     if (shared_panels) {  // no stale tag of an earlier call may match
         if ((e = hipMemsetAsync(ws.xch, 0, (size_t)kXchGranules * sizeof(unsigned long long) * batch, stream)) != hipSuccess)
             return e;
+        // A matrix that was given up is skipped by its panels from then on, so its row maps are no longer written --
+        // but where the strip(t) tiles ride in the panel launches they still run for it (ostrip_body: the 256-thread
+        // groups of a workgroup share its barriers; computed, not stored) and address its rows THROUGH submap and
+        // rowsrc.  Whatever an earlier call or another owner left in the workspace must not reach them: 0 is a valid
+        // position.  (submap, invsub and rowsrc are carved in one run, in front of orig, which the init kernel wrote.)
+        if ((e = hipMemsetAsync(ws.submap[0], 0, (size_t)((char *)ws.orig - (char *)ws.submap[0]), stream)) != hipSuccess)
+            return e;
     }
     // The strip(t) tiles follow each block sub-panel by sub-panel in the columns outside it -- unless the look-ahead
     // is on: those columns are then still being written by the previous block's second-stream update while the

@@ -1,0 +1,144 @@
+// mi32_context.h -- what the host units of libmat_inv_32.so share: the context, the settings launch planning reads,
+// the grow-only device buffer, error reporting, and the declarations that cross unit boundaries.
+//   mi32_plan.hip     launch planning, pure host code: no HIP runtime call, no context
+//   mi32_context.hip  context life cycle, setters, workspace, profiler
+//   mi32_device.hip   the device-pointer entry points
+//   mi32_hostptr.hip  the host-pointer entry points and the C++ drop-ins of the reference's headers
+#pragma once
+#include <cstdlib>
+#include <functional>
+#include <mutex>
+#include <string>
+
+#include "mi32_internal.h"
+
+struct HostCopier;  // mi32_hostptr.hip
+
+// internal to the library: none of this is an exported symbol
+#pragma GCC visibility push(hidden)
+
+// ---- errors ---------------------------------------------------------------------------------------------------------
+extern thread_local std::string g_last_error;  // mi32_last_error(); defined in mi32_context.hip
+// MI32_OK for hipSuccess; else sets g_last_error ("what: HIP's text") and returns MI32_RUNTIME_ERROR
+int hip_status(hipError_t e, const char *what);
+// return from the calling function unless the library call / the HIP call succeeded
+#define MI32_TRY(call)                    \
+    do {                                  \
+        const int rc__ = (call);          \
+        if (rc__ != MI32_OK) return rc__; \
+    } while (0)
+#define MI32_HIP(call) MI32_TRY(hip_status((call), #call))
+
+inline int env_int(const char *name, int dflt)
+{
+    const char *s = std::getenv(name);
+    return (s && *s) ? std::atoi(s) : dflt;
+}
+
+// ---- settings ---------------------------------------------------------------------------------------------------------
+// What launch planning reads of a context (the mi32_set_* calls write it); a call without a context plans with the
+// defaults.  0 / AUTO: the environment's value, then the built-in choice (see mi32_plan.hip, the one reader of each knob).
+struct Settings {
+    int algo = MI32_ALGO_AUTO;
+    bool pivoting = true;  // false: the reference's no-pivot variant (the diagonal entry is every step's pivot)
+    int panel_w = 0;
+    int block_w = 0;
+    bool lookahead = true;  // false: no second stream, neither for the look-ahead half nor for a split batch
+};
+
+// ---- grow-only device memory --------------------------------------------------------------------------------------------
+// The workspace, the context's own status words and the staging of the host-pointer calls.  ensure() returns at once
+// while the block is large enough; to grow it waits for every stream of the context, frees and allocates anew (the
+// contents are lost).
+struct DeviceBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    int ensure(mi32_context *h, size_t want);
+    void release();
+};
+
+void host_copier_destroy(HostCopier *c);
+
+struct mi32_context {
+    int device = 0;
+    Settings set;
+    HostCopier *copier = nullptr;  // made by the first host-pointer call large enough to use it
+    mi32::Profiler *prof = nullptr;  // an EventProfiler (mi32_context.hip) while profiling is on
+    hipEvent_t switch_event = nullptr;
+    hipStream_t aux_stream = nullptr;   // look-ahead half of the rank-bw updates (lowest priority)
+    hipStream_t split_stream = nullptr; // second half of a split batch (same priority as the main stream)
+    hipEvent_t la_events[8] = {};
+    int cu_count = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    DeviceBuffer ws;
+    // staging for the host-pointer entry points
+    DeviceBuffer d_in, d_out, d_status;
+    // status words of device-resident calls that pass no status buffer: the kernels always have one to flag
+    // a bad pivot or a lost panel partner in (a given-up matrix is then skipped and comes out as NaN)
+    DeviceBuffer d_istatus;
+    std::mutex mu;
+};
+inline Settings settings_of(const mi32_context *h) { return h ? h->set : Settings(); }
+
+int visible_devices(int *count);  // MI32_RUNTIME_ERROR when there is none
+int sync_all_streams(mi32_context *h);
+// the status buffer a device-resident call runs with: the caller's, or the context's own
+int status_buffer(mi32_context *h, int *d_status, int batch, int **out);
+// the same, zeroed on the stream (MI32_OK): for the kernels that only ever raise a member's flag
+int zeroed_status_buffer(mi32_context *h, int *d_status, int batch, int **out);
+
+// ---- launch planning (mi32_plan.hip) --------------------------------------------------------------------------------------
+int resolve_algo(const Settings &s, int n, size_t elem_bytes);
+mi32::BlockedPlan plan_blocked(const Settings &s, int n, int batch);
+int block_w64(const Settings &s);
+size_t ws_bytes_for(const Settings &s, int n, int batch, int algo);  // fp32
+void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive);
+bool split_batch(const Settings &s, int algo, int n, int batch);  // where the context has a second stream for it
+
+// An instance of the one-launch kernels: register-resident with `lanes` per member (8 ... 64), or workgroup-resident
+// with `rows_per_thread` (40 ... 64); the other field is 0.
+struct KernelInstance {
+    int lanes, rows_per_thread;
+    bool operator==(const KernelInstance &o) const { return lanes == o.lanes && rows_per_thread == o.rows_per_thread; }
+};
+// The kernel classes of a variable-size batch, in launch order: class k takes the orders whose resident_lanes /
+// workgroup_rows_per_thread are kVbatchClass[k]'s.
+static constexpr int kVbatchClasses = 8;
+extern const KernelInstance kVbatchClass[kVbatchClasses];
+
+// A variable-size batch plan (mi32_vbatch_create): immutable after creation.  The orders and the sorted member list
+// are the only device memory it owns, 8 bytes per member.
+struct mi32_vbatch {
+    int device = 0;
+    int batch = 0;
+    int class_begin[kVbatchClasses + 1] = {};  // class k takes d_members[class_begin[k] .. class_begin[k + 1])
+    // the members of order n are d_members[order_begin[n] .. order_begin[n + 1]), n = 1 ... 128 (host only: the solve's
+    // launches follow the width n + columns, not the order's class)
+    int order_begin[mi32::kWorkgroupMaxOrder + 2] = {};
+    int *d_orders = nullptr;   // int[batch], the caller's member order
+    int *d_members = nullptr;  // int[batch], member indices in ascending order of their orders (stable)
+};
+int vbatch_sort(const int *orders, int batch, int *perm, int *class_begin, int *order_begin);
+
+// A X = B: one launch of a call, the `count` sorted members from `first` on (of a uniform batch: all of them) with the
+// columns col0 ... col0 + cols - 1 of their B.  The six ints are what mi32_vbatch_solve_launches reports per launch.
+struct SolveLaunch {
+    int first, count, col0, cols;
+    KernelInstance kernel;
+};
+using SolveLaunchFn = std::function<bool(const SolveLaunch &)>;  // false ends the walk
+int solve_chunk_cols(int n);  // the widest chunk of columns beside an order; 0: the order has no spare column
+// the launches of a uniform batch of order n, then of a plan's members (order_begin as in mi32_vbatch), in the order
+// they are enqueued; solve_chunk_cols(n) > 0 / vsolve_has_columns(order_begin) is the caller's business
+void solve_walk(int n, int batch, int nrhs, const SolveLaunchFn &f);
+void vsolve_walk(const int *order_begin, int nrhs, const SolveLaunchFn &f);
+bool vsolve_has_columns(const int *order_begin);  // no member of an order without a spare column
+
+// ---- device-pointer calls (mi32_device.hip) ---------------------------------------------------------------------------
+// One inversion with the settings given, whatever the context's own are.  The caller holds h->mu and has checked the
+// arguments.
+int inv_device(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status);
+int inv_device(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status);
+
+#pragma GCC visibility pop

@@ -1,0 +1,331 @@
+// mi32_device.hip -- the device-pointer entry points of libmat_inv_32.so: what mi32_plan.hip decided, enqueued on the
+// context's streams.
+#include <new>
+#include <vector>
+
+#include "mi32_context.h"
+
+using namespace mi32;
+
+// A uniform batch on the one-launch paths: the register-resident kernels up to kResidentMaxOrder rows, the
+// workgroup-resident ones above (n <= kWorkgroupMaxOrder is the caller's business).  det: where the determinants go,
+// empty for none; d_inv may be null only with one.  The caller holds h->mu and has set the device.
+template <typename T>
+static int one_launch_device(mi32_context *h, bool pivoting, const T *d_a, int n, int batch, T *d_inv, int *d_status,
+                             const DetOut det)
+{
+    MI32_TRY(zeroed_status_buffer(h, d_status, batch, &d_status));
+    const hipError_t e = n <= kResidentMaxOrder
+                             ? resident_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting)
+                             : workgroup_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting);
+    return hip_status(e, "kernel launch");
+}
+
+// how a blocked fp32 inversion of order n is enqueued on this context
+static BlockedExec blocked_exec(mi32_context *h, const Settings &s, int n)
+{
+    BlockedExec ex;
+    ex.stream = h->stream;
+    ex.aux = s.lookahead ? h->aux_stream : nullptr;
+    ex.events = h->la_events;
+    ex.n_events = h->aux_stream ? 8 : 0;
+    lookahead_geometry(h->cu_count, n, &ex.aux_workgroups, &ex.aux_exclusive);
+    ex.prof = h->prof;
+    ex.pivoting = s.pivoting;
+    return ex;
+}
+
+// The two halves of a split batch (split_batch of mi32_plan.hip), the second on the context's split stream; the
+// workspace holds one part per half (ws_bytes_for).
+static int blocked_invert_split(mi32_context *h, const BlockedPlan &p, const BlockedExec &ex, const float *d_a, float *d_inv,
+                                int batch, int *d_status)
+{
+    const int b0 = (batch + 1) / 2, b1 = batch - b0;
+    const size_t mat = (size_t)p.n * p.n;
+    char *ws1 = (char *)h->ws.ptr + blocked_workspace_bytes(p, b0);
+    // the second stream joins here and is joined again at the end (events 0 and 1 are free: the
+    // look-ahead, their other user, only runs for single matrices)
+    MI32_HIP(hipEventRecord(h->la_events[0], h->stream));
+    MI32_HIP(hipStreamWaitEvent(h->split_stream, h->la_events[0], 0));
+    BlockedExec ex0 = ex, ex1 = ex;
+    ex0.aux = ex1.aux = nullptr;
+    ex1.stream = h->split_stream;
+    hipError_t e = blocked_invert(p, d_a, d_inv, b0, d_status, h->ws.ptr, ex0);
+    if (e == hipSuccess)
+        e = blocked_invert(p, d_a + (size_t)b0 * mat, d_inv + (size_t)b0 * mat, b1, d_status + b0, ws1, ex1);
+    MI32_HIP(hipEventRecord(h->la_events[1], h->split_stream));
+    MI32_HIP(hipStreamWaitEvent(h->stream, h->la_events[1], 0));
+    return hip_status(e, "kernel launch");
+}
+
+int inv_device(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status)
+{
+    MI32_HIP(hipSetDevice(h->device));
+    const int algo = resolve_algo(s, n, sizeof(float));
+    MI32_TRY(h->ws.ensure(h, ws_bytes_for(s, n, batch, algo)));
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
+        return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
+    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
+    hipError_t e;
+    if (algo == MI32_ALGO_SWEEP)
+        e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting);
+    else {
+        const BlockedExec ex = blocked_exec(h, s, n);
+        const BlockedPlan p = plan_blocked(s, n, batch);
+        // (plans with panels shared by several workgroups are not split: those workgroups need whole CUs at the same
+        // time, which the other half's rank-bw grid would keep from them for the length of its launch)
+        if (h->split_stream && split_batch(s, algo, n, batch) && !p.multi_panel)
+            return blocked_invert_split(h, p, ex, d_a, d_inv, batch, d_status);
+        e = blocked_invert(p, d_a, d_inv, batch, d_status, h->ws.ptr, ex);
+    }
+    return hip_status(e, "kernel launch");
+}
+
+int inv_device(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status)
+{
+    MI32_HIP(hipSetDevice(h->device));
+    const int algo = resolve_algo(s, n, sizeof(double));
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
+        return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
+    const bool blocked = algo == MI32_ALGO_BLOCKED;
+    const bool nopivot = blocked && !s.pivoting;
+    const Blocked64Plan bp = make_blocked64_plan(n, block_w64(s));
+    const NoPivot64Plan npp = make_nopivot64_plan(n, block_w64(s));
+    const SweepPlan sp = make_sweep_plan(n);
+    MI32_TRY(h->ws.ensure(h, nopivot ? nopivot64_workspace_bytes(npp, batch)
+                             : blocked ? blocked64_workspace_bytes(bp, batch)
+                                       : sweep_workspace_bytes(sp, batch, sizeof(double))));
+    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
+    const hipError_t e =
+        nopivot   ? nopivot64_invert(npp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof)
+        : blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof)
+                  : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting);
+    return hip_status(e, "kernel launch");
+}
+
+// the arguments are checked before the context is touched
+template <typename T>
+static int inv_device_checked(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status)
+{
+    if (!h || !d_a || !d_inv || n <= 0 || batch <= 0 || d_a == d_inv) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return inv_device(h, h->set, d_a, n, batch, d_inv, d_status);
+}
+
+// the inverse with the determinant on the one-launch paths, whatever the context's algorithm (see the header); the
+// arguments are checked before the context is touched
+template <typename T>
+static int inv_det_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, double *d_det_mant,
+                          int *d_det_exp)
+{
+    if (!h || !d_a || n <= 0 || n > kWorkgroupMaxOrder || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp)
+        return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, DetOut{d_det_mant, d_det_exp});
+}
+
+// A X = B on the one-launch paths: one launch per chunk of columns (solve_walk); every launch repeats the elimination
+// of A, and the status words are zeroed once: a launch only ever raises a member's flag.
+template <typename T>
+static int solve_device(mi32_context *h, const T *d_a, int n, int batch, const T *d_b, int nrhs, T *d_x, int *d_status)
+{
+    if (!h || !d_a || !d_b || !d_x || solve_chunk_cols(n) == 0 || batch <= 0 || nrhs <= 0 || d_x == d_a) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    MI32_TRY(zeroed_status_buffer(h, d_status, batch, &d_status));
+    hipError_t e = hipSuccess;
+    solve_walk(n, batch, nrhs, [&](const SolveLaunch &l) {
+        const SolveArgs<T> s{d_a, d_b, d_x, d_status, n, batch, nrhs, l.col0, l.cols};
+        e = l.kernel.lanes ? resident_solve(s, h->stream, h->prof, h->set.pivoting)
+                           : workgroup_solve(s, h->stream, h->prof, h->set.pivoting);
+        return e == hipSuccess;
+    });
+    return hip_status(e, "kernel launch");
+}
+
+// DET: the det kernels, d_inv may be null
+template <typename T, bool DET>
+static int inv_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
+                               T *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant = nullptr,
+                               int *d_det_exp = nullptr)
+{
+    if (!h || !p || !d_a || (!DET && !d_inv) || (DET && (!d_det_mant || !d_det_exp))) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    MI32_TRY(zeroed_status_buffer(h, d_status, p->batch, &d_status));
+    const VbatchArgs<T> v{p->d_orders, p->d_members, d_a, d_inv, d_lda, d_ldinv, d_status};
+    const DetOut det = DET ? DetOut{d_det_mant, d_det_exp} : DetOut{nullptr, nullptr};
+    for (int k = 0; k < kVbatchClasses; ++k) {
+        const int first = p->class_begin[k], count = p->class_begin[k + 1] - first;
+        if (count == 0) continue;  // a class without members is not launched
+        const KernelInstance &c = kVbatchClass[k];
+        MI32_TRY(hip_status(
+            c.lanes ? resident_vinvert(c.lanes, v, det, first, count, h->stream, h->prof, h->set.pivoting)
+                    : workgroup_vinvert(c.rows_per_thread, v, det, first, count, h->stream, h->prof, h->set.pivoting),
+            "kernel launch"));
+    }
+    return MI32_OK;
+}
+
+// A X = B for a variable-size batch: the launches of vsolve_walk.  The arguments are checked before the context is
+// touched.
+template <typename T>
+static int solve_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda,
+                                 const T *const *d_b, const int *d_ldb, int nrhs, T *const *d_x, const int *d_ldx,
+                                 int *d_status)
+{
+    if (!h || !p || !d_a || !d_b || !d_x || nrhs <= 0) return MI32_BAD_SHAPE;
+    if (p->device != h->device || !vsolve_has_columns(p->order_begin)) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    // zeroed once: a launch only ever raises a member's flag
+    MI32_TRY(zeroed_status_buffer(h, d_status, p->batch, &d_status));
+    hipError_t e = hipSuccess;
+    vsolve_walk(p->order_begin, nrhs, [&](const SolveLaunch &l) {
+        const VsolveArgs<T> v{p->d_orders, p->d_members, d_a, d_b, d_x, d_lda, d_ldb, d_ldx, d_status, nrhs, l.col0, l.cols};
+        e = l.kernel.lanes
+                ? resident_vsolve(l.kernel.lanes, v, l.first, l.count, h->stream, h->prof, h->set.pivoting)
+                : workgroup_vsolve(l.kernel.rows_per_thread, v, l.first, l.count, h->stream, h->prof, h->set.pivoting);
+        return e == hipSuccess;
+    });
+    return hip_status(e, "kernel launch");
+}
+
+extern "C" {
+
+int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status)
+{
+    return inv_device_checked(h, d_a, n, batch, d_inv, d_status);
+}
+
+int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status)
+{
+    return inv_device_checked(h, d_a, n, batch, d_inv, d_status);
+}
+
+int mi32_inv_det_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                        double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                            double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const float *d_b, int nrhs, float *d_x,
+                      int *d_status)
+{
+    return solve_device(h, d_a, n, batch, d_b, nrhs, d_x, d_status);
+}
+
+int mi32_solve_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, const double *d_b, int nrhs, double *d_x,
+                          int *d_status)
+{
+    return solve_device(h, d_a, n, batch, d_b, nrhs, d_x, d_status);
+}
+
+int mi32_vbatch_create(mi32_handle_t h, const int *orders, int batch, mi32_vbatch_t *out)
+{
+    if (!out) return MI32_BAD_SHAPE;
+    *out = nullptr;
+    if (!h || !orders || batch <= 0) return MI32_BAD_SHAPE;
+    std::vector<int> perm((size_t)batch);
+    mi32_vbatch *p = new (std::nothrow) mi32_vbatch();
+    if (!p) return MI32_RUNTIME_ERROR;
+    const int rc = vbatch_sort(orders, batch, perm.data(), p->class_begin, p->order_begin);
+    if (rc != MI32_OK) {
+        delete p;
+        return rc;
+    }
+    p->device = h->device;
+    p->batch = batch;
+    const size_t bytes = (size_t)batch * sizeof(int);
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_orders, bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_members, bytes);
+    // synchronous copies from pageable memory: the host arrays may go away when this returns
+    if (e == hipSuccess) e = hipMemcpy(p->d_orders, orders, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_members, perm.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)mi32_vbatch_destroy(p);
+        return hip_status(e, "mi32_vbatch_create");
+    }
+    *out = p;
+    return MI32_OK;
+}
+
+int mi32_vbatch_destroy(mi32_vbatch_t p)
+{
+    if (!p) return MI32_OK;
+    (void)hipSetDevice(p->device);
+    // hipFree synchronises with the device: calls that still read the plan finish first
+    if (p->d_orders) (void)hipFree(p->d_orders);
+    if (p->d_members) (void)hipFree(p->d_members);
+    delete p;
+    return MI32_OK;
+}
+
+int mi32_vbatch_info(mi32_vbatch_t p, int *batch, int *class_begin)
+{
+    if (!p) return MI32_BAD_SHAPE;
+    if (batch) *batch = p->batch;
+    if (class_begin)
+        for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = p->class_begin[k];
+    return MI32_OK;
+}
+
+int mi32_inv_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                             float *const *d_inv, const int *d_ldinv, int *d_status)
+{
+    return inv_device_vbatched<float, false>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+}
+
+int mi32_inv_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                 double *const *d_inv, const int *d_ldinv, int *d_status)
+{
+    return inv_device_vbatched<double, false>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status);
+}
+
+int mi32_inv_det_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                                 float *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                 int *d_det_exp)
+{
+    return inv_device_vbatched<float, true>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                     double *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
+                                     int *d_det_exp)
+{
+    return inv_device_vbatched<double, true>(h, p, d_a, d_lda, d_inv, d_ldinv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_solve_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
+                               const float *const *d_b, const int *d_ldb, int nrhs, float *const *d_x, const int *d_ldx,
+                               int *d_status)
+{
+    return solve_device_vbatched(h, p, d_a, d_lda, d_b, d_ldb, nrhs, d_x, d_ldx, d_status);
+}
+
+int mi32_solve_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                   const double *const *d_b, const int *d_ldb, int nrhs, double *const *d_x,
+                                   const int *d_ldx, int *d_status)
+{
+    return solve_device_vbatched(h, p, d_a, d_lda, d_b, d_ldb, nrhs, d_x, d_ldx, d_status);
+}
+
+int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out)
+{
+    if (!h || !d_a || !d_x || !d_out || n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    MI32_TRY(h->ws.ensure(h, ws_bytes_for(h->set, n, batch, resolve_algo(h->set, n, sizeof(float)))));
+    return hip_status(residual_launch(d_a, d_x, n, batch, d_out, h->ws.ptr, h->stream), "residual launch");
+}
+
+}  // extern "C"

@@ -1,0 +1,336 @@
+// mi32_plan.hip -- launch planning of libmat_inv_32.so: which algorithm, which blocking, how much workspace, which
+// kernel instance for which members and columns.  Pure host code: functions of the settings, the environment and the
+// shape, no HIP runtime call and no context -- the mi32_resolve_* entry points answer with what a call would do.
+#include "mi32_context.h"
+
+using namespace mi32;
+
+// Blocked from a measured cross-over on MI355X: fp32 32 rows, fp64 (windowed steps + rank-bw updates on the fp64
+// matrix cores) 256 rows; the no-pivot variants 512 rows both (fp32: the W x W diagonal block is its whole "panel";
+// fp64: a blocked path of its own, mi32_nopivot64.hip).  MI32_ALGO_SWEEP keeps the unblocked sweep.
+int resolve_algo(const Settings &s, int n, size_t elem_bytes)
+{
+    const bool f32 = elem_bytes == sizeof(float);
+    int algo = s.algo != MI32_ALGO_AUTO ? s.algo : env_int("MI32_ALGO", MI32_ALGO_AUTO);
+    // the register-resident path holds orders up to 64; above, RESIDENT resolves to what AUTO resolves to
+    if (algo == MI32_ALGO_RESIDENT && n <= kResidentMaxOrder) return algo;
+    // MI32_ALGO_WORKGROUP up to 128 rows: the register-resident path takes the orders it holds, so that one setting
+    // serves orders on both sides of 64; above 128 it resolves to what AUTO resolves to
+    if (algo == MI32_ALGO_WORKGROUP && n <= kWorkgroupMaxOrder)
+        return n <= kResidentMaxOrder ? MI32_ALGO_RESIDENT : MI32_ALGO_WORKGROUP;
+    const int cross = !s.pivoting ? 512 : f32 ? 32 : 256;
+    if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
+    if (f32 && algo == MI32_ALGO_BLOCKED && !blocked_supported(n)) algo = MI32_ALGO_SWEEP;  // panel would not fit in registers
+    return algo;
+}
+
+BlockedPlan plan_blocked(const Settings &s, int n, int batch)
+{
+    const int w = s.panel_w ? s.panel_w : env_int("MI32_PANEL_W", 0);
+    int bw = s.block_w ? s.block_w : env_int("MI32_BLOCK_W", 0);
+    if (bw == 0) {
+        // A single matrix is bound by the pivot chain and bw = 256 gives the rank-bw update its best
+        // arithmetic intensity.  A batch that fills the GPU is bound by the HBM traffic of the in-block
+        // updates (np x bw re-written per sub-panel): bw = 128 halves it (measured 64 x 2048^2:
+        // 23.0 ms vs 24.7 ms; single 4096^2: 11.4 ms vs 11.2 ms).
+        const double elems = (double)batch * (double)n * (double)n;
+        bw = (batch >= 8 && elems >= 64.0 * 1024.0 * 1024.0) ? 128 : 256;
+        // (Rounds 1-2 ran N > 14336 with bw = 512 for the rank-bw update's sake: 120 instead of 114 TFLOP/s.  With the
+        // pivot-row strips of round 3 an in-block update tile costs more and there are twice as many per sub-panel at
+        // 512: 16384^2 122 ms at 256, 126 at 384, 140 at 512; 12288^2 65.5 vs 75.9; 8192^2 33.9 vs 38.0.)
+    }
+    return make_blocked_plan(n, w, bw, batch);
+}
+
+int block_w64(const Settings &s) { return s.block_w ? s.block_w : env_int("MI32_BLOCK_W64", 0); }
+
+size_t ws_bytes_for(const Settings &s, int n, int batch, int algo)
+{
+    size_t a;
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) a = 0;  // no working copy: only the residual check needs a workspace
+    else if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
+    else {
+        const BlockedPlan p = plan_blocked(s, n, batch);
+        // a batch that may be split in two halves (mi32_inv_device) carves one workspace per half
+        a = blocked_workspace_bytes(p, (batch + 1) / 2) + blocked_workspace_bytes(p, batch - (batch + 1) / 2);
+        const size_t whole = blocked_workspace_bytes(p, batch);
+        if (whole > a) a = whole;
+    }
+    const size_t r = residual_workspace_bytes(n, batch);
+    return a > r ? a : r;
+}
+
+// The look-ahead half of a single large matrix (blocked_invert): how many CUs it runs on and whether it shares them.
+// Measured on MI355X (256 CUs), ms per inversion, "free CUs / LDS KB per look-ahead workgroup":
+//   N  4096:  32/84 8.81   32/156 8.66   64/156 8.53   96/156 8.51   128/156 8.49
+//   N  6144:  16/84 18.96  32/84 17.88   32/156 17.78  64/156 17.01  128/156 17.33
+//   N  8192:  16/84 30.6   32/156 30.3   64/156 29.5
+//   N 10240:  16/84 41.7   32/84 40.6    32/156 42.1   64/156 40.9   128/156 50.2
+//   N 12288:  16/84 58.5   32/84 57.9    32/156 59.0   64/156 60.8   128/156 84.7
+//   N 16384:  16/84 107.5  32/84 111.4   32/156 125.4  64/156 124.3  (8/84 107.0, 5/84 137.7: the shared panels starve)
+// Round 3 (reference-order strips, bw = 256 everywhere), same notation:
+//   N  8192:  8/84 34.8   16/84 34.9   32/84 33.2   64/84 33.9   32/156 35.6   64/156 33.9
+//   N 12288:  8/84 70.5   16/84 70.4   32/84 66.9   64/84 67.9   32/156 72.8   64/156 68.4
+//   N 16384:  8/84 119.1  16/84 121.8  32/84 125.4  64/84 141.9  32/156 134.1
+//   (two or three look-ahead workgroups per CU, 76 / 50 KB each: 8192 37.7, 12288 77.8, 16384 143-145: the shared panels starve)
+// Up to ~7168 rows the half is short against the panel phase: it gets few CUs, all to itself, and the panel chain
+// keeps the rest undisturbed; above, every block waits for the half: it gets all but 32 / 16 CUs and shares them.
+void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive)
+{
+    int reserve;
+    bool excl;
+    if (n < 5120) { reserve = cus / 2; excl = true; }
+    else if (n <= 7168) { reserve = cus / 4; excl = true; }
+    else if (n <= 14336) { reserve = cus / 8; excl = false; }
+    else { reserve = cus / 32; excl = false; }
+    if (reserve < 1) reserve = 1;
+    if (reserve > cus - 1) reserve = cus - 1;
+    *workgroups = cus - reserve;
+    *exclusive = excl;
+}
+
+// A GPU-filling batch of the blocked path is run as two halves on the context's two streams: the MFMA-bound
+// rank-bw launches of one half overlap the latency / HBM-bound sub-panel launches of the other (64 x 2048^2:
+// 18.5 -> 17.4 ms; three or four parts lose; round 3: 8 x 4096^2 23.6 -> 22.1 ms, 4 x 4096^2 15.7 -> 15.0: from four
+// matrices on).  Both halves use the blocking of the whole batch, so a matrix's
+// result does not depend on the split; mi32_set_lookahead(h, 0) turns the second stream off altogether.
+bool split_batch(const Settings &s, int algo, int n, int batch)
+{
+    return algo == MI32_ALGO_BLOCKED && s.lookahead && batch >= 4 && (double)batch * n * n >= 64.0 * 1024.0 * 1024.0 &&
+           env_int("MI32_BATCH_SPLIT", 1) != 0;
+}
+
+// ---- variable-size batches ---------------------------------------------------------------------------------------
+// 0 ... 3 the register-resident instances, 4 ... 7 the workgroup-resident ones
+const KernelInstance kVbatchClass[kVbatchClasses] = {{8, 0}, {16, 0}, {32, 0}, {64, 0}, {0, 40}, {0, 48}, {0, 56}, {0, 64}};
+
+// The kernel class of an order; resident_lanes and workgroup_rows_per_thread stay the single source of the
+// boundaries.  -1: no instance takes the order.
+static int vbatch_class(int n)
+{
+    const KernelInstance inst{resident_lanes(n), workgroup_rows_per_thread(n)};
+    for (int k = 0; k < kVbatchClasses; ++k)
+        if (kVbatchClass[k] == inst) return k;
+    return -1;
+}
+
+// The counting sort behind mi32_vbatch_bin, O(batch) and stable; order_begin (may be null; int[kWorkgroupMaxOrder + 2]):
+// the members of order n are perm[order_begin[n] .. order_begin[n + 1]).  perm and class_begin may be null too.
+int vbatch_sort(const int *orders, int batch, int *perm, int *class_begin, int *order_begin)
+{
+    if (!orders || batch <= 0) return MI32_BAD_SHAPE;
+    int start[kWorkgroupMaxOrder + 2] = {};
+    for (int b = 0; b < batch; ++b) {
+        const int n = orders[b];
+        if (n < 1 || n > kWorkgroupMaxOrder) return MI32_BAD_SHAPE;
+        ++start[n + 1];
+    }
+    int cls[kVbatchClasses + 1] = {};
+    for (int n = 1; n <= kWorkgroupMaxOrder; ++n) {
+        cls[vbatch_class(n) + 1] += start[n + 1];  // the members of order n (every order 1 ... 128 has a class)
+        start[n + 1] += start[n];                  // start[n]: where the members of order n begin
+    }
+    for (int k = 0; k < kVbatchClasses; ++k) cls[k + 1] += cls[k];
+    if (class_begin)
+        for (int k = 0; k <= kVbatchClasses; ++k) class_begin[k] = cls[k];
+    if (order_begin)
+        for (int n = 0; n <= kWorkgroupMaxOrder + 1; ++n) order_begin[n] = start[n];
+    if (perm)
+        for (int b = 0; b < batch; ++b) perm[start[orders[b]]++] = b;
+    return MI32_OK;
+}
+
+// ---- A X = B on the one-launch paths ----------------------------------------------------------------------------------
+// A call's nrhs columns are cut into chunks of at most solve_chunk_cols(n): what is left of one 64-lane group beside an
+// order up to 32, of the workgroup's 128 columns above (0: no order of these kernels, or no spare column).  Full chunks
+// first; every launch repeats the elimination of A.
+int solve_chunk_cols(int n)
+{
+    return n < 1 || n >= kWorkgroupMaxOrder ? 0 : n <= 32 ? kResidentMaxOrder - n : kWorkgroupMaxOrder - n;
+}
+// THE rule, chunk width -> kernel: a chunk whose width n + cols fits a 64-lane group runs on the register-resident
+// kernel (resident_lanes of the width), a wider one on the workgroup-resident kernel.
+static KernelInstance solve_instance(int n, int cols)
+{
+    if (n + cols <= kResidentMaxOrder) return {resident_lanes(n + cols), 0};
+    return {0, workgroup_solve_rows_per_thread(n)};
+}
+// How an order's chunks run.  Two orders' chunk sequences agree when these agree: col0 and cols of every chunk follow.
+struct SolveChunks {
+    int cols;              // columns of a full chunk (of the only chunk, when nrhs fits one)
+    long long chunks;      // ceil(nrhs / cap)
+    KernelInstance first;  // the kernel of the full chunks
+    KernelInstance last;   // of the remainder (the same when there is none)
+    bool operator==(const SolveChunks &o) const
+    {
+        return cols == o.cols && chunks == o.chunks && first == o.first && last == o.last;
+    }
+};
+static SolveChunks solve_chunks(int n, int nrhs)
+{
+    const int cap = solve_chunk_cols(n);
+    SolveChunks c;
+    c.cols = nrhs < cap ? nrhs : cap;
+    c.chunks = ((long long)nrhs + cap - 1) / cap;
+    c.first = solve_instance(n, c.cols);
+    c.last = solve_instance(n, (int)(nrhs - (c.chunks - 1) * cap));
+    return c;
+}
+// one launch per chunk for the `count` members from `first` on; false: f ended the walk
+static bool walk_chunks(const SolveChunks &c, int nrhs, int first, int count, const SolveLaunchFn &f)
+{
+    for (long long k = 0; k < c.chunks; ++k) {
+        const long long col0 = k * c.cols;
+        const int cols = (int)(nrhs - col0 < c.cols ? nrhs - col0 : c.cols);
+        if (!f(SolveLaunch{first, count, (int)col0, cols, k + 1 < c.chunks ? c.first : c.last})) return false;
+    }
+    return true;
+}
+
+void solve_walk(int n, int batch, int nrhs, const SolveLaunchFn &f) { (void)walk_chunks(solve_chunks(n, nrhs), nrhs, 0, batch, f); }
+
+// Every member is treated as a uniform batch of its order is; one run of launches for every maximal run of consecutive
+// sorted members whose chunk sequences agree.  The one place the rule lives: mi32_vbatch_solve_launches reports this
+// list and mi32_solve_device_vbatched* walks it.
+void vsolve_walk(const int *order_begin, int nrhs, const SolveLaunchFn &f)
+{
+    int n = 1;
+    while (n < kWorkgroupMaxOrder) {
+        if (order_begin[n + 1] == order_begin[n]) {  // no member of this order
+            ++n;
+            continue;
+        }
+        const SolveChunks c = solve_chunks(n, nrhs);
+        int end = n + 1;  // the run takes the orders n ... end - 1
+        while (end < kWorkgroupMaxOrder && (order_begin[end + 1] == order_begin[end] || solve_chunks(end, nrhs) == c)) ++end;
+        // (orders without members at the run's end belong to no launch: the range below does not see them)
+        if (!walk_chunks(c, nrhs, order_begin[n], order_begin[end] - order_begin[n], f)) return;
+        n = end;
+    }
+}
+
+// an order 128 has no spare column
+bool vsolve_has_columns(const int *order_begin)
+{
+    return order_begin[kWorkgroupMaxOrder + 1] == order_begin[kWorkgroupMaxOrder];
+}
+
+extern "C" {
+
+size_t mi32_workspace_bytes(int n, int batch, int algo)
+{
+    if (n <= 0 || batch <= 0) return 0;
+    Settings s;
+    s.algo = algo;
+    return ws_bytes_for(s, n, batch, resolve_algo(s, n, sizeof(float)));
+}
+
+int mi32_resolve_algo(mi32_handle_t h, int n, int /*batch*/) { return resolve_algo(settings_of(h), n, sizeof(float)); }
+
+int mi32_resolve_blocking(mi32_handle_t h, int n, int batch, int *panel_width, int *block_width)
+{
+    if (n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
+    const BlockedPlan p = plan_blocked(settings_of(h), n, batch);
+    if (panel_width) *panel_width = p.w;
+    if (block_width) *block_width = p.bw;
+    return MI32_OK;
+}
+
+int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, int capacity, int *nblocks)
+{
+    if (n <= 0 || batch <= 0 || capacity < 0 || (capacity > 0 && !widths)) return MI32_BAD_SHAPE;
+    const BlockedPlan p = plan_blocked(settings_of(h), n, batch);
+    if (nblocks) *nblocks = p.nblk;
+    for (int b = 0; b < p.nblk && b < capacity; ++b) widths[b] = p.wblk[b];
+    return MI32_OK;
+}
+
+int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width)
+{
+    if (n <= 0 || !block_width) return MI32_BAD_SHAPE;
+    const Settings s = settings_of(h);
+    if (resolve_algo(s, n, sizeof(double)) != MI32_ALGO_BLOCKED) *block_width = 0;
+    else *block_width = s.pivoting ? make_blocked64_plan(n, block_w64(s)).bw : make_nopivot64_plan(n, block_w64(s)).bw;
+    return MI32_OK;
+}
+
+int mi32_resolve_resident(mi32_handle_t /*h*/, int n, int elem_bytes, int *lanes_per_matrix, int *max_order)
+{
+    if (n <= 0 || (elem_bytes != 4 && elem_bytes != 8)) return MI32_BAD_SHAPE;
+    if (lanes_per_matrix) *lanes_per_matrix = resident_lanes(n);
+    if (max_order) *max_order = kResidentMaxOrder;
+    return MI32_OK;
+}
+
+int mi32_resolve_workgroup(mi32_handle_t /*h*/, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
+                           int *max_order)
+{
+    if (n <= 0 || (elem_bytes != 4 && elem_bytes != 8)) return MI32_BAD_SHAPE;
+    const int rpt = workgroup_rows_per_thread(n);
+    if (threads_per_matrix) *threads_per_matrix = rpt ? 256 : 0;
+    if (rows_per_thread) *rows_per_thread = rpt;
+    if (max_order) *max_order = kWorkgroupMaxOrder;
+    return MI32_OK;
+}
+
+int mi32_resolve_solve(mi32_handle_t /*h*/, int n, int nrhs, int elem_bytes, int *chunk_cols, int *launches, int *lanes,
+                       int *rows_per_thread)
+{
+    const int cap = solve_chunk_cols(n);
+    if (cap == 0 || nrhs <= 0 || (elem_bytes != 4 && elem_bytes != 8) || !chunk_cols || !launches || !lanes ||
+        !rows_per_thread)
+        return MI32_BAD_SHAPE;
+    const SolveChunks c = solve_chunks(n, nrhs);
+    *chunk_cols = cap;
+    *launches = (int)c.chunks;
+    *lanes = c.first.lanes;  // the first chunk's kernel
+    *rows_per_thread = c.first.rows_per_thread;
+    return MI32_OK;
+}
+
+const char *mi32_dominant_kernel(int algo)
+{
+    return algo == MI32_ALGO_WORKGROUP ? "gj_workgroup_kernel"
+           : algo == MI32_ALGO_RESIDENT ? "gj_resident_kernel"
+           : algo == MI32_ALGO_SWEEP  ? "gj_sweep_step_kernel"
+                                      : "gj_rank_bw2_kernel";
+}
+
+int mi32_vbatch_bin(const int *orders, int batch, int *perm, int *class_begin)
+{
+    if (!perm || !class_begin) return MI32_BAD_SHAPE;
+    return vbatch_sort(orders, batch, perm, class_begin, nullptr);
+}
+
+int mi32_vbatch_solve_launches(const int *orders, int batch, int nrhs, int *launches, int capacity, int *count)
+{
+    if (!orders || !count || batch <= 0 || nrhs <= 0 || capacity < 0 || (capacity > 0 && !launches)) return MI32_BAD_SHAPE;
+    int order_begin[kWorkgroupMaxOrder + 2];
+    if (vbatch_sort(orders, batch, nullptr, nullptr, order_begin) != MI32_OK) return MI32_BAD_SHAPE;
+    if (!vsolve_has_columns(order_begin)) return MI32_BAD_SHAPE;
+    long long total = 0;
+    vsolve_walk(order_begin, nrhs, [&](const SolveLaunch &s) {
+        if (total < capacity) {
+            int *l = launches + 6 * total;
+            l[0] = s.first, l[1] = s.count, l[2] = s.col0, l[3] = s.cols, l[4] = s.kernel.lanes, l[5] = s.kernel.rows_per_thread;
+        }
+        ++total;
+        return true;
+    });
+    if (total > 0x7fffffffLL) return MI32_BAD_SHAPE;
+    *count = (int)total;
+    return MI32_OK;
+}
+
+// GPU g of G owns the matrices [g * ceil(B / G), min(B, (g + 1) * ceil(B / G))) (possibly none)
+int mi32_shard_range(int batch, int ngpus, int g, int *lo, int *hi)
+{
+    if (batch < 0 || ngpus <= 0 || g < 0 || g >= ngpus || !lo || !hi) return MI32_BAD_SHAPE;
+    const int per = (batch + ngpus - 1) / ngpus;
+    const long long l = (long long)g * per;
+    *lo = l < batch ? (int)l : batch;
+    *hi = (l + per < batch) ? (int)(l + per) : batch;
+    return MI32_OK;
+}
+
+}  // extern "C"

@@ -144,7 +144,7 @@ def expected_inverse(oracle, member):
 
 
 def would_split(n, batch):
-    """split_batch of mi32_host.hip, for plans without shared panels: from four matrices and 64 Mi elements on the
+    """split_batch of mi32_plan.hip, for plans without shared panels: from four matrices and 64 Mi elements on the
     batch runs as two halves, ceil(batch / 2) and the rest, on two streams."""
     return batch >= 4 and batch * n * n >= 64 * 1024 * 1024
 

@@ -878,6 +878,56 @@ def test_host_pointer_entry_points_are_thread_safe(oracle):
     assert total >= compute > 0
 
 
+def test_host_copy_paths_at_the_copier_threshold(monkeypatch):
+    """The host-pointer calls move 32 MiB and more through the six-lane pinned copier (2 MiB chunks, two buffers per
+    lane) and less, or anything with MI32_HOST_COPY=0, through one plain copy.  Batches of 64 x 64 fp32 matrices are
+    16 KiB steps around that threshold: 2047 members stay under it, 2048 are exactly 32 MiB (16 full chunks, the
+    `>=`), 2049 make 17 chunks -- lanes 0-4 get three (a pinned buffer is re-used behind its event), lane 5 two, the
+    last chunk is 16 KiB.  Every route must give, bit for bit, what the device-pointer call gives on the same
+    members (it uses neither copy path and a member's result does not depend on its neighbours), the status words
+    included: the last member is singular.  The fp64 twin: one 2048 x 2048 matrix, exactly 32 MiB."""
+    n, B = 64, 2049
+    rng = np.random.default_rng(20_490)
+    mats = rng.uniform(-1.0, 1.0, (B, n, n)) + n * np.eye(n)   # diagonally dominant ...
+    perm = rng.permuted(np.tile(np.arange(n), (B, 1)), axis=1)
+    mats = np.take_along_axis(mats, perm[:, :, None], axis=1)  # ... with its rows permuted, each member its own way
+    mats = mats.astype(np.float32)
+    mats[B - 1] = 1.0
+    assert len({m.tobytes() for m in mats}) == B
+    inv = g.Inverter()
+    try:
+        x, st = inv.inv(torch.from_numpy(mats).cuda())
+        torch.cuda.synchronize()
+        want, want_st = x.cpu().numpy(), st.cpu().numpy()
+        assert want_st.tolist() == [0] * (B - 1) + [2]
+        for knob in (None, "0"):
+            if knob is None:
+                monkeypatch.delenv("MI32_HOST_COPY", raising=False)
+            else:
+                monkeypatch.setenv("MI32_HOST_COPY", knob)
+            for b in (2047, 2048, 2049):
+                assert (b * n * n * 4 >= 32 << 20) == (b >= 2048)
+                got, got_st = g.matrix_inv_32_batched(mats[:b])
+                assert np.array_equal(got_st, want_st[:b]), (knob, b)
+                assert np.array_equal(got.view(np.uint32), want[:b].view(np.uint32)), (knob, b)
+        n64 = 2048
+        a64 = gate_matrix(n64, 20_491).astype(np.float64)
+        assert a64.nbytes == 32 << 20
+        x64, st64 = inv.inv(torch.from_numpy(a64).cuda())
+        torch.cuda.synchronize()
+        want64 = x64.cpu().numpy().reshape(-1)
+        assert int(st64[0]) == 0 and np.isfinite(want64).all()
+        for knob in (None, "0"):
+            if knob is None:
+                monkeypatch.delenv("MI32_HOST_COPY", raising=False)
+            else:
+                monkeypatch.setenv("MI32_HOST_COPY", knob)
+            got64 = g.matrix_inv_64(a64.reshape(-1), n64)
+            assert got64.size == n64 * n64 and np.array_equal(got64.view(np.uint64), want64.view(np.uint64)), knob
+    finally:
+        inv.close()
+
+
 def test_device_call_without_status_buffer(inv_blocked):
     """d_status = NULL is allowed by the C ABI: the context keeps the status words itself."""
     n = 200

@@ -61,6 +61,7 @@ C_ABI_SYMBOLS = (
     "mi32_resolve_blocking_f64",
     "mi32_resolve_blocking",
     "mi32_resolve_panel_widths",
+    "mi32_resolve_route",
     "mi32_resolve_resident",
     "mi32_resolve_workgroup",
     "mi32_vbatch_bin",
@@ -96,6 +97,14 @@ TIMES10_SLOTS = ("queue", "buffers", "build", "makeAug", "pivot", "row", "column
 
 class Mi32Error(RuntimeError):
     pass
+
+
+class Route(ctypes.Structure):
+    """mi32_route_t: how a blocked fp32 call runs (mi32_resolve_route)."""
+    _fields_ = [("np", ctypes.c_int), ("block_width", ctypes.c_int), ("nblocks", ctypes.c_int),
+                ("shared_panels", ctypes.c_int), ("lookahead", ctypes.c_int), ("parts", ctypes.c_int),
+                ("part_batch", ctypes.c_int * 2), ("part_strips_at_end", ctypes.c_int * 2),
+                ("first_fused_block", ctypes.c_int)]
 
 
 def build_library(force: bool = False) -> str:
@@ -196,6 +205,8 @@ def load() -> ctypes.CDLL:
     lib.mi32_resolve_blocking_f64.argtypes = [vp, ctypes.c_int, ip]
     lib.mi32_resolve_panel_widths.restype = ctypes.c_int
     lib.mi32_resolve_panel_widths.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
+    lib.mi32_resolve_route.restype = ctypes.c_int
+    lib.mi32_resolve_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Route), ip, ctypes.c_int]
     lib.mi32_resolve_resident.restype = ctypes.c_int
     lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
     lib.mi32_resolve_workgroup.restype = ctypes.c_int
@@ -235,6 +246,17 @@ def load() -> ctypes.CDLL:
     lib.mi32_version.argtypes = []
     _lib = lib
     return lib
+
+
+def resolve_route(handle, n: int, batch: int):
+    """mi32_resolve_route as (dict of the mi32_route_t fields, workgroups per panel at the start of every outer block);
+    ``handle`` may be None: what a fresh context does."""
+    r = Route()
+    groups = (ctypes.c_int * 128)()
+    check(load().mi32_resolve_route(handle, int(n), int(batch), ctypes.byref(r), groups, 128), "mi32_resolve_route")
+    route = {name: getattr(r, name) for name, _ in Route._fields_}
+    route["part_batch"], route["part_strips_at_end"] = list(r.part_batch), list(r.part_strips_at_end)
+    return route, [int(groups[b]) for b in range(r.nblocks)]
 
 
 def check(rc: int, what: str) -> int:

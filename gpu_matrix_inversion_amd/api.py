@@ -351,6 +351,12 @@ class Inverter:
                    "mi32_resolve_panel_widths")
         return [int(buf[i]) for i in range(min(nb.value, 128))]
 
+    def resolved_route(self, n: int, batch: int = 1):
+        """How a blocked fp32 call of this shape runs on this Inverter: (dict of the ``mi32_route_t`` fields -- shared
+        panels, look-ahead, parts and where each part's strips run, first fused block --, workgroups per panel at the
+        start of every outer block).  ValueError for an order the blocked path does not take."""
+        return _lib.resolve_route(self._h, n, batch)
+
     def dominant_kernel(self, n: int, batch: int = 1) -> str:
         return self._lib.mi32_dominant_kernel(self.resolved_algo(n, batch)).decode()
 

@@ -60,8 +60,10 @@
 // checks: inv(diag(A, I)) = diag(inv(A), I); a real column only ever takes its
 // pivot from the real rows, so the padding is never swapped into the matrix.
 //
-// Where things are.  This file is the translation unit of the whole path: the plan, the workspace layout, the init and
-// un-permute kernels and the schedule (blocked_invert), which launches everything else through the launchers of
+// Where things are.  How a call runs -- blocking, sub-panel widths, fused blocks, shared panels, look-ahead, split,
+// where the strips go -- is decided in mi32_plan.hip (plan_route) and arrives as a BlockedRoute (mi32_internal.h).  This
+// file is the translation unit of every kernel of the path: the workspace layout, the init and un-permute kernels and
+// the schedule (blocked_invert), which walks the route and launches everything else through the launchers of
 //   mi32_blocked_subpanel.h          once per sub-panel: dispatch_subpanel, the multi-workgroup panel, the in-block update
 //                                    alone, the no-pivot variant's diagonal panel; the test and diagnostic hooks
 //   mi32_blocked_block.h             once per block: the block's strips in one launch, the multiplier transposition, the
@@ -72,57 +74,13 @@
 //   mi32_update_tile.h               update(t) and strip(t): the 64-column tiles of the sub-panel launches
 //   mi32_strip.h, mi32_dpp.h         the pivot-row strip; DPP reductions and row helpers
 //   mi32_blocked_internal.h          constants, the launches' argument structs, host helpers
-#include <cstdlib>
-
 #include "mi32_blocked_block.h"
 #include "mi32_blocked_subpanel.h"
 
 namespace mi32 {
 
-BlockedPlan make_blocked_plan(int n, int w, int bw, int batch)
-{
-    BlockedPlan p;
-    p.n = n;
-    p.np = (n + 127) & ~127;
-    // Row stride: np + 64 floats (256 B): keeps rows 256-B aligned and avoids a power-of-two stride.
-    p.ld = p.np + 64;
-    int nt = (p.np >= 2048) ? 1024 : 512;
-    int rpt = 1;
-    while (rpt * nt < p.np) rpt *= 2;
-    if (rpt > 8 && nt == 512) {  // no 512-thread instance holds more than 8 rows per lane: use 1024
-        nt = 1024;
-        rpt = 1;
-        while (rpt * nt < p.np) rpt *= 2;
-    }
-    p.nthreads_panel = nt;
-    p.rpt = rpt;
-    // Multi-workgroup panels need every workgroup of a panel resident at once and a whole CU each; with the
-    // look-ahead kernel holding all but 16 (32 below 8192 rows) CUs that is safe for a few matrices (MI32_MULTI_PANEL=0 turns it off).
-    p.multi_panel = (nt == 1024 && p.np > kPanelGroupRows && batch * kMaxPanelGroups <= 16) ? 1 : 0;
-    if (const char *e = std::getenv("MI32_MULTI_PANEL")) p.multi_panel = p.multi_panel && std::atoi(e) != 0;
-    if (w <= 0) w = 16;  // 32 is selectable where it fits, but measured slower (4.6 vs 4.2 ms at 2048^2)
-    w = (w >= 32) ? 32 : (w >= 16) ? 16 : (w >= 8 ? 8 : 4);
-    p.w = w;
-    if (bw <= 0) bw = 256;
-    bw = (bw + 127) & ~127;
-    if (bw > kMaxBW) bw = kMaxBW;
-    if (bw > p.np) bw = p.np;
-    p.bw = bw;
-    p.nblk = (p.np + bw - 1) / bw;
-    for (int b = 0; b < p.nblk && b < 128; ++b) {
-        int bnt, brpt;
-        panel_geometry(p, p.np - b * bw, bnt, brpt);
-        int wmax = ((bnt == 1024) ? 64 : 128) / brpt;  // floats of slab per thread
-        if (wmax > kMaxW) wmax = kMaxW;
-        int wb = w < wmax ? w : wmax;                  // wmax < 4 (np > 16384) is rejected by blocked_supported()
-        wb = (wb >= 32) ? 32 : (wb >= 16) ? 16 : (wb >= 8 ? 8 : 4);
-        p.wblk[b] = (unsigned char)wb;
-    }
-    return p;
-}
 // (the update tiles address a matrix with 32-bit byte offsets from its base: mi32_rank_bw.h, inblock_update_body)
 static_assert(16384ull * (16384 + 64) * sizeof(float) < (1ull << 32), "a working copy must stay below 4 GiB");
-bool blocked_supported(int n) { return n > 0 && ((n + 127) & ~127) <= 16384; }
 
 struct BlockedWs {
     float *m0, *m1;     // the two working copies, np x ld each
@@ -152,7 +110,7 @@ struct BlockedWs {
     int mtld;           // row stride of mt: every register row of a panel workgroup has a slot (rows >= np too)
     size_t pt_bstride;  // floats between pt[i] and pt[i + 1]
 };
-static size_t blocked_carve(const BlockedPlan &p, int batch, void *base, BlockedWs &o)
+static size_t blocked_carve(const BlockedRoute &p, int batch, void *base, BlockedWs &o)
 {
     const size_t mbytes = align256((size_t)p.np * p.ld * sizeof(float));
     const size_t tbytes = align256((size_t)kMaxW * p.np * sizeof(float));
@@ -191,7 +149,7 @@ static size_t blocked_carve(const BlockedPlan &p, int batch, void *base, Blocked
     o.invp = c.take<int>(ibytes);
     return c.off;
 }
-size_t blocked_workspace_bytes(const BlockedPlan &p, int batch) { BlockedWs ws; return blocked_carve(p, batch, nullptr, ws); }
+size_t blocked_workspace_bytes(const BlockedRoute &r, int batch) { BlockedWs ws; return blocked_carve(r, batch, nullptr, ws); }
 
 // ---- init: A -> diag(A, I) in the first working copy (makeAugmentedMatrix counterpart,
 //      mat_inv_32.cpp:177-192) + the compact copies of the first two sub-panels' columns ------
@@ -262,23 +220,17 @@ __global__ __launch_bounds__(256) void unpermute_columns_ld_kernel(const float *
 // panel phase needs at once, and (B) all other columns.  (A) stays on the main stream; (B) runs on a
 // second stream and overlaps with block b+1's panel phase, which is latency bound on a few CUs.  The
 // next rank-bw update (and the final un-permutation) wait for (B) through an event.
-hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, int batch, int *d_status, void *wsp,
+hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, float *d_inv, int *d_status, void *wsp,
                           const BlockedExec &ex)
 {
+    const int batch = p.part_batch[part];
+    const bool lookahead = p.lookahead;  // (never for a half of a split batch: plan_route)
+    if (lookahead && (ex.aux == nullptr || ex.n_events < 4 || ex.aux_workgroups <= 0)) return hipErrorInvalidValue;
     BlockedWs ws;
     blocked_carve(p, batch, wsp, ws);
     const int np = p.np;
     hipStream_t stream = ex.stream;
     Profiler *prof = ex.prof;
-    // look-ahead pays when the GPU is otherwise idle during the panel phase: a single large matrix
-    // (measured in round 1: 8192^2 51 -> 45 ms, 16384^2 399 -> 330 ms, 4096^2 11.2 -> 11.0 ms, 2048^2 4.2 -> 4.4 ms; with
-    // the half on CUs of its own, round 2: 3584^2 7.39 -> 7.00 ms, 3072^2 5.79 -> 5.63, 2560^2 4.32 -> 4.34, 2048^2 3.01 -> 3.14)
-    // Round 3 (reference-order arithmetic: the pivot rows' strip per block sits between the block's last panel and its
-    // rank-bw update, and rides in the panel launches only WITHOUT the second stream), with / without:
-    // 4096^2 10.23 / 10.09, 4352^2 11.50 / 11.66, 5120^2 15.02 / 15.79, 8192^2 34.0 / 37.1 -> on above 4096 padded rows.
-    int la_min = 4096 + 1;
-    if (const char *ev = std::getenv("MI32_LOOKAHEAD_MIN")) la_min = std::atoi(ev) > 2048 ? std::atoi(ev) : 2048;
-    const bool lookahead = ex.aux != nullptr && ex.n_events >= 4 && ex.aux_workgroups > 0 && batch == 1 && np >= la_min;
     hipError_t e;
     const PanelExport no_export = {ws.pt[0], ws.pt_bstride, -(1 << 30), 1, 0};
     if (d_status) {  // MI32_OK; the init kernel flags non-finite input, the panels bad pivots and lost partners
@@ -288,8 +240,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         // the first two sub-panels of the first block are exported as they are: the first has no pending
         // update at all, the second gets the first one's update in its panel's prologue
         ProfScope ps(prof, KC_INIT, stream);
-        const PanelExport ex0 = {ws.pt[0], ws.pt_bstride, 0, ex.pivoting ? (int)p.wblk[0] : 16,
-                                 (ex.pivoting && np <= kFusedRows) ? 2 : 1};
+        const PanelExport ex0 = {ws.pt[0], ws.pt_bstride, 0, (int)p.wblk[0], p.fused(0) ? 2 : 1};
         hipLaunchKernelGGL(blocked_init_kernel, dim3((np + 255) / 256, (np + 15) / 16, batch), dim3(256), 0, stream,
                            d_a, p.n, np, p.ld, ws.mstride, ws.m0, ex0, ws.tstride, ws.orig, d_status);
     }
@@ -311,10 +262,9 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         return e;
     // plans with shared panels (multi-workgroup panels, pivoting only): every launch skips a matrix whose panel lost
     // a partner (SubpanelArgs::guard)
-    const bool shared_panels = p.multi_panel && ex.pivoting;
-    const int *guard = shared_panels ? d_status : nullptr;
+    const int *guard = p.shared_panels ? d_status : nullptr;
     unsigned panel_launches = 0;  // tags of the multi-workgroup panels' exchange granules: unique per launch
-    if (shared_panels) {  // no stale tag of an earlier call may match
+    if (p.shared_panels) {  // no stale tag of an earlier call may match
         if ((e = hipMemsetAsync(ws.xch, 0, (size_t)kXchGranules * sizeof(unsigned long long) * batch, stream)) != hipSuccess)
             return e;
         // A matrix that was given up is skipped by its panels from then on, so its row maps are no longer written --
@@ -325,13 +275,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         if ((e = hipMemsetAsync(ws.submap[0], 0, (size_t)((char *)ws.orig - (char *)ws.submap[0]), stream)) != hipSuccess)
             return e;
     }
-    // The strip(t) tiles follow each block sub-panel by sub-panel in the columns outside it -- unless the look-ahead
-    // is on: those columns are then still being written by the previous block's second-stream update while the
-    // block's panels run (the next block's columns too: half (A) of the previous block covered THIS block's), and
-    // the block's strips run in one launch at its end (gj_block_strip_kernel).  So do GPU-filling batches: there the
-    // strip(t) tiles (256-thread groups, one global round trip per 32 earlier steps) cost more than the one launch
-    // per block (measured 64 x 2048^2: 23.0 vs 21.7 ms).
-    const bool strips_at_end = lookahead || batch * ((np + 63) / 64) > 256;
+    const bool strips_at_end = p.part_strips_at_end[part];  // else the strip(t) tiles ride in the panel launches
     // what every sub-panel launch shares
     SubpanelArgs base = {};
     base.np = np; base.n = p.n; base.ld = p.ld; base.batch = batch;
@@ -347,16 +291,13 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
         const int kb = (C0 + p.bw <= np) ? p.bw : np - C0;
         int **rsb = &ws.rowsrc[2 * (blk & 1)];
         float *mf = ws.mf[blk & 1], *ub = ws.ub[blk & 1], *xs = ws.xs[blk & 1];
-        // sub-panel width of this block and of the next one (the no-pivot variant has no register-resident panel
-        // whose rows would limit it)
-        const int w = ex.pivoting ? (int)p.wblk[blk] : 16;
-        const int w_next = !ex.pivoting ? 16 : (blk + 1 < p.nblk) ? (int)p.wblk[blk + 1] : w;
+        // sub-panel width of this block and of the next one
+        const int w = p.wblk[blk];
+        const int w_next = (blk + 1 < p.nblk) ? (int)p.wblk[blk + 1] : w;
         const int S = kb / w;                                            // sub-panels of this block (even)
         // Fused mode: launch s = panel(s) || update(s-1), the panel applies update(s-1) to its own columns in a
-        // prologue.  It pays while the panel workgroup holds at most 2 rows per lane (measured: 2048^2 3.23 ->
-        // 3.06 ms, 1024^2 1.40 -> 1.27 ms); with more rows the prologue (rows x W x W fmaf on ONE CU) costs what
-        // the update launch did (4096^2: 8.9 -> 9.5 ms), so those blocks keep panel(s) and update(s) apart.
-        const bool fused = ex.pivoting && (np - C0) <= kFusedRows;
+        // prologue; the other blocks keep panel(s) and update(s) apart.
+        const bool fused = p.fused(blk);
         const int os_ntiles = strips_at_end ? 0 : (np - kb) / 64;
         float *x = cur, *y = oth;  // the block's panel columns alternate between the two copies
         // Each builder fills its own fields of a launch's arguments.  panel(s): sub-panel s's pivot steps.
@@ -381,8 +322,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
             A.orig = ws.orig;
             A.aux_out = ws.aux[s & 1];
             A.status = d_status;
-            const int prow = np - A.row_lo;  // rows the panel holds
-            A.ngroups = (shared_panels && prow > kPanelGroupRows) ? (prow + kPanelGroupRows - 1) / kPanelGroupRows : 1;
+            A.ngroups = p.panel_groups(np - A.row_lo);  // by the rows the panel holds
             A.xch = ws.xch;
             A.tag_base = ++panel_launches;
         };
@@ -391,8 +331,8 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
             A.u_c0 = C0 + t * w;
             A.C0 = C0; A.kb = kb;
             A.u_mt = ws.mt[t & 1];
-            A.u_rowsrc = ex.pivoting ? rsb[fused ? t & 1 : 0] : ws.orig;  // no pivoting: no row ever moves
-            A.u_submap = ex.pivoting ? ws.submap[t & 1] : ws.orig;
+            A.u_rowsrc = p.pivoting ? rsb[fused ? t & 1 : 0] : ws.orig;  // no pivoting: no row ever moves
+            A.u_submap = p.pivoting ? ws.submap[t & 1] : ws.orig;
             A.u_mf = mf;
         };
         // update(t): the columns of the block that are not sub-panel t's own
@@ -401,7 +341,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
             A.upd_on = 1;
             A.u_has_prev = fused && (t > 0);
             A.u_above_hi = A.u_has_prev ? A.u_c0 - w : A.u_c0;  // = the first row panel(t) held
-            A.u_panel_hi = ex.pivoting ? np : A.u_c0 + w;
+            A.u_panel_hi = p.pivoting ? np : A.u_c0 + w;
             A.x = x; A.y = y;
             A.u_gt = ws.gt[t & 1];
             A.u_pt_in = ws.pt[t % 3];
@@ -445,7 +385,7 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
                     panel(P, s);
                     if (with_strip) strip(P, t);
                     ProfScope ps(prof, KC_PANEL, stream);
-                    if (!ex.pivoting) {
+                    if (!p.pivoting) {
                         // the no-pivot variant: the W x W diagonal block alone (+ the strip tiles that ride with a panel)
                         launch_diag_panel(P, stream);
                     } else if ((e = dispatch_subpanel(p, w, P, stream)) != hipSuccess) {
@@ -461,10 +401,10 @@ hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, 
             const bool has_next = next < np;
             const int kb_next = has_next ? ((next + p.bw <= np) ? p.bw : np - next) : 0;
             // position after the block -> row index at its start
-            const int *rowsrc = ex.pivoting ? rsb[fused ? (S - 1) & 1 : 0] : ws.orig;
+            const int *rowsrc = p.pivoting ? rsb[fused ? (S - 1) & 1 : 0] : ws.orig;
             // the next block's first two sub-panels, fully updated, for its first two panels
             const PanelExport exn =
-                has_next ? PanelExport{ws.pt[0], ws.pt_bstride, next, w_next, (ex.pivoting && (np - next) <= kFusedRows) ? 2 : 1}
+                has_next ? PanelExport{ws.pt[0], ws.pt_bstride, next, w_next, p.fused(blk + 1) ? 2 : 1}
                          : no_export;
             const int copy = (x != oth) ? 1 : 0;
             if (pending_b) {  // this update reads all of `cur` and overwrites `oth`: the previous (B) must be done

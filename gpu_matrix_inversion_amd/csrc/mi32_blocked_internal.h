@@ -15,20 +15,12 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 // k-tile depth and waves/SIMD of the rank-bw update (mi32_rank_bw.h)
 static constexpr int kBwBK = 16;
 static constexpr int kBwWPS = 3;
-static constexpr int kMaxBW = 512;  // widest outer block (rows of the transposed panel Gk)
-
-static constexpr int kMaxW = 32;  // widest sub-panel (columns kept in registers)
-// A panel of more than kPanelGroupRows candidate rows is shared by up to kMaxPanelGroups workgroups (one CU
-// each, <= 4 rows per lane at 1024 threads) that exchange every step's local winner through global memory.
-static constexpr int kMaxPanelGroups = 4;
-static constexpr int kPanelGroupRows = 4096;
+// (kMaxBW, kMaxW, kMaxPanelGroups, kPanelGroupRows and kFusedRows: beside the route, mi32_internal.h)
 static constexpr int kXchGranules = 2 * kMaxPanelGroups * 32;  // 8-byte granules per matrix: [parity][group][32]
 // how long a workgroup of a shared panel waits for a partner's record before it gives the matrix up
 // (MI32_RUNTIME_ERROR, output poisoned with NaN): 0.25 s of the 100 MHz s_memrealtime clock
 static constexpr unsigned long long kPanelXchTimeoutTicks = 25000000ull;
 static constexpr int kAuxFloats = 2 * kMaxW * kMaxW;  // per matrix and sub-panel: what a panel leaves for the rows above the block
-// Fused launches exist for the panel geometries of at most kFusedRows rows (see "Fused mode" in blocked_invert).
-static constexpr int kFusedRows = 2048;
 
 // Where a wide kernel exports freshly computed columns for the panel workgroup: columns
 // [col, col + w * count) go to `count` consecutive compact panels (w columns each) starting at `base`.
@@ -155,28 +147,6 @@ static hipError_t with_constant(int v, F &&f)
     hipError_t e = hipErrorInvalidValue;
     (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
     return e;
-}
-
-// Panel-kernel geometry: NT threads hold the rows at or below the block x w columns in registers, rpt rows
-// each (1024 threads leave <= 128 VGPRs per lane, i.e. rpt * w <= 64 floats of slab).
-// Thread geometry of a panel launch that holds `nrows` rows: the smallest that fits (fewer waves and fewer
-// rows per lane both shorten a pivot step).
-inline void panel_geometry(const BlockedPlan &p, int nrows, int &nt, int &rpt)
-{
-    rpt = 1;
-    if (p.multi_panel && nrows > kPanelGroupRows) {  // shared by ceil(nrows / 4096) workgroups of 1024 x 4 rows
-        nt = 1024;
-        rpt = 4;
-        return;
-    }
-    if (nrows <= 256) nt = 256;
-    else if (nrows <= 512) nt = 512;
-    else {
-        nt = p.nthreads_panel;
-        while (rpt * nt < nrows) rpt *= 2;
-        // 2049 ... 3072 rows at 1024 threads: three rows per lane (a fourth, dead row costs every pivot step its issue)
-        if (nt == 1024 && rpt == 4 && 3 * nt >= nrows) rpt = 3;
-    }
 }
 
 // Raises a kernel's dynamic-LDS limit to `bytes`, once per device (function attributes are per device; any thread may

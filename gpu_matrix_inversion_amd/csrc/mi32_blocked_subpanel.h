@@ -125,7 +125,7 @@ extern "C" int mi32_debug_drop_panel_group(int enable)
 //  * panel(s) alone: the smallest thread geometry that holds its rows (fewer waves and fewer rows per lane both
 //    shorten a pivot step);
 //  * update(t) alone: 256-thread workgroups, one tile each.
-static hipError_t dispatch_subpanel(const BlockedPlan &p, int w, const SubpanelArgs &A0, hipStream_t stream)
+static hipError_t dispatch_subpanel(const BlockedRoute &p, int w, const SubpanelArgs &A0, hipStream_t stream)
 {
     SubpanelArgs A = A0;
     const int tiles = A.upd_on ? (A.kb / 64) * (p.np / 64) : 0;

@@ -90,11 +90,16 @@ int zeroed_status_buffer(mi32_context *h, int *d_status, int batch, int **out);
 
 // ---- launch planning (mi32_plan.hip) --------------------------------------------------------------------------------------
 int resolve_algo(const Settings &s, int n, size_t elem_bytes);
-mi32::BlockedPlan plan_blocked(const Settings &s, int n, int batch);
+bool blocked_supported(int n);  // fp32: the register-resident panel holds at most 16384 (padded) rows
+mi32::BlockedRoute plan_route(const Settings &s, int n, int batch, bool aux_stream, bool split_stream);
+// with what the context offers; a null handle plans as a fresh context does
+inline mi32::BlockedRoute route_of(const mi32_context *h, const Settings &s, int n, int batch)
+{
+    return plan_route(s, n, batch, !h || h->aux_stream, !h || h->split_stream);
+}
 int block_w64(const Settings &s);
 size_t ws_bytes_for(const Settings &s, int n, int batch, int algo);  // fp32
 void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive);
-bool split_batch(const Settings &s, int algo, int n, int batch);  // where the context has a second stream for it
 
 // An instance of the one-launch kernels: register-resident with `lanes` per member (8 ... 64), or workgroup-resident
 // with `rows_per_thread` (40 ... 64); the other field is 0.

@@ -21,38 +21,35 @@ static int one_launch_device(mi32_context *h, bool pivoting, const T *d_a, int n
     return hip_status(e, "kernel launch");
 }
 
-// how a blocked fp32 inversion of order n is enqueued on this context
-static BlockedExec blocked_exec(mi32_context *h, const Settings &s, int n)
+// the resources a blocked fp32 inversion of order n is enqueued with on this context
+static BlockedExec blocked_exec(mi32_context *h, int n)
 {
     BlockedExec ex;
     ex.stream = h->stream;
-    ex.aux = s.lookahead ? h->aux_stream : nullptr;
+    ex.aux = h->aux_stream;
     ex.events = h->la_events;
     ex.n_events = h->aux_stream ? 8 : 0;
     lookahead_geometry(h->cu_count, n, &ex.aux_workgroups, &ex.aux_exclusive);
     ex.prof = h->prof;
-    ex.pivoting = s.pivoting;
     return ex;
 }
 
-// The two halves of a split batch (split_batch of mi32_plan.hip), the second on the context's split stream; the
-// workspace holds one part per half (ws_bytes_for).
-static int blocked_invert_split(mi32_context *h, const BlockedPlan &p, const BlockedExec &ex, const float *d_a, float *d_inv,
-                                int batch, int *d_status)
+// The two parts of a split batch, the second on the context's split stream; the workspace holds one part per half
+// (ws_bytes_for).
+static int blocked_invert_split(mi32_context *h, const BlockedRoute &r, const BlockedExec &ex, const float *d_a, float *d_inv,
+                                int *d_status)
 {
-    const int b0 = (batch + 1) / 2, b1 = batch - b0;
-    const size_t mat = (size_t)p.n * p.n;
-    char *ws1 = (char *)h->ws.ptr + blocked_workspace_bytes(p, b0);
+    const int b0 = r.part_batch[0];
+    const size_t mat = (size_t)r.n * r.n;
+    char *ws1 = (char *)h->ws.ptr + blocked_workspace_bytes(r, b0);
     // the second stream joins here and is joined again at the end (events 0 and 1 are free: the
     // look-ahead, their other user, only runs for single matrices)
     MI32_HIP(hipEventRecord(h->la_events[0], h->stream));
     MI32_HIP(hipStreamWaitEvent(h->split_stream, h->la_events[0], 0));
-    BlockedExec ex0 = ex, ex1 = ex;
-    ex0.aux = ex1.aux = nullptr;
+    BlockedExec ex1 = ex;
     ex1.stream = h->split_stream;
-    hipError_t e = blocked_invert(p, d_a, d_inv, b0, d_status, h->ws.ptr, ex0);
-    if (e == hipSuccess)
-        e = blocked_invert(p, d_a + (size_t)b0 * mat, d_inv + (size_t)b0 * mat, b1, d_status + b0, ws1, ex1);
+    hipError_t e = blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex);
+    if (e == hipSuccess) e = blocked_invert(r, 1, d_a + (size_t)b0 * mat, d_inv + (size_t)b0 * mat, d_status + b0, ws1, ex1);
     MI32_HIP(hipEventRecord(h->la_events[1], h->split_stream));
     MI32_HIP(hipStreamWaitEvent(h->stream, h->la_events[1], 0));
     return hip_status(e, "kernel launch");
@@ -70,13 +67,10 @@ int inv_device(mi32_context *h, Settings s, const float *d_a, int n, int batch, 
     if (algo == MI32_ALGO_SWEEP)
         e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting);
     else {
-        const BlockedExec ex = blocked_exec(h, s, n);
-        const BlockedPlan p = plan_blocked(s, n, batch);
-        // (plans with panels shared by several workgroups are not split: those workgroups need whole CUs at the same
-        // time, which the other half's rank-bw grid would keep from them for the length of its launch)
-        if (h->split_stream && split_batch(s, algo, n, batch) && !p.multi_panel)
-            return blocked_invert_split(h, p, ex, d_a, d_inv, batch, d_status);
-        e = blocked_invert(p, d_a, d_inv, batch, d_status, h->ws.ptr, ex);
+        const BlockedRoute r = route_of(h, s, n, batch);
+        const BlockedExec ex = blocked_exec(h, n);
+        if (r.parts == 2) return blocked_invert_split(h, r, ex, d_a, d_inv, d_status);
+        e = blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex);
     }
     return hip_status(e, "kernel launch");
 }

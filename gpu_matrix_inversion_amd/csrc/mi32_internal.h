@@ -94,30 +94,78 @@ struct SweepPlan {
     int col_tiles;
 };
 
-struct BlockedPlan {
+// ---- the blocked fp32 path's route -------------------------------------------------------------------------------------
+static constexpr int kMaxBW = 512;  // widest outer block (rows of the transposed panel Gk)
+static constexpr int kMaxW = 32;    // widest sub-panel (columns kept in registers)
+// A panel of more than kPanelGroupRows candidate rows is shared by up to kMaxPanelGroups workgroups (one CU
+// each, <= 4 rows per lane at 1024 threads) that exchange every step's local winner through global memory.
+static constexpr int kMaxPanelGroups = 4;
+static constexpr int kPanelGroupRows = 4096;
+// Fused launches exist for the panel geometries of at most kFusedRows rows (see "Fused mode" in blocked_invert).
+static constexpr int kFusedRows = 2048;
+
+// How one blocked fp32 call runs.  Every decision of the path is taken once, by plan_route (mi32_plan.hip), from the
+// settings, the shape and the streams the context offers; blocked_invert and the launchers read it and decide nothing.
+struct BlockedRoute {
+    // ---- geometry
     int n;     // matrix order
     int np;    // padded order (multiple of 128), identity padding
     int ld;    // row stride of the working copies in floats (np + 64)
     int w;     // widest sub-panel allowed (what the caller asked for; 16 by default)
     int bw;    // outer block width
+    int nblk;
     int nthreads_panel;
     int rpt;   // rows per thread in the panel kernel when it holds all np rows
-    // Sub-panel width of every outer block.  The panel kernel keeps (rows at or below the block) x width
-    // floats in registers, so the first blocks of a large matrix use narrow sub-panels and the width grows
-    // as the elimination retires rows (16384 rows: 4, 8192: 8, 4096 and fewer: 16).
-    int nblk;
+    bool pivoting;  // false: the reference's no-pivot variant (the diagonal entry is every step's pivot)
+    // ---- per outer block
+    // Sub-panel width.  The panel kernel keeps (rows at or below the block) x width floats in registers, so the first
+    // blocks of a large matrix use narrow sub-panels and the width grows as the elimination retires rows (16384 rows:
+    // 4, 8192: 8, 4096 and fewer: 16).  Without pivoting there is no register-resident panel: 16 in every block.
     unsigned char wblk[128];
-    // more than 4096 candidate rows: the panel is shared by up to 4 workgroups instead of narrowing the
-    // sub-panels (small batches only: all of a panel's workgroups must be resident at the same time)
-    int multi_panel;
+    // Blocks from this one on run panel(s) || update(s-1) as one launch (nblk: none does; pivoting only).
+    int first_fused;
+    bool fused(int blk) const { return blk >= first_fused; }
+    // More than kPanelGroupRows candidate rows: the panel is shared by up to kMaxPanelGroups workgroups instead of
+    // narrowing the sub-panels (pivoting and small batches only: all of a panel's workgroups must be resident at the
+    // same time).  Every launch then skips a matrix whose panel lost a partner.
+    bool shared_panels;
+    // workgroups of a panel that holds `rows` rows (it changes inside a block: 8320 rows, 3 -> 2 at 8192)
+    int panel_groups(int rows) const { return shared_panels ? (rows + kPanelGroupRows - 1) / kPanelGroupRows : 1; }
+    // the rank-bw update of a block is cut in two and all but the next block's columns run on the second stream
+    bool lookahead;
+    // ---- parts: the whole batch on the main stream, or ceil(batch / 2) there and the rest on the split stream.  Both
+    // halves run with the blocking and the panels of the whole batch; a half never has the look-ahead.
+    int parts;
+    int part_batch[2];
+    // true: the block's strips in one launch at its end; false: they ride in the panel launches (decided per part)
+    bool part_strips_at_end[2];
 };
 
+// Thread geometry of a panel launch that holds `nrows` rows: NT threads hold the rows x w columns in registers, rpt
+// rows each (1024 threads leave <= 128 VGPRs per lane, i.e. rpt * w <= 64 floats of slab) -- the smallest that fits
+// (fewer waves and fewer rows per lane both shorten a pivot step).
+inline void panel_geometry(const BlockedRoute &r, int nrows, int &nt, int &rpt)
+{
+    rpt = 1;
+    if (r.panel_groups(nrows) > 1) {  // shared by ceil(nrows / 4096) workgroups of 1024 x 4 rows
+        nt = 1024;
+        rpt = 4;
+        return;
+    }
+    if (nrows <= 256) nt = 256;
+    else if (nrows <= 512) nt = 512;
+    else {
+        nt = r.nthreads_panel;
+        while (rpt * nt < nrows) rpt *= 2;
+        // 2049 ... 3072 rows at 1024 threads: three rows per lane (a fourth, dead row costs every pivot step its issue)
+        if (nt == 1024 && rpt == 4 && 3 * nt >= nrows) rpt = 3;
+    }
+}
+
 SweepPlan make_sweep_plan(int n);
-BlockedPlan make_blocked_plan(int n, int w, int bw, int batch);
-bool blocked_supported(int n);  // the register-resident panel holds at most 16384 (padded) rows
 
 size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes);
-size_t blocked_workspace_bytes(const BlockedPlan &p, int batch);
+size_t blocked_workspace_bytes(const BlockedRoute &r, int batch);  // of `batch` members (a whole call, or one part)
 
 // Enqueue a whole inversion on `stream`.  ws: workspace of at least the size
 // reported above, 256-byte aligned.
@@ -311,8 +359,9 @@ template <typename T>
 hipError_t workgroup_vsolve(int rows_per_thread, const VsolveArgs<T> &v, int first, int count, hipStream_t stream,
                             Profiler *prof, bool pivoting);
 
-// streams/events a blocked inversion is enqueued with: `aux` (may be null) carries the look-ahead half
-// of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel phase done"
+// The resources a blocked inversion is enqueued with (what to do with them is the route's business): `aux` carries the
+// look-ahead half of each rank-bw update; events[0 .. n/2) mark "second-stream work done", events[n/2 .. n) "panel
+// phase done"
 struct BlockedExec {
     hipStream_t stream = nullptr;
     hipStream_t aux = nullptr;
@@ -321,9 +370,9 @@ struct BlockedExec {
     int aux_workgroups = 0;  // grid of the persistent look-ahead kernel: CUs minus the ones kept free
     bool aux_exclusive = false;  // its workgroups take a whole CU's LDS: nothing of the main stream shares their CUs
     Profiler *prof = nullptr;
-    bool pivoting = true;  // false: the reference's no-pivot variant (the diagonal entry is every step's pivot)
 };
-hipError_t blocked_invert(const BlockedPlan &p, const float *d_a, float *d_inv, int batch, int *d_status, void *ws,
+// enqueues part `part` of the route: its r.part_batch[part] members at d_a / d_inv / d_status, in the workspace ws
+hipError_t blocked_invert(const BlockedRoute &r, int part, const float *d_a, float *d_inv, int *d_status, void *ws,
                           const BlockedExec &ex);
 // getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths (mi32_sweep.hip).  Working
 // column c holds inverse column orig[c].  orig and invp hold np entries per matrix, np apart.

@@ -24,22 +24,113 @@ int resolve_algo(const Settings &s, int n, size_t elem_bytes)
     return algo;
 }
 
-BlockedPlan plan_blocked(const Settings &s, int n, int batch)
+// (the update tiles address a matrix with 32-bit byte offsets from its base, so a working copy must stay below 4 GiB:
+// mi32_blocked.hip asserts it for this bound)
+bool blocked_supported(int n) { return n > 0 && ((n + 127) & ~127) <= 16384; }
+
+// A knob whose every set value counts, the empty string included: atoi of it (MI32_MULTI_PANEL, MI32_LOOKAHEAD_MIN;
+// env_int reads the empty string as unset).
+static bool env_atoi(const char *name, int *value)
 {
-    const int w = s.panel_w ? s.panel_w : env_int("MI32_PANEL_W", 0);
+    const char *e = std::getenv(name);
+    if (e) *value = std::atoi(e);
+    return e != nullptr;
+}
+
+// THE route of a blocked fp32 call: every decision of the path, each rule once.  aux_stream / split_stream: what the
+// context offers (a call without one plans as a fresh context does, with both).
+BlockedRoute plan_route(const Settings &s, int n, int batch, bool aux_stream, bool split_stream)
+{
+    BlockedRoute r = {};
+    const double elems = (double)batch * (double)n * (double)n;
+    // ---- geometry
+    r.n = n;
+    r.np = (n + 127) & ~127;
+    // Row stride: np + 64 floats (256 B): keeps rows 256-B aligned and avoids a power-of-two stride.
+    r.ld = r.np + 64;
+    r.pivoting = s.pivoting;
+    int nt = (r.np >= 2048) ? 1024 : 512;
+    int rpt = 1;
+    while (rpt * nt < r.np) rpt *= 2;
+    if (rpt > 8 && nt == 512) {  // no 512-thread instance holds more than 8 rows per lane: use 1024
+        nt = 1024;
+        rpt = 1;
+        while (rpt * nt < r.np) rpt *= 2;
+    }
+    r.nthreads_panel = nt;
+    r.rpt = rpt;
+    int w = s.panel_w ? s.panel_w : env_int("MI32_PANEL_W", 0);
+    if (w <= 0) w = 16;  // 32 is selectable where it fits, but measured slower (4.6 vs 4.2 ms at 2048^2)
+    r.w = w = (w >= 32) ? 32 : (w >= 16) ? 16 : (w >= 8 ? 8 : 4);
     int bw = s.block_w ? s.block_w : env_int("MI32_BLOCK_W", 0);
     if (bw == 0) {
         // A single matrix is bound by the pivot chain and bw = 256 gives the rank-bw update its best
         // arithmetic intensity.  A batch that fills the GPU is bound by the HBM traffic of the in-block
         // updates (np x bw re-written per sub-panel): bw = 128 halves it (measured 64 x 2048^2:
         // 23.0 ms vs 24.7 ms; single 4096^2: 11.4 ms vs 11.2 ms).
-        const double elems = (double)batch * (double)n * (double)n;
         bw = (batch >= 8 && elems >= 64.0 * 1024.0 * 1024.0) ? 128 : 256;
         // (Rounds 1-2 ran N > 14336 with bw = 512 for the rank-bw update's sake: 120 instead of 114 TFLOP/s.  With the
         // pivot-row strips of round 3 an in-block update tile costs more and there are twice as many per sub-panel at
         // 512: 16384^2 122 ms at 256, 126 at 384, 140 at 512; 12288^2 65.5 vs 75.9; 8192^2 33.9 vs 38.0.)
     }
-    return make_blocked_plan(n, w, bw, batch);
+    if (bw <= 0) bw = 256;
+    bw = (bw + 127) & ~127;
+    if (bw > kMaxBW) bw = kMaxBW;
+    if (bw > r.np) bw = r.np;
+    r.bw = bw;
+    r.nblk = (r.np + bw - 1) / bw;
+    // ---- shared panels need every workgroup of a panel resident at once and a whole CU each; with the look-ahead
+    // kernel holding all but 16 (32 below 8192 rows) CUs that is safe for a few matrices (MI32_MULTI_PANEL=0 turns
+    // them off).  The no-pivot variant has no panel search to share: it ignores the flag, but a batch it is set for
+    // is never split.
+    bool multi_panel = nt == 1024 && r.np > kPanelGroupRows && batch * kMaxPanelGroups <= 16;
+    int knob;
+    if (env_atoi("MI32_MULTI_PANEL", &knob)) multi_panel = multi_panel && knob != 0;
+    r.shared_panels = multi_panel && s.pivoting;
+    // ---- per outer block
+    for (int b = 0; b < r.nblk && b < 128; ++b) {
+        int bnt, brpt;
+        panel_geometry(r, r.np - b * bw, bnt, brpt);
+        int wmax = ((bnt == 1024) ? 64 : 128) / brpt;  // floats of slab per thread
+        if (wmax > kMaxW) wmax = kMaxW;
+        int wb = w < wmax ? w : wmax;                  // wmax < 4 (np > 16384) is rejected by blocked_supported()
+        wb = (wb >= 32) ? 32 : (wb >= 16) ? 16 : (wb >= 8 ? 8 : 4);
+        // (the no-pivot variant has no register-resident panel whose rows would limit the width)
+        r.wblk[b] = s.pivoting ? (unsigned char)wb : 16;
+    }
+    // Fused mode pays while the panel workgroup holds at most 2 rows per lane (measured: 2048^2 3.23 -> 3.06 ms,
+    // 1024^2 1.40 -> 1.27 ms); with more rows the prologue (rows x W x W fmaf on ONE CU) costs what the update launch
+    // did (4096^2: 8.9 -> 9.5 ms).  The first block with at most kFusedRows rows:
+    r.first_fused = !s.pivoting ? r.nblk : r.np <= kFusedRows ? 0 : (r.np - kFusedRows + bw - 1) / bw;
+    // ---- look-ahead: it pays when the GPU is otherwise idle during the panel phase: a single large matrix
+    // (measured in round 1: 8192^2 51 -> 45 ms, 16384^2 399 -> 330 ms, 4096^2 11.2 -> 11.0 ms, 2048^2 4.2 -> 4.4 ms; with
+    // the half on CUs of its own, round 2: 3584^2 7.39 -> 7.00 ms, 3072^2 5.79 -> 5.63, 2560^2 4.32 -> 4.34, 2048^2 3.01 -> 3.14)
+    // Round 3 (reference-order arithmetic: the pivot rows' strip per block sits between the block's last panel and its
+    // rank-bw update, and rides in the panel launches only WITHOUT the second stream), with / without:
+    // 4096^2 10.23 / 10.09, 4352^2 11.50 / 11.66, 5120^2 15.02 / 15.79, 8192^2 34.0 / 37.1 -> on above 4096 padded rows.
+    int la_min = 4096 + 1;
+    if (env_atoi("MI32_LOOKAHEAD_MIN", &knob)) la_min = knob > 2048 ? knob : 2048;
+    r.lookahead = s.lookahead && aux_stream && batch == 1 && r.np >= la_min;
+    // ---- parts.  A GPU-filling batch is run as two halves on the context's two streams: the MFMA-bound rank-bw
+    // launches of one half overlap the latency / HBM-bound sub-panel launches of the other (64 x 2048^2: 18.5 -> 17.4 ms;
+    // three or four parts lose; round 3: 8 x 4096^2 23.6 -> 22.1 ms, 4 x 4096^2 15.7 -> 15.0: from four matrices on).
+    // Both halves use the blocking of the whole batch, so a matrix's result does not depend on the split;
+    // mi32_set_lookahead(h, 0) turns the second stream off altogether.  Plans with the shared-panel flag are not split:
+    // a panel's workgroups need whole CUs at the same time, which the other half's rank-bw grid would keep from them
+    // for the length of its launch.
+    const bool split = split_stream && s.lookahead && batch >= 4 && elems >= 64.0 * 1024.0 * 1024.0 &&
+                       env_int("MI32_BATCH_SPLIT", 1) != 0 && !multi_panel;
+    r.parts = split ? 2 : 1;
+    r.part_batch[0] = split ? (batch + 1) / 2 : batch;
+    r.part_batch[1] = batch - r.part_batch[0];
+    // The strip(t) tiles follow each block sub-panel by sub-panel in the columns outside it -- unless the look-ahead
+    // is on: those columns are then still being written by the previous block's second-stream update while the
+    // block's panels run (the next block's columns too: half (A) of the previous block covered THIS block's), and
+    // the block's strips run in one launch at its end (gj_block_strip_kernel).  So do GPU-filling batches: there the
+    // strip(t) tiles (256-thread groups, one global round trip per 32 earlier steps) cost more than the one launch
+    // per block (measured 64 x 2048^2: 23.0 vs 21.7 ms).  Each part counts its own tiles.
+    for (int i = 0; i < r.parts; ++i) r.part_strips_at_end[i] = r.lookahead || r.part_batch[i] * ((r.np + 63) / 64) > 256;
+    return r;
 }
 
 int block_w64(const Settings &s) { return s.block_w ? s.block_w : env_int("MI32_BLOCK_W64", 0); }
@@ -50,8 +141,8 @@ size_t ws_bytes_for(const Settings &s, int n, int batch, int algo)
     if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) a = 0;  // no working copy: only the residual check needs a workspace
     else if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
     else {
-        const BlockedPlan p = plan_blocked(s, n, batch);
-        // a batch that may be split in two halves (mi32_inv_device) carves one workspace per half
+        const BlockedRoute p = plan_route(s, n, batch, true, true);
+        // a batch that may be split in two halves carves one workspace per half -- reserved whether or not this call splits
         a = blocked_workspace_bytes(p, (batch + 1) / 2) + blocked_workspace_bytes(p, batch - (batch + 1) / 2);
         const size_t whole = blocked_workspace_bytes(p, batch);
         if (whole > a) a = whole;
@@ -87,17 +178,6 @@ void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive)
     if (reserve > cus - 1) reserve = cus - 1;
     *workgroups = cus - reserve;
     *exclusive = excl;
-}
-
-// A GPU-filling batch of the blocked path is run as two halves on the context's two streams: the MFMA-bound
-// rank-bw launches of one half overlap the latency / HBM-bound sub-panel launches of the other (64 x 2048^2:
-// 18.5 -> 17.4 ms; three or four parts lose; round 3: 8 x 4096^2 23.6 -> 22.1 ms, 4 x 4096^2 15.7 -> 15.0: from four
-// matrices on).  Both halves use the blocking of the whole batch, so a matrix's
-// result does not depend on the split; mi32_set_lookahead(h, 0) turns the second stream off altogether.
-bool split_batch(const Settings &s, int algo, int n, int batch)
-{
-    return algo == MI32_ALGO_BLOCKED && s.lookahead && batch >= 4 && (double)batch * n * n >= 64.0 * 1024.0 * 1024.0 &&
-           env_int("MI32_BATCH_SPLIT", 1) != 0;
 }
 
 // ---- variable-size batches ---------------------------------------------------------------------------------------
@@ -230,7 +310,7 @@ int mi32_resolve_algo(mi32_handle_t h, int n, int /*batch*/) { return resolve_al
 int mi32_resolve_blocking(mi32_handle_t h, int n, int batch, int *panel_width, int *block_width)
 {
     if (n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
-    const BlockedPlan p = plan_blocked(settings_of(h), n, batch);
+    const BlockedRoute p = route_of(h, settings_of(h), n, batch);
     if (panel_width) *panel_width = p.w;
     if (block_width) *block_width = p.bw;
     return MI32_OK;
@@ -239,9 +319,24 @@ int mi32_resolve_blocking(mi32_handle_t h, int n, int batch, int *panel_width, i
 int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, int capacity, int *nblocks)
 {
     if (n <= 0 || batch <= 0 || capacity < 0 || (capacity > 0 && !widths)) return MI32_BAD_SHAPE;
-    const BlockedPlan p = plan_blocked(settings_of(h), n, batch);
+    // (the widths of the pivoting plan whatever the handle's pivoting: the no-pivot variant runs 16 in every block)
+    Settings s = settings_of(h);
+    s.pivoting = true;
+    const BlockedRoute p = route_of(h, s, n, batch);
     if (nblocks) *nblocks = p.nblk;
-    for (int b = 0; b < p.nblk && b < capacity; ++b) widths[b] = p.wblk[b];
+    for (int b = 0; b < p.nblk && b < capacity && b < 128; ++b) widths[b] = p.wblk[b];
+    return MI32_OK;
+}
+
+int mi32_resolve_route(mi32_handle_t h, int n, int batch, mi32_route_t *route, int *panel_groups, int capacity)
+{
+    if (n <= 0 || batch <= 0 || !blocked_supported(n) || !route || capacity < 0 || (capacity > 0 && !panel_groups))
+        return MI32_BAD_SHAPE;
+    const BlockedRoute r = route_of(h, settings_of(h), n, batch);
+    *route = mi32_route_t{r.np, r.bw, r.nblk, r.shared_panels, r.lookahead, r.parts,
+                          {r.part_batch[0], r.part_batch[1]},
+                          {r.part_strips_at_end[0], r.part_strips_at_end[1]}, r.first_fused};
+    for (int b = 0; panel_groups && b < r.nblk && b < capacity; ++b) panel_groups[b] = r.panel_groups(r.np - b * r.bw);
     return MI32_OK;
 }
 

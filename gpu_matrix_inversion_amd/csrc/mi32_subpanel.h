@@ -41,7 +41,7 @@ __global__ __launch_bounds__(NT) void gj_subpanel_kernel(SubpanelArgs A)
     ostrip_body<W>(A, u * (NT / 256) + grp, sp_smem + (size_t)grp * sizeof(OStripShared<W>), threadIdx.x & 255);
 }
 
-// The instances of gj_subpanel_kernel: every panel geometry make_blocked_plan can give a block -- one row per lane at
+// The instances of gj_subpanel_kernel: every panel geometry plan_route can give a block -- one row per lane at
 // 256 threads; at 512 threads at most 8 rows per lane and 128 floats of slab, at 1024 threads at most 64 floats
 // (three rows per lane: at 1024 threads only).
 constexpr bool subpanel_instance(int nt, int rpt, int w, bool fused)

@@ -322,6 +322,23 @@ int mi32_resolve_blocking(mi32_handle_t h, int n, int batch, int *panel_width, i
  * first blocks of a large matrix use narrower sub-panels): *nblocks receives the number of outer blocks,
  * widths[0 .. min(capacity, *nblocks)) their sub-panel widths. */
 int mi32_resolve_panel_widths(mi32_handle_t h, int n, int batch, int *widths, int capacity, int *nblocks);
+/* How a blocked fp32 call of this shape would run on this handle, answered without a device (h may be NULL: what a
+ * fresh context does) from the settings, the environment and the shape -- the one description the library itself
+ * enqueues the call from.  The widths of the sub-panels: mi32_resolve_panel_widths. */
+typedef struct {
+    int np, block_width, nblocks; /* padded order (multiple of 128), outer block width, number of outer blocks */
+    int shared_panels;            /* 1: panels of more than 4096 rows are shared by several workgroups */
+    int lookahead;                /* 1: all but the next block's columns of a rank-bw update run on the second stream */
+    int parts;                    /* 1 or 2: a batch split in two halves runs them on two streams */
+    int part_batch[2];            /* members per part (second 0 when parts == 1) */
+    int part_strips_at_end[2];    /* 1: the block's strips in one launch at its end; 0: they ride in the panel launches */
+    int first_fused_block;        /* blocks from this one on run panel and in-block update as one launch; nblocks when
+                                   * no block is fused */
+} mi32_route_t;
+/* panel_groups[0 .. min(capacity, nblocks)) (may be NULL with capacity 0): workgroups per panel at the start of each
+ * outer block.  MI32_BAD_SHAPE for n <= 0, batch <= 0, an order the blocked path does not take (more than 16384
+ * padded rows) or a NULL route. */
+int mi32_resolve_route(mi32_handle_t h, int n, int batch, mi32_route_t *route, int *panel_groups, int capacity);
 /* The register-resident path (MI32_ALGO_RESIDENT), answered without a device (h may be NULL): *lanes_per_matrix =
  * lanes that hold one matrix of this order (8 / 16 / 32 / 64 for 1 <= n <= 64, 0 above: RESIDENT falls back
  * there), *max_order = the largest order it takes (64).  elem_bytes: 4 (fp32) or 8 (fp64); anything else, or

@@ -143,12 +143,6 @@ def expected_inverse(oracle, member):
     return x.reshape(n, n) if member.transform is None else apply_variant(x, member.transform)
 
 
-def would_split(n, batch):
-    """split_batch of mi32_plan.hip, for plans without shared panels: from four matrices and 64 Mi elements on the
-    batch runs as two halves, ceil(batch / 2) and the rest, on two streams."""
-    return batch >= 4 and batch * n * n >= 64 * 1024 * 1024
-
-
 # ---- the plans the GPU tests rely on (mi32_resolve_blocking / mi32_resolve_panel_widths) --------------------------
 # (n, batch, MI32_MULTI_PANEL or None, block width, sub-panel width of every block)
 PLANS = [
@@ -162,16 +156,3 @@ PLANS = [
     (N_WIDE, 2, None, 256, [16] * 33),
     (N_WIDE, 5, None, 256, [4] + [8] * 16 + [16] * 16),  # what the single-matrix case above stands in for
 ]
-
-
-def shared_panel_groups(n, bw, block):
-    """Workgroups per shared panel at the start of outer block ``block``: ceil(candidate rows / 4096)."""
-    rows = -(-n // 128) * 128 - block * bw
-    return -(-rows // 4096)
-
-
-def strips_ride_in_panel_launches(n, batch):
-    """blocked_invert: a batch's strip tiles follow each sub-panel while batch * ceil(np / 64) <= 256 (a single matrix
-    above 4096 rows runs the look-ahead, which moves them to the block's end whatever the count)."""
-    np_ = -(-n // 128) * 128
-    return batch > 1 and batch * (-(-np_ // 64)) <= 256

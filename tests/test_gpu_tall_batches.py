@@ -55,7 +55,9 @@ def test_shared_panels_with_a_batch_index_bit_identical_to_oracle(oracle, inv_bl
     member of every batch but the first is a 2^40-scaled variant (full division in its strips, beside a member on the
     fast one), and a variant's winning rows sit in other workgroups than its base's at the same step."""
     assert inv_blocked.resolved_panel_widths(N, batch) == ALL_16 and inv_blocked.resolved_blocking(N, batch) == (16, 256)
-    assert C.strips_ride_in_panel_launches(N, batch) == (batch < 4)
+    route, groups = inv_blocked.resolved_route(N, batch)
+    assert route["shared_panels"] == 1 and route["parts"] == 1 and groups[:2] == [2, 1]
+    assert (route["part_strips_at_end"][0] == 0) == (batch < 4)
     members = C.tall_batch(N, batch, rotate)
     x, st = run_batch(inv_blocked, [m.matrix for m in members])
     assert st == [0] * batch
@@ -78,7 +80,8 @@ def test_three_workgroup_panels_in_a_batch_of_two_bit_identical_to_oracle_digest
     dig, a = wide
     n = C.N_WIDE
     assert inv_blocked.resolved_panel_widths(n, 2) == [16] * 33
-    assert [C.shared_panel_groups(n, 256, b) for b in (0, 1, 17)] == [3, 2, 1]
+    route, groups = inv_blocked.resolved_route(n, 2)
+    assert route["shared_panels"] == 1 and [groups[b] for b in (0, 1, 17)] == [3, 2, 1]
     a1, t = C.variant(a, 8200, -9)
     x, st = run_batch(inv_blocked, [a, a1])
     assert st == [0, 0]
@@ -133,7 +136,7 @@ def test_a_lost_partner_poisons_its_own_member_only(oracle, inv_blocked):
     NaN-filled inverse for member 1 -- and status 0 and the oracle's bits for member 0, whose panels ran beside it in
     every one of those launches.  The next call on the same handle is healthy for both.  (The documented time-out
     path, run once.)"""
-    assert inv_blocked.resolved_panel_widths(N, 2) == ALL_16 and C.shared_panel_groups(N, 256, 0) == 2
+    assert inv_blocked.resolved_panel_widths(N, 2) == ALL_16 and inv_blocked.resolved_route(N, 2)[1][0] == 2
     members = C.tall_batch(N, 2)
     lib = _lib.load()
     lib.mi32_debug_drop_panel_group(1)
@@ -160,7 +163,8 @@ def test_batches_beyond_shared_panels_split_and_unsplit_bit_identical_to_oracle(
     widths = inv_blocked.resolved_panel_widths(N, batch)
     assert widths == [8] + [16] * (len(widths) - 1) and len(widths) == -(-4224 // bw)
     assert inv_blocked.resolved_blocking(N, batch) == (16, bw)
-    assert C.would_split(N, batch)
+    route = inv_blocked.resolved_route(N, batch)[0]
+    assert (route["shared_panels"], route["parts"], route["part_batch"]) == (0, 2, [(batch + 1) // 2, batch // 2])
     members = C.tall_batch(N, batch)
     mats = [m.matrix for m in members]
     for b in singular:
@@ -169,6 +173,7 @@ def test_batches_beyond_shared_panels_split_and_unsplit_bit_identical_to_oracle(
         assert min(singular) < (batch + 1) // 2 <= max(singular)
     x_split, st_split = run_batch(inv_blocked, mats)
     monkeypatch.setenv("MI32_BATCH_SPLIT", "0")   # read per call
+    assert inv_blocked.resolved_route(N, batch)[0]["parts"] == 1
     x_one, st_one = run_batch(inv_blocked, mats)
     want = [2 if b in singular else 0 for b in range(batch)]
     assert st_split == want and st_one == want
@@ -196,3 +201,16 @@ def test_no_pivot_batch_above_4096_rows_bit_identical_to_oracle(oracle):
     want = oracle.matrix_inversion_no_pivots(a, N)
     assert canonical_bytes(x[0].cpu().numpy()) == canonical_bytes(want)
     assert canonical_bytes(x[1].cpu().numpy()) == canonical_bytes(C.apply_variant_nopivot(want, t))
+
+
+# ---- h. the route a live context reports ---------------------------------------------------------------------------
+def test_a_context_routes_as_the_null_handle_does_until_its_second_stream_is_turned_off(inv_blocked):
+    """mi32_resolve_route with a handle: a fresh context has both streams, as the null handle assumes
+    (tests/test_tall_batch_cases.py pins those answers); mi32_set_lookahead(h, 0) takes the look-ahead and the split
+    away.  No inversion runs."""
+    assert inv_blocked.resolved_route(N, 2) == _lib.resolve_route(None, N, 2)
+    assert inv_blocked.resolved_route(N, 1)[0]["lookahead"] == 1 and inv_blocked.resolved_route(N, 5)[0]["parts"] == 2
+    inv_blocked.set_lookahead(False)
+    assert inv_blocked.resolved_route(N, 1)[0]["lookahead"] == 0
+    off = inv_blocked.resolved_route(N, 5)[0]
+    assert (off["parts"], off["part_batch"]) == (1, [5, 0])

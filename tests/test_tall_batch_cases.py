@@ -1,6 +1,6 @@
 """CPU proof of tests/tall_batch_cases.py, before the GPU sees any of it: the two transform identities hold bit for bit
-on the oracle, and the library plans the shapes of tests/test_gpu_tall_batches.py the way those tests need -- asked
-through the C ABI with a null handle, the plan code needs no device.  No tolerance: bytes and literal plan values."""
+on the oracle, and the library plans and routes the shapes of tests/test_gpu_tall_batches.py the way those tests need
+-- asked through the C ABI with a null handle, the plan code needs no device.  No tolerance: bytes and literal plan values."""
 import ctypes
 
 import numpy as np
@@ -122,30 +122,104 @@ def test_plans_the_gpu_tests_rely_on(monkeypatch, n, batch, multi, bw, widths):
     assert got == widths and len(got) == -(-(-(-n // 128) * 128) // bw)
 
 
+ROUTE_KNOBS = ("MI32_PANEL_W", "MI32_BLOCK_W", "MI32_MULTI_PANEL", "MI32_ALGO", "MI32_LOOKAHEAD_MIN", "MI32_BATCH_SPLIT")
+END, RIDE = 1, 0   # mi32_route_t.part_strips_at_end
+
+
+def _route(n, batch):
+    """(np, bw, blocks, shared, look-ahead, members per part, strips per part, first fused block) and the workgroups
+    per panel by block, of mi32_resolve_route with a null handle."""
+    r, groups = _lib.resolve_route(None, n, batch)
+    assert r["parts"] in (1, 2) and len(groups) == r["nblocks"]
+    assert r["part_batch"][r["parts"]:] == [0] * (2 - r["parts"]) and sum(r["part_batch"]) == batch
+    return ((r["np"], r["block_width"], r["nblocks"], r["shared_panels"], r["lookahead"], r["part_batch"][:r["parts"]],
+             r["part_strips_at_end"][:r["parts"]], r["first_fused_block"]), groups)
+
+
 def test_every_route_above_4096_rows_is_reached_by_a_case(monkeypatch):
-    """The routing table of DESIGN.md ("Routing above 4096 rows"), row by row, as the thresholds in the code give it
-    for the shapes of tests/test_gpu_tall_batches.py."""
-    for name in ("MI32_PANEL_W", "MI32_BLOCK_W", "MI32_MULTI_PANEL", "MI32_ALGO"):
+    """The routing table of DESIGN.md ("Routing above 4096 rows"), row by row, as the library itself routes the shapes
+    of tests/test_gpu_tall_batches.py: asked of mi32_resolve_route, which answers from the one description the launcher
+    runs a call from.  Literal values, no device."""
+    for name in ROUTE_KNOBS:
         monkeypatch.delenv(name, raising=False)
     tall, wide = C.N_TALL, C.N_WIDE
-    shared = lambda n, b: set(_plan(n, b)[2]) == {16}   # noqa: E731  (all-16 above 4096 rows: shared panels are on)
-    # batch 2 ... 4: shared panels with a batch index; strips ride for 2 and 3, run at the block's end for 4
-    assert all(shared(tall, b) for b in (1, 2, 3, 4)) and not shared(tall, 5)
-    assert [C.strips_ride_in_panel_launches(tall, b) for b in (2, 3, 4)] == [True, True, False]
-    assert C.shared_panel_groups(tall, 256, 0) == 2 and C.shared_panel_groups(tall, 256, 1) == 1
-    # three workgroups per panel, going 3 -> 2 -> 1 inside the FIRST block (8320, 8192 and 4096 rows are the edges)
-    assert shared(wide, 2) and not C.strips_ride_in_panel_launches(wide, 2)
-    assert C.shared_panel_groups(wide, 256, 0) == 3 and -(-(8320 - 128) // 4096) == 2 and -(-(8320 - 240) // 4096) == 2
-    assert [C.shared_panel_groups(wide, 256, b) for b in (1, 16, 17)] == [2, 2, 1]
-    # batch >= 5: one workgroup per panel, and the batch is split over two streams; a batch of 4 is large enough to
-    # be split but keeps its shared panels, which are never split
-    assert [C.would_split(tall, b) for b in (2, 3, 4, 5, 8)] == [False, False, True, True, True]
-    assert _plan(tall, 5)[2][0] == 8 and _plan(tall, 5)[1] == 256
+    # batch 1: shared panels and the look-ahead, which moves the strips to the block's end.  Two workgroups per panel
+    # in the first block only; blocks 9 ... 16 hold at most 2048 rows
+    assert _route(tall, 1) == ((4224, 256, 17, 1, 1, [1], [END], 9), [2] + [1] * 16)
+    # batch 2 ... 4: shared panels with a batch index, no look-ahead; strips ride for 2 and 3 (132 and 198 tiles), run
+    # at the block's end for 4 (264) -- which is large enough to be split but keeps its shared panels, never split
+    assert _route(tall, 2) == ((4224, 256, 17, 1, 0, [2], [RIDE], 9), [2] + [1] * 16)
+    assert _route(tall, 3) == ((4224, 256, 17, 1, 0, [3], [RIDE], 9), [2] + [1] * 16)
+    assert _route(tall, 4) == ((4224, 256, 17, 1, 0, [4], [END], 9), [2] + [1] * 16)
+    # batch >= 5: one workgroup per panel (8 rows per lane: W = 8 in the first block), and the batch is split over two
+    # streams; each half counts its own strip tiles
+    assert _route(tall, 5) == ((4224, 256, 17, 0, 0, [3, 2], [RIDE, RIDE], 9), [1] * 17)
+    assert _plan(tall, 5) == (16, 256, [8] + [16] * 16)
+    assert _route(tall, 7) == ((4224, 256, 17, 0, 0, [4, 3], [END, RIDE], 9), [1] * 17)
     # batch >= 8 and 64 Mi elements: block width 128
+    assert _route(tall, 8) == ((4224, 128, 33, 0, 0, [4, 4], [END, END], 17), [1] * 33)
     assert _plan(tall, 7)[1] == 256 and _plan(tall, 8)[1] == 128
-    # above 8192 rows without shared panels: 16 rows per lane, W = 4 -- a batch of 5 and the single matrix with
-    # MI32_MULTI_PANEL=0 that stands in for it plan the same widths
+    # three workgroups per panel, going 3 -> 2 -> 1 (8320, 8192 and 4096 rows are the edges): 3 in block 0 only, 2 up
+    # to block 16 (4224 rows), 1 from block 17 (3968 rows) on
+    groups_wide = [3] + [2] * 16 + [1] * 16
+    assert _route(wide, 1) == ((8320, 256, 33, 1, 1, [1], [END], 25), groups_wide)
+    assert _route(wide, 2) == ((8320, 256, 33, 1, 0, [2], [END], 25), groups_wide)       # 260 tiles
+    assert [groups_wide[b] for b in (0, 1, 16, 17)] == [3, 2, 2, 1]
+    assert -(-(8320 - 128) // 4096) == 2 and -(-(8320 - 240) // 4096) == 2   # 3 -> 2 inside the FIRST block
+    assert all(set(_plan(n, b)[2]) == {16} for n, b in ((tall, 1), (tall, 2), (tall, 3), (tall, 4), (wide, 1), (wide, 2)))
+    # above 8192 rows without shared panels: 16 rows per lane, W = 4
+    assert _route(wide, 5) == ((8320, 256, 33, 0, 0, [3, 2], [END, END], 25), [1] * 33)
     five = _plan(wide, 5)
+    assert five == (16, 256, [4] + [8] * 16 + [16] * 16)
+    # up to 4096 rows: no shared panels, no look-ahead, the strips ride; four matrices are 2^26 elements and split
+    assert _route(4096, 1) == ((4096, 256, 16, 0, 0, [1], [RIDE], 8), [1] * 16)
+    assert _route(4096, 4) == ((4096, 256, 16, 0, 0, [2, 2], [RIDE, RIDE], 8), [1] * 16)   # 128 tiles each
+    # MI32_BATCH_SPLIT=0: one part, which counts all 330 tiles
+    monkeypatch.setenv("MI32_BATCH_SPLIT", "0")
+    assert _route(tall, 5) == ((4224, 256, 17, 0, 0, [5], [END], 9), [1] * 17)
+    monkeypatch.delenv("MI32_BATCH_SPLIT")
+    # MI32_MULTI_PANEL=0: the single matrix that stands in for a batch of five plans the same widths and keeps its
+    # look-ahead
     monkeypatch.setenv("MI32_MULTI_PANEL", "0")
-    assert _plan(wide, 1) == five and five[2][0] == 4
+    assert _route(wide, 1) == ((8320, 256, 33, 0, 1, [1], [END], 25), [1] * 33)
+    assert _plan(wide, 1) == five
     assert _plan(tall, 1)[2] == _plan(tall, 5)[2] == [8] + [16] * 16
+
+
+def test_each_routing_threshold_has_a_shape_on_either_side(monkeypatch):
+    """One (n, batch) on each side of every threshold of plan_route, at the smallest shape that has the edge."""
+    for name in ROUTE_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    route = lambda n, batch: _lib.resolve_route(None, n, batch)[0]   # noqa: E731
+    # fused blocks: at most 2048 rows
+    assert route(2048, 1)["first_fused_block"] == 0
+    assert (route(2176, 1)["np"], route(2176, 1)["first_fused_block"], route(2176, 1)["nblocks"]) == (2176, 1, 9)
+    # shared panels and the look-ahead: more than 4096 padded rows; shared panels up to four matrices
+    lo, hi = route(4096, 1), route(4224, 1)
+    assert (lo["np"], lo["shared_panels"], lo["lookahead"]) == (4096, 0, 0)
+    assert (hi["np"], hi["shared_panels"], hi["lookahead"]) == (4224, 1, 1)
+    assert route(4224, 4)["shared_panels"] == 1 and route(4224, 5)["shared_panels"] == 0
+    # strips: they ride up to 256 tiles of 64 columns (128 rows: two per member)
+    assert (route(128, 128)["parts"], route(128, 128)["part_strips_at_end"]) == (1, [0, 0])
+    assert (route(128, 129)["parts"], route(128, 129)["part_strips_at_end"]) == (1, [1, 0])
+    # split: from four matrices and 2^26 elements on
+    assert (route(4096, 4)["parts"], route(4096, 4)["part_batch"]) == (2, [2, 2])
+    assert (route(4095, 4)["parts"], route(4095, 4)["part_batch"]) == (1, [4, 0])
+    assert route(4096, 3)["parts"] == 1
+    # block width 128: from eight matrices and 2^26 elements on (8 x 2896^2 < 2^26 <= 8 x 2897^2)
+    assert 8 * 2896 ** 2 < 2 ** 26 <= 8 * 2897 ** 2
+    assert route(2896, 8)["block_width"] == 256 and route(2897, 8)["block_width"] == 128
+    assert route(4200, 7)["block_width"] == 256
+    # MI32_LOOKAHEAD_MIN: the fewest padded rows with the look-ahead; values up to 2048 mean 2048
+    assert route(2300, 1)["lookahead"] == 0
+    for value in ("2048", "100"):
+        monkeypatch.setenv("MI32_LOOKAHEAD_MIN", value)
+        assert (route(2300, 1)["np"], route(2300, 1)["lookahead"]) == (2304, 1)
+        assert route(2300, 1)["part_strips_at_end"] == [1, 0]
+        assert route(2048, 1)["lookahead"] == 1 and route(1920, 1)["lookahead"] == 0
+    # what the blocked path does not take
+    lib = _lib.load()
+    r = _lib.Route()
+    for n, batch in ((0, 1), (4200, 0), (16385, 1)):
+        assert lib.mi32_resolve_route(None, n, batch, ctypes.byref(r), None, 0) == _lib.MI32_BAD_SHAPE
+    assert lib.mi32_resolve_route(None, 16384, 1, ctypes.byref(r), None, 0) == _lib.MI32_OK and r.np == 16384

@@ -1,6 +1,8 @@
 """The fp64 no-pivot variant (matrix_inversion_no_pivots of the reference, headers.h:11) on its blocked path
 (mi32_nopivot64.hip): AUTO from N = 512 on, explicit ``algo="blocked"`` at any order.  Every result is compared bit for
-bit (``np.array_equal``) with the oracle's no-pivot restatement, which is what the sweep kernels return."""
+bit (``np.array_equal``) with the oracle's no-pivot restatement, which is what the sweep kernels return.  Every valid
+input here is strictly diagonally dominant with a positive diagonal; tests/test_gpu_nopivot.py runs the same path on
+inputs that are not (tests/nopivot_cases.py)."""
 import time
 
 import numpy as np

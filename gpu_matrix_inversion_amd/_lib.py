@@ -80,6 +80,9 @@ C_ABI_SYMBOLS = (
     "mi32_solve_device_vbatched",
     "mi32_solve_device_vbatched_f64",
     "mi32_vbatch_solve_launches",
+    "mi32_apply_device_vbatched",
+    "mi32_apply_device_vbatched_f64",
+    "mi32_vbatch_apply_launches",
     "mi32_dominant_kernel",
     "mi32_last_error",
     "mi32_version",
@@ -238,6 +241,11 @@ def load() -> ctypes.CDLL:
         fn.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp]
     lib.mi32_vbatch_solve_launches.restype = ctypes.c_int
     lib.mi32_vbatch_solve_launches.argtypes = [ip, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
+    for fn in (lib.mi32_apply_device_vbatched, lib.mi32_apply_device_vbatched_f64):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
+    lib.mi32_vbatch_apply_launches.restype = ctypes.c_int
+    lib.mi32_vbatch_apply_launches.argtypes = [ip, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
     lib.mi32_dominant_kernel.restype = ctypes.c_char_p
     lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
     lib.mi32_last_error.restype = ctypes.c_char_p

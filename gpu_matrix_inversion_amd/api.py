@@ -243,6 +243,7 @@ class RaggedPlan:
         rows = self.orders.astype(np.int64)
         self.total_rows = int(rows.sum())
         self._row_offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(rows)[:-1]))).to(self.device)
+        self._row_ptrs = {}  # (base address, dtype, nrhs) -> int64 device tensor of member addresses (row_pointers)
 
     def packed_pointers(self, flat):
         """int64 device tensor of the member addresses inside the packed tensor ``flat`` (cached per base and dtype)."""
@@ -255,11 +256,25 @@ class RaggedPlan:
             self._ptrs[key] = ptrs
         return ptrs
 
+    def row_pointers(self, t, nrhs):
+        """int64 device tensor of the member addresses inside ``t``, a packed right-hand side of ``nrhs`` columns
+        (member b's rows start at ``sum_{i<b} n_i``; cached per base, dtype and width: an iteration that applies the
+        same buffers again computes nothing)."""
+        key = (t.data_ptr(), t.dtype, int(nrhs))
+        ptrs = self._row_ptrs.get(key)
+        if ptrs is None:
+            if len(self._row_ptrs) >= 8:
+                self._row_ptrs.clear()
+            ptrs = self._row_offsets * (int(nrhs) * t.element_size()) + t.data_ptr()
+            self._row_ptrs[key] = ptrs
+        return ptrs
+
     def close(self):
         if getattr(self, "_p", None):
             self._lib.mi32_vbatch_destroy(self._p)
             self._p = None
             self._ptrs = {}
+            self._row_ptrs = {}
 
     def __del__(self):  # pragma: no cover
         try:
@@ -659,6 +674,95 @@ class Inverter:
                                  m.dtype, nrhs, lda=lds)
         return out, st
 
+    # ---- Z = X R: applying stored inverses ----
+    def resolved_apply_ragged(self, orders, nrhs: int, elem_bytes: int = 4):
+        """The launches of one ``apply_pointers`` / ``apply_ragged`` / ``apply_diag_blocks`` call on members of these
+        orders (each 1 ... 128) with ``nrhs`` columns, host only: a list of ``(first, count, lanes, chunk_cols)`` -- a
+        range of the member list sorted by order, the lanes that own one member (8 / 16 / 32 / 64, or 128: one
+        workgroup of 128 threads per member) and the columns the kernel holds at a time.  One launch per lane class
+        that has members, at most five whatever ``nrhs`` is.  An order outside 1 ... 128, ``nrhs < 1`` or an
+        ``elem_bytes`` other than 4 or 8 raises ValueError."""
+        o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        count = ctypes.c_int()
+        out = np.empty((5, 4), np.int32)
+        _lib.check(self._lib.mi32_vbatch_apply_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs), int(elem_bytes),
+                                                        out.ctypes.data_as(ip), 5, ctypes.byref(count)),
+                   "mi32_vbatch_apply_launches")
+        return [tuple(int(v) for v in row) for row in out[:count.value]]
+
+    def apply_pointers(self, plan, x_ptrs, r_ptrs, z_ptrs, dtype, nrhs, ldx=None, ldr=None, ldz=None):
+        """``Z_b = X_b R_b`` for every member of the plan in one call, the low-level form: ``x_ptrs`` / ``r_ptrs`` /
+        ``z_ptrs`` are int64 device tensors of ``plan.batch`` member addresses (row-major members of ``dtype`` float32
+        / float64: X is n x n, R and Z are n x ``nrhs``), ``ldx`` / ``ldr`` / ``ldz`` int32 device tensors of leading
+        dimensions in elements (None: the member's order for ``ldx``, ``nrhs`` for the other two).  Every component is
+        one chain of fused multiply-adds over j ascending from +0, so the result is reproducible bit for bit; there
+        is no status.  A member may be applied in place (the same address and leading dimension for R and Z); Z over
+        X, or members that overlap otherwise, are undefined.  Asynchronous on torch's current stream."""
+        torch = self._torch
+        self._check_plan(plan)
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype: torch.float32 or torch.float64")
+        if int(nrhs) != nrhs or nrhs < 1:
+            raise ValueError("nrhs: at least one column")
+        for t, what in ((x_ptrs, "x_ptrs"), (r_ptrs, "r_ptrs"), (z_ptrs, "z_ptrs")):
+            self._check_tensor(t, torch.int64, what, plan.batch)
+        for ld, what in ((ldx, "ldx"), (ldr, "ldr"), (ldz, "ldz")):
+            if ld is not None:
+                self._check_tensor(ld, torch.int32, what, plan.batch)
+        self._bind_stream()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        fn = self._lib.mi32_apply_device_vbatched if dtype == torch.float32 else self._lib.mi32_apply_device_vbatched_f64
+        _lib.check(fn(self._h, plan._p, ptr(x_ptrs), ptr(ldx), ptr(r_ptrs), ptr(ldr), int(nrhs), ptr(z_ptrs), ptr(ldz)),
+                   "mi32_apply_device_vbatched")
+
+    @staticmethod
+    def _overlap(a, b):
+        """Whether the storage spans of two contiguous tensors of one device meet."""
+        a0, b0 = a.data_ptr(), b.data_ptr()
+        return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+    def apply_ragged(self, plan, x_flat, r, out=None):
+        """``z = blockdiag(X) r`` for members of mixed orders 1 ... 128 in one call: with ``x_flat`` the inverses
+        ``inv_ragged`` stored, the application of a block-Jacobi preconditioner at n^2 multiply-adds per block.
+        ``x_flat`` is the packed layout of ``inv_ragged``; ``r`` is a contiguous ``(plan.total_rows,)`` or
+        ``(plan.total_rows, K)`` tensor of x_flat's dtype and device in which member i's rows start at
+        ``sum_{k<i} n_k`` (a vector keeps its shape).  ``out`` may be ``r`` itself (in place) or a contiguous tensor
+        of its shape; it must not alias ``x_flat``.  Returns z."""
+        torch = self._torch
+        self._check_plan(plan)
+        if x_flat.dtype not in (torch.float32, torch.float64):
+            raise ValueError("expected a float32 or float64 tensor")
+        self._check_tensor(x_flat, x_flat.dtype, "x_flat")
+        if x_flat.numel() != plan.flat_size:
+            raise ValueError(f"x_flat holds {x_flat.numel()} elements, the plan's members {plan.flat_size}")
+        rhs, out, nrhs = self._packed_rhs(plan, x_flat.dtype, x_flat.device, r, out, "r")
+        if self._overlap(out, x_flat):
+            raise ValueError("out must not alias x_flat")
+        self.apply_pointers(plan, plan.packed_pointers(x_flat), plan.row_pointers(rhs, nrhs),
+                            plan.row_pointers(out, nrhs), x_flat.dtype, nrhs)
+        return out
+
+    def apply_diag_blocks(self, x, block_orders, r, out=None):
+        """``z = blockdiag(x) r`` in one call: ``x`` holds the consecutive diagonal blocks of the orders
+        ``block_orders`` (each 1 ... 128, summing to N) either as the dense square N x N matrix ``inv_diag_blocks``
+        returns, of which only the block entries are read, or as a 1-D packed tensor (``inv_diag_blocks(...,
+        packed=True)``).  ``r`` is ``(N,)`` or ``(N, K)`` of x's dtype and device; ``out`` may be ``r`` itself.
+        Returns z.  The plan of the last block structure is kept (shared with ``inv_diag_blocks``)."""
+        if x.dim() == 1:
+            plan = self._diag_blocks_structure(block_orders, x.device, None)[0]
+            if x.numel() != plan.flat_size:
+                raise ValueError(f"the packed x holds {x.numel()} elements, blocks of these orders {plan.flat_size} "
+                                 "(the sum of their squares)")
+            return self.apply_ragged(plan, x, r, out)
+        plan, elem_off, lds = self._diag_blocks_plan(x, block_orders)
+        rhs, out, nrhs = self._packed_rhs(plan, x.dtype, x.device, r, out, "r")
+        if self._overlap(out, x):
+            raise ValueError("out must not alias x")
+        self.apply_pointers(plan, elem_off * x.element_size() + x.data_ptr(), plan.row_pointers(rhs, nrhs),
+                            plan.row_pointers(out, nrhs), x.dtype, nrhs, ldx=lds)
+        return out
+
     def _diag_blocks_plan(self, m, block_orders):
         """``(plan, element offsets of the blocks in m, leading dimensions)`` for the diagonal blocks of ``m``, from
         the one-entry cache ``_diag_plan`` where the block structure is that of the last call."""
@@ -669,10 +773,20 @@ class Inverter:
             raise ValueError(f"m is on {m.device}, expected {self.device}")
         if m.dim() != 2 or m.shape[0] != m.shape[1] or not m.is_contiguous():
             raise ValueError("expected a contiguous square matrix")
+        return self._diag_blocks_structure(block_orders, m.device, m.shape[0])
+
+    def _diag_blocks_structure(self, block_orders, device, total):
+        """The cache behind ``_diag_blocks_plan``; ``total``: what the orders must sum to (None: anything, the packed
+        form)."""
+        torch = self._torch
+        if device != self.device:
+            raise ValueError(f"the blocks are on {device}, expected {self.device}")
         orders = np.asarray(block_orders)
-        if orders.ndim != 1 or orders.size == 0 or int(orders.sum()) != m.shape[0]:
+        if orders.ndim != 1 or orders.size == 0:
+            raise ValueError("block_orders: a non-empty 1-D sequence of block orders")
+        if total is not None and int(orders.sum()) != total:
             raise ValueError("block_orders must sum to the matrix order")
-        ld = m.shape[0]
+        ld = int(orders.sum())
         key = orders.astype(np.int32).tobytes()
         if self._diag_plan is None or self._diag_plan[0] != key:
             if self._diag_plan is not None:
@@ -684,14 +798,24 @@ class Inverter:
                                torch.full((orders.size,), ld, dtype=torch.int32, device=self.device))
         return self._diag_plan[1:]
 
-    def inv_diag_blocks(self, m, block_orders, out=None, *, det=False):
+    def inv_diag_blocks(self, m, block_orders, out=None, *, det=False, packed=False):
         """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
         orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
         default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``; with
         ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block (the determinant of the block-diagonal
-        matrix is their product: add the logarithms of ``slogdet_from_frexp``)."""
+        matrix is their product: add the logarithms of ``slogdet_from_frexp``).  ``packed=True``: ``out`` is the packed
+        layout of ``inv_ragged`` instead -- a 1-D tensor of ``sum n_b^2`` elements, block b at offset
+        ``sum_{i<b} n_i^2``, what ``apply_diag_blocks`` takes -- and no N x N buffer is touched."""
         torch = self._torch
         plan, elem_off, lds = self._diag_blocks_plan(m, block_orders)
+        if packed:
+            if out is None:
+                out = torch.empty(plan.flat_size, dtype=m.dtype, device=m.device)
+            else:
+                self._check_tensor(out, m.dtype, "out", plan.flat_size)
+            r = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(), plan.packed_pointers(out), m.dtype,
+                                  lda=lds, det=det)
+            return (out, r[0], r[1]) if det else (out, r)
         if out is None:
             out = torch.zeros_like(m)
         elif out.shape != m.shape or out.dtype != m.dtype or out.device != m.device or not out.is_contiguous():

@@ -3,6 +3,7 @@
 #include <new>
 #include <vector>
 
+#include "mi32_apply.h"
 #include "mi32_context.h"
 
 using namespace mi32;
@@ -187,6 +188,25 @@ static int solve_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T 
     return hip_status(e, "kernel launch");
 }
 
+// Z = X R for a variable-size batch: the launches of apply_walk, no workspace, no memset, no status (a product cannot
+// fail).  The arguments are checked before the context is touched.
+template <typename T>
+static int apply_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_x, const int *d_ldx,
+                                 const T *const *d_r, const int *d_ldr, int nrhs, T *const *d_z, const int *d_ldz)
+{
+    if (!h || !p || !d_x || !d_r || !d_z || nrhs <= 0) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const ApplyArgs<T> a{p->d_orders, p->d_members, d_x, d_r, d_z, d_ldx, d_ldr, d_ldz, nrhs};
+    hipError_t e = hipSuccess;
+    apply_walk(p->class_begin, sizeof(T), [&](const ApplyLaunch &l) {
+        e = apply_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+        return e == hipSuccess;
+    });
+    return hip_status(e, "kernel launch");
+}
+
 extern "C" {
 
 int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status)
@@ -311,6 +331,19 @@ int mi32_solve_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const doubl
                                    const int *d_ldx, int *d_status)
 {
     return solve_device_vbatched(h, p, d_a, d_lda, d_b, d_ldb, nrhs, d_x, d_ldx, d_status);
+}
+
+int mi32_apply_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_x, const int *d_ldx,
+                               const float *const *d_r, const int *d_ldr, int nrhs, float *const *d_z, const int *d_ldz)
+{
+    return apply_device_vbatched(h, p, d_x, d_ldx, d_r, d_ldr, nrhs, d_z, d_ldz);
+}
+
+int mi32_apply_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_x, const int *d_ldx,
+                                   const double *const *d_r, const int *d_ldr, int nrhs, double *const *d_z,
+                                   const int *d_ldz)
+{
+    return apply_device_vbatched(h, p, d_x, d_ldx, d_r, d_ldr, nrhs, d_z, d_ldz);
 }
 
 int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out)

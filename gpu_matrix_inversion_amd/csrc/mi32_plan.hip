@@ -1,6 +1,7 @@
 // mi32_plan.hip -- launch planning of libmat_inv_32.so: which algorithm, which blocking, how much workspace, which
 // kernel instance for which members and columns.  Pure host code: functions of the settings, the environment and the
 // shape, no HIP runtime call and no context -- the mi32_resolve_* entry points answer with what a call would do.
+#include "mi32_apply.h"
 #include "mi32_context.h"
 
 using namespace mi32;
@@ -295,6 +296,19 @@ bool vsolve_has_columns(const int *order_begin)
     return order_begin[kWorkgroupMaxOrder + 1] == order_begin[kWorkgroupMaxOrder];
 }
 
+// ---- Z = X R for a variable-size batch -----------------------------------------------------------------------------------
+// One launch per lane class that has members; the columns are walked inside the kernel.  mi32_vbatch_apply_launches
+// reports this list and mi32_apply_device_vbatched* walks it.
+void mi32::apply_walk(const int *class_begin, size_t elem_bytes, const ApplyLaunchFn &f)
+{
+    static_assert(kVbatchClasses == 8 && kApplyClasses == 5, "the plan's classes 4 ... 7 share the 128-thread kernel");
+    for (int k = 0; k < kApplyClasses; ++k) {
+        const int first = class_begin[k], end = class_begin[k + 1 < kApplyClasses ? k + 1 : kVbatchClasses];
+        if (end == first) continue;  // a class without members is not launched
+        if (!f(ApplyLaunch{first, end - first, kApplyLanes[k], apply_chunk_cols(elem_bytes)})) return;
+    }
+}
+
 extern "C" {
 
 size_t mi32_workspace_bytes(int n, int batch, int algo)
@@ -414,6 +428,27 @@ int mi32_vbatch_solve_launches(const int *orders, int batch, int nrhs, int *laun
     });
     if (total > 0x7fffffffLL) return MI32_BAD_SHAPE;
     *count = (int)total;
+    return MI32_OK;
+}
+
+int mi32_vbatch_apply_launches(const int *orders, int batch, int nrhs, int elem_bytes, int *launches, int capacity,
+                               int *count)
+{
+    if (!orders || !count || batch <= 0 || nrhs <= 0 || (elem_bytes != 4 && elem_bytes != 8) || capacity < 0 ||
+        (capacity > 0 && !launches))
+        return MI32_BAD_SHAPE;
+    int class_begin[kVbatchClasses + 1];
+    if (vbatch_sort(orders, batch, nullptr, class_begin, nullptr) != MI32_OK) return MI32_BAD_SHAPE;
+    int total = 0;
+    apply_walk(class_begin, (size_t)elem_bytes, [&](const ApplyLaunch &a) {
+        if (total < capacity) {
+            int *l = launches + 4 * total;
+            l[0] = a.first, l[1] = a.count, l[2] = a.lanes, l[3] = a.cols;
+        }
+        ++total;
+        return true;
+    });
+    *count = total;
     return MI32_OK;
 }
 

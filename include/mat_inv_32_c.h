@@ -271,6 +271,40 @@ int mi32_solve_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const doubl
  * order outside 1 ... 127. */
 int mi32_vbatch_solve_launches(const int *orders, int batch, int nrhs, int *launches, int capacity, int *count);
 
+/* Apply stored matrices to right-hand sides: Z_b = X_b R_b for every member of a plan (mixed orders 1 ... 128, order 128
+ * included), with ONE nrhs >= 1 for the call.  With X_b a stored inverse (mi32_inv_device_vbatched) this is the
+ * per-iteration half of a block-Jacobi preconditioner, z = blockdiag(A)^-1 r, at n^2 multiply-adds per member and column
+ * where mi32_solve_device_vbatched repeats the elimination.  d_x, d_r, d_z: DEVICE arrays of `batch` device pointers;
+ * member b's X is n_b x n_b with rows d_ldx[b] elements apart, its R and Z are n_b x nrhs with rows d_ldr[b] / d_ldz[b]
+ * elements apart.  d_ldx, d_ldr, d_ldz: device int[batch]; a NULL d_ldx means the member's order, a NULL d_ldr or d_ldz
+ * means nrhs.  Element alignment is all a member needs.  Padding is never read and never written.
+ *
+ * The arithmetic is fixed, so the result is reproducible bit for bit and a few lines of C restate it:
+ *     z[i][k] = acc after:  acc = +0;  for j = 0 ... n-1 ascending:  acc = fma(x[i][j], r[j][k], acc)
+ * one fused multiply-add per term in the element type.  No term is skipped -- a zero in X is multiplied through, NaN and
+ * infinity propagate by IEEE rules -- and there is no status: a product cannot fail.  The kernels' layout (lanes per
+ * member, tiles, column chunks) does not enter the result.
+ *
+ * A member may be applied in place, d_z[b] == d_r[b] with d_ldz[b] == d_ldr[b] (a member's loads of a chunk of columns
+ * all precede its stores of that chunk); Z over X, and members that overlap in any other way, are undefined.  One
+ * launch per lane class that has members -- at most five, whatever nrhs is: the columns are walked inside the kernel --
+ * no workspace and no memset.  A NULL h, p, d_x, d_r or d_z, nrhs <= 0 or a plan of another device is MI32_BAD_SHAPE,
+ * decided before the context is touched.  The context's mutex and stream; its algorithm and pivoting settings are
+ * ignored.  Asynchronous on the context's stream under profiling class 3. */
+int mi32_apply_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_x, const int *d_ldx,
+                               const float *const *d_r, const int *d_ldr, int nrhs, float *const *d_z, const int *d_ldz);
+int mi32_apply_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_x, const int *d_ldx,
+                                   const double *const *d_r, const int *d_ldr, int nrhs, double *const *d_z,
+                                   const int *d_ldz);
+/* The launches of such a call, pure host code (no device; the call itself walks this very list): launches[4 * i ...]
+ * <- first, count (a range of the sorted member list), lanes per member (8 / 16 / 32 / 64 for the orders up to 8 / 16 /
+ * 32 / 64; 128: one workgroup of 128 threads per member, the orders 65 ... 128), columns per chunk (8 for elem_bytes 4,
+ * 4 for 8; the same for every launch), ordered by first.  At most `capacity` launches are written (launches may be NULL
+ * when capacity is 0); *count is always the full number, at most five.  MI32_BAD_SHAPE: a NULL orders or count,
+ * batch <= 0, nrhs <= 0, elem_bytes other than 4 or 8, capacity < 0, an order outside 1 ... 128. */
+int mi32_vbatch_apply_launches(const int *orders, int batch, int nrhs, int elem_bytes, int *launches, int capacity,
+                               int *count);
+
 /* Device-side verification (the reference's matrix_multiply.cpp:17-36,193-200 and
  * the residual BASELINE.json gates): per matrix, d_out[3*b+0] = ||A X - I||_inf,
  * d_out[3*b+1] = ||X A - I||_inf, d_out[3*b+2] = sqrt(N) - ||A X||_F, all

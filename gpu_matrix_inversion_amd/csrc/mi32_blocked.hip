@@ -57,8 +57,13 @@
 //
 // The working matrix is the N x N in-place form (see mi32_sweep.hip), padded
 // with an identity block to a multiple of 128 so that no tile needs bounds
-// checks: inv(diag(A, I)) = diag(inv(A), I); a real column only ever takes its
-// pivot from the real rows, so the padding is never swapped into the matrix.
+// checks: inv(diag(I, A)) = diag(I, inv(A)).  The padding comes FIRST (rows and
+// columns [0, np - n)), so its steps run while every entry is finite -- pivot 1,
+// multipliers 0, exact no-ops -- and its rows are retired before the first real
+// step: a padded row still takes fmaf(-0, u, 0) in the real steps (NaN where an
+// overflowed pivot row holds an infinity), but nothing reads it any more.  With
+// the padding behind the matrix those NaNs came back through the padded steps
+// and an inverse that overflows lost its infinities to NaN, column by column.
 //
 // Where things are.  How a call runs -- blocking, sub-panel widths, fused blocks, shared panels, look-ahead, split,
 // where the strips go -- is decided in mi32_plan.hip (plan_route) and arrives as a BlockedRoute (mi32_internal.h).  This
@@ -151,7 +156,7 @@ static size_t blocked_carve(const BlockedRoute &p, int batch, void *base, Blocke
 }
 size_t blocked_workspace_bytes(const BlockedRoute &r, int batch) { BlockedWs ws; return blocked_carve(r, batch, nullptr, ws); }
 
-// ---- init: A -> diag(A, I) in the first working copy (makeAugmentedMatrix counterpart,
+// ---- init: A -> diag(I, A) in the first working copy (makeAugmentedMatrix counterpart,
 //      mat_inv_32.cpp:177-192) + the compact copies of the first two sub-panels' columns ------
 __global__ __launch_bounds__(256) void blocked_init_kernel(const float *__restrict__ in, int n, int np, int ld,
                                                             size_t mstride, float *__restrict__ m0, PanelExport ex,
@@ -163,6 +168,7 @@ __global__ __launch_bounds__(256) void blocked_init_kernel(const float *__restri
     const int i0 = blockIdx.y * 16;
     const float *a = in + (size_t)b * n * n;
     float *m = m0 + (size_t)b * mstride;
+    const int pad = np - n;  // the identity padding comes first
     bool nonfinite = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
     if (j < np) {
 #pragma unroll 4
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(256) void blocked_init_kernel(const float *__restri
             const int i = i0 + u;
             if (i >= np) break;
             float v;
-            if (i < n && j < n) v = a[(size_t)i * n + j];
+            if (i >= pad && j >= pad) v = a[(size_t)(i - pad) * n + (j - pad)];
             else v = (i == j) ? 1.0f : 0.0f;
             nonfinite = nonfinite || (v - v != 0.0f);
             m[(size_t)i * ld + j] = v;
@@ -199,6 +205,7 @@ __global__ __launch_bounds__(256) void unpermute_columns_ld_kernel(const float *
     float *o = out + (size_t)b * n * n;
     const int i0 = blockIdx.x * rows_per_block;
     const int nr = (n - i0 < rows_per_block) ? (n - i0) : rows_per_block;
+    const int pad = np - n;  // the matrix lies behind the identity padding: rows and columns [pad, np)
     // a matrix whose shared panel lost a partner workgroup went on with stale data: hand out NaN, not numbers
     if (status != nullptr && __builtin_amdgcn_readfirstlane(status[b]) == MI32_RUNTIME_ERROR) {
         for (int r = 0; r < nr; ++r)
@@ -208,10 +215,10 @@ __global__ __launch_bounds__(256) void unpermute_columns_ld_kernel(const float *
     for (int r = 0; r < nr; ++r)
         for (int c4 = tid * 4; c4 < np; c4 += 1024)
             *reinterpret_cast<float4 *>(&s_rows[(size_t)r * np + c4]) =
-                *reinterpret_cast<const float4 *>(w + (size_t)(i0 + r) * ld + c4);
+                *reinterpret_cast<const float4 *>(w + (size_t)(pad + i0 + r) * ld + c4);
     __syncthreads();
     for (int j = tid; j < n; j += 256) {
-        const int c = invp[(size_t)b * istride + j];
+        const int c = invp[(size_t)b * istride + pad + j];
         for (int r = 0; r < nr; ++r) o[(size_t)(i0 + r) * n + j] = s_rows[(size_t)r * np + c];
     }
 }

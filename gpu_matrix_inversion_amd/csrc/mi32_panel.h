@@ -391,9 +391,9 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
         }
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            // A candidate is a row of the matrix at or below the block.  A real column (slot < n) may only take
-            // its pivot from the real rows: the identity padding holds exact zeros there, which can tie only
-            // with an all-zero column, and then the lowest position -- a real row -- wins the tie.
+            // A candidate is a row of the matrix at or below the block.  The identity padding comes first
+            // (mi32_blocked.hip): its rows are retired by their own steps before the first real column is
+            // searched, so a real column only ever takes its pivot from the real rows.
             // Rows beyond the matrix (row >= np) are dead and are never written back.
             const bool live = (row + j < np) && (p0[j] >= c0);
             npl[g * V + j] = live ? ~(unsigned)p0[j] : (unsigned)p0[j];

@@ -351,6 +351,7 @@ hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, flo
             A.u_panel_hi = p.pivoting ? np : A.u_c0 + w;
             A.x = x; A.y = y;
             A.u_gt = ws.gt[t & 1];
+            A.u_tri = p.pivoting && panel_instance(p, blk, t).tri;  // panel(t) wrote no Gt_t
             A.u_pt_in = ws.pt[t % 3];
             A.u_aux = ws.aux[t & 1];
             // fused: sub-panel t+2's columns (t+1's are brought up to date by its own panel);

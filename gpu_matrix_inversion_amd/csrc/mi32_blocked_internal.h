@@ -64,7 +64,7 @@ struct SubpanelArgs {
     int first_in_block;
     const float *pt_in;      // Pt_s: this sub-panel's columns, updates up to s-2 applied, order after s-2
     const float *mt_prev;    // Mt_{s-1}: the multipliers of sub-panel s-1, same order
-    float *gt_out;           // Gt_s, order after s-1
+    float *gt_out;           // Gt_s, order after s-1 (not written by a panel with triangular steps: panel_tri, mi32_internal.h)
     float *mt_out;           // Mt_s: the multipliers of this sub-panel's W steps (fused: order after s-1; else slab order = the same)
     size_t mtstride; int mtld;
     const int *submap_prev;  // submap of sub-panel s-1: position after s-1 -> index in order after s-2
@@ -94,6 +94,8 @@ struct SubpanelArgs {
     const float *x;  // working copy in order after t-1
     float *y;        // working copy written in order after t
     const float *u_gt;     // Gt_t
+    int u_tri;             // panel(t) ran triangular steps (panel_tri): it wrote no Gt_t, the column-tile-0 tiles
+                           // compute G_t of its rows from Mt_t and aux_t
     const float *u_mt;     // Mt_t
     const int *u_rowsrc;   // position after t -> row index at the start of the block
     float *u_mf;           // the block's negated multipliers by block-start row index, [np][mf_ld]

@@ -162,6 +162,39 @@ inline void panel_geometry(const BlockedRoute &r, int nrows, int &nt, int &rpt)
     }
 }
 
+// Which panel instance runs TRIANGULAR pivot steps (mi32_panel.h, panel_step): step R updates the columns c > R only and
+// the panel writes no G_s -- the column-tile-0 update tiles compute it from the multipliers and the normalised pivot
+// rows (SubpanelArgs::u_tri), and one wave of the panel completes the pivot rows left of their pivots after the last
+// step (tri_left_rows: ~3 us).  That pays where the panel's own FMAs and its G_s store cost more, and it is on for the
+// one instance it was measured on: the unfused one-workgroup panel of 1024 threads x 4 rows per lane x 16 columns
+// (3073 ... 4096 rows; 31.5 -> 28.0 us per launch).  At one to three rows per lane the same change cost 0.2 ... 3 us per
+// launch; the other geometries with four and more rows per lane have not been timed.
+// Never the multi-workgroup panels: their exchange granules carry no multiplier history.
+constexpr bool panel_tri(int nt, int rpt, int w, bool multi, bool fused)
+{
+    return !multi && !fused && nt == 1024 && rpt == 4 && w == 16;
+}
+
+// The kernel instance that runs panel(s) of outer block blk with pivoting: what blocked_invert and dispatch_subpanel
+// make of the route (thread geometry by the rows the panel holds; fused when an update rides in its launch, which the
+// first panel of a fused block has none of).
+struct PanelInstance {
+    int nt, rpt, w, groups;
+    bool fused, tri;
+};
+inline PanelInstance panel_instance(const BlockedRoute &r, int blk, int s)
+{
+    PanelInstance pi;
+    pi.w = r.wblk[blk];
+    pi.fused = r.fused(blk) && s > 0;
+    const int c0 = blk * r.bw + s * pi.w;
+    const int rows = r.np - (pi.fused ? c0 - pi.w : c0);  // a fused panel holds the pivot rows of s-1 once more
+    pi.groups = r.panel_groups(rows);
+    panel_geometry(r, rows, pi.nt, pi.rpt);
+    pi.tri = panel_tri(pi.nt, pi.rpt, pi.w, pi.groups > 1, pi.fused);
+    return pi;
+}
+
 SweepPlan make_sweep_plan(int n);
 
 size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes);

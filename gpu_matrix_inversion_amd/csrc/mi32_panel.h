@@ -29,7 +29,7 @@ __device__ unsigned long long *g_panel_stamps;  // [1024 launches][64 slots]
 // submap[position] = where the data that now belongs at that position lies in the
 // previous order tells the rank-k updates where every other column's data still lives.
 
-template <int NW, int W>
+template <int NW, int W, bool TRI>
 struct __attribute__((aligned(16))) PanelShared {
     float cand[NW][W];          // per wave: its best candidate row as found (wave-private scratch)
     float prn[2][NW][W];        // per step parity, per wave: that row NORMALISED (candidate pivot row)
@@ -37,9 +37,12 @@ struct __attribute__((aligned(16))) PanelShared {
     float prn_all[W][W];        // the normalised pivot row of every step, exported for the rows above the block
     float bprev[W][W];          // the previous sub-panel's W pivot rows, restricted to this sub-panel's columns
     float uprev[W][W];          // ... as that sub-panel's own steps saw them (u_m of the strip)
-    float lt[W][W + 4];         // -multipliers of those W pivot rows, [step][row]; at the end: this sub-panel's own
+    float lt[W][W + 4];         // -multipliers of those W pivot rows, [step][row] (the prologue's strip)
     unsigned gx[2][kMaxPanelGroups][W + 2];  // multi-workgroup panels: every workgroup's winner of this step
     int lost;                   // multi-workgroup panels: a partner timed out (sticky; zeroed at kernel start)
+    // triangular steps (the only instances that pay for it): the winner of step R as found, [R][c < R] = its
+    // multipliers of the earlier steps, [R][R] = its pivot (tri_left_rows makes prn_all's left part of them)
+    float raw[TRI ? W : 1][W];
 };
 
 // which matrix row register row k of thread tid holds: V consecutive rows per thread so that the
@@ -103,11 +106,13 @@ __device__ __forceinline__ void mt_store(float *sbase, unsigned voff, T v)
 // LBL (fused instances: the rows' labels at entry differ from their slab index), mt_base + moff[k] per row.
 template <int NT, int RPT, int W, int R, bool MULTI, bool LBL>
 __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[RPT],
-                                           const int (&moff)[LBL ? RPT : 1], PanelShared<NT / 64, W> &sh,
+                                           const int (&moff)[LBL ? RPT : 1],
+                                           PanelShared<NT / 64, W, panel_tri(NT, RPT, W, MULTI, LBL)> &sh,
                                            int wave_u, int c0, bool wave_active, bool &singular, PanelGroup &pg,
                                            float *mtp, int mtld)
 {
     constexpr int par = R & 1;
+    constexpr bool TRI = panel_tri(NT, RPT, W, MULTI, LBL);  // the step runs on the columns c > R only (fixColumn below)
     const int slot = c0 + R;
     // The lane id is recomputed in every step (two v_mbcnt, opaque to the optimiser): a `lane` carried through
     // the 16 unrolled steps is the first thing the 128-VGPR instances spill, and every path of the step reads
@@ -196,6 +201,10 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
             const float num = (lane < W) ? ((lane == R) ? 1.0f : sh.cand[wave_u][lane]) : 0.0f;
             if (kSub) MI32_PSTAMP(pg.tag_base, 36);
             qv = num / cpiv;
+            // Triangular steps: the candidate's columns < R hold its multipliers of those steps, not row entries
+            // (the steps below leave columns <= R alone).  Should it win, the register takes to LDS what the epilogue
+            // needs instead: lanes < R the multiplier as found, lane W the pivot.
+            if constexpr (TRI) qv = (lane < R) ? num : (lane == W ? cpiv : qv);
             cand_bad = (cpiv == 0.0f || cpiv - cpiv != 0.0f);
             if (kSub) MI32_PSTAMP(pg.tag_base, 37);
             if (lane < W) sh.prn[par][wave_u][lane] = qv;
@@ -283,24 +292,33 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
     }
     const int wv = MULTI ? (int)(lo & 0xFu) : (int)(lo & 0xFFu);
     if (key == 0ull) singular = true;  // cannot happen (position `slot` is always a live candidate); never trust it
-    if constexpr (!MULTI) {
+    if constexpr (!MULTI) {  // triangular steps: only the columns c > R are read below
 #pragma unroll
-        for (int c = 0; c < W; c += 4) {
+        for (int c = TRI ? ((R + 1) / 4) * 4 : 0; c < W; c += 4) {
             const float4 t = *reinterpret_cast<const float4 *>(&sh.prn[par][wv][c]);
             prn[c] = t.x; prn[c + 1] = t.y; prn[c + 2] = t.z; prn[c + 3] = t.w;
         }
     }
-    if (kSub) { asm volatile("" ::"v"(prn[0]), "v"(prn[W - 1])); MI32_PSTAMP(pg.tag_base, 41); }
+    if (kSub) { asm volatile("" ::"v"(prn[W - 1])); MI32_PSTAMP(pg.tag_base, 41); }
     // -- fixColumn on the slab, branch-free; the pivot column holds the implicit identity column, whose
     //    entry is 0 in every row but the pivot row.  The pivot row itself is overwritten right after.
+    //    Triangular steps (panel_tri, mi32_internal.h) run on the columns c > R only -- all that the later searches
+    //    and multipliers depend on.  A column c <= R keeps what it held when its own step ran, the row's multiplier of
+    //    that step (its pivot, in the pivot row): the finished entries of those columns are a function of the
+    //    multipliers and the normalised pivot rows, and the update tiles evaluate it (inblock_update_body).
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const float f = col[k];
+        if constexpr (!TRI) {
 #pragma unroll
-        for (int c = 0; c < W; ++c)
-            a[k][c] = (c == R) ? __builtin_fmaf(-f, prn[R], 0.0f) : __builtin_fmaf(-f, prn[c], a[k][c]);
+            for (int c = 0; c < W; ++c)
+                a[k][c] = (c == R) ? __builtin_fmaf(-f, prn[R], 0.0f) : __builtin_fmaf(-f, prn[c], a[k][c]);
+        } else {
+#pragma unroll
+            for (int c = R + 1; c < W; ++c) a[k][c] = __builtin_fmaf(-f, prn[c], a[k][c]);
+        }
     }
-    if (kSub) { asm volatile("" ::"v"(a[0][0]), "v"(a[RPT - 1][W - 1])); MI32_PSTAMP(pg.tag_base, 42); }
+    if (kSub) { asm volatile("" ::"v"(a[0][W - 1]), "v"(a[RPT - 1][W - 1])); MI32_PSTAMP(pg.tag_base, 42); }
     // -- pivotElements == exchange of two position labels: the row that held `slot` takes p ...
     if (p != slot) {
 #pragma unroll
@@ -312,13 +330,22 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
         // the winner's own pivot entry decides "singular" (zero, NaN or infinite pivot); its normalised row is
         // still in lanes 0..W-1 -- no LDS read on the slowest wave's way to the next barrier
         if (cand_bad) singular = true;
-        if (!MULTI && lane < W) sh.prn_all[R][lane] = qv;
+        if constexpr (TRI) {
+            // qv: lanes < R the candidate's multipliers as found, lanes R .. W-1 its normalised row, lane W its pivot.
+            // One LDS store on the slowest wave's way to the next barrier, as in the full step: the address differs.
+            float *dst = &sh.prn_all[R][lane];
+            if (lane < R) dst = &sh.raw[R][lane];
+            if (lane == W) dst = &sh.raw[R][R];
+            if (lane <= W) *dst = qv;
+        } else if (!MULTI && lane < W) {
+            sh.prn_all[R][lane] = qv;
+        }
 #pragma unroll
         for (int k = 0; k < RPT; ++k)
             if (own_k == k) {
                 if (lane == own_lane) {
 #pragma unroll
-                    for (int c = 0; c < W; ++c) a[k][c] = prn[c];
+                    for (int c = TRI ? R + 1 : 0; c < W; ++c) a[k][c] = prn[c];
                     npl[k] = (unsigned)slot;
                 }
             }
@@ -328,17 +355,45 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
 
 template <int NT, int RPT, int W, bool MULTI, bool LBL, int... Rs>
 __device__ __forceinline__ void panel_steps(float (&a)[RPT][W], unsigned (&npl)[RPT],
-                                            const int (&moff)[LBL ? RPT : 1], PanelShared<NT / 64, W> &sh,
+                                            const int (&moff)[LBL ? RPT : 1],
+                                            PanelShared<NT / 64, W, panel_tri(NT, RPT, W, MULTI, LBL)> &sh,
                                             int wave_u, int c0, bool wave_active, bool &singular, PanelGroup &pg,
                                             float *mtp, int mtld, std::integer_sequence<int, Rs...>)
 {
     (panel_step<NT, RPT, W, Rs, MULTI, LBL>(a, npl, moff, sh, wave_u, c0, wave_active, singular, pg, mtp, mtld), ...);
 }
 
-template <int NW, int W>
+// Triangular steps, after the last one: the entries the W pivot rows hold LEFT of their pivot column, which no step
+// computed.  The row that won step R entered it with
+//     x[c] = fmaf(-f_{R-1}, prn_{R-1}[c], ... fmaf(-f_{c+1}, prn_{c+1}[c], fmaf(-f_c, prn_c[c], 0)) ...),   c < R,
+// (fixColumn of the steps c .. R-1 on its column c, which held the identity column's 0 when step c ran; f_m = the
+// multiplier it kept in column m = raw[R][m]) and fixRow made prn_R[c] = x[c] / pivot (IEEE division, as in the
+// step).  Lane c owns column c: what it needs of the earlier pivot rows, prn_m[c], c < m < R, it has computed itself;
+// prn_c[c] = 1/pivot_c is in prn_all already.  One wave; no step of the chain waits for another lane.
+template <int W, int R>
+__device__ __forceinline__ void tri_left_row(float (&pl)[W], const float (&raw)[W][W], int c)
+{
+    if constexpr (R == 0) return;  // the first pivot row has nothing left of its pivot
+    float v = 0.0f;
+#pragma unroll
+    for (int m = 0; m < R; ++m) {
+        const float t = __builtin_fmaf(-raw[R][m], pl[m], v);
+        v = (m >= c) ? t : v;
+    }
+    const float q = v / raw[R][R];
+    pl[R] = (c < R) ? q : pl[R];
+}
+template <int W, int... Rs>
+__device__ __forceinline__ void tri_left_rows(float (&pl)[W], const float (&raw)[W][W], int c,
+                                              std::integer_sequence<int, Rs...>)
+{
+    (tri_left_row<W, Rs>(pl, raw, c), ...);
+}
+
+template <int NW, int W, bool TRI>
 constexpr size_t panel_shared_bytes()
 {
-    return (sizeof(PanelShared<NW, W>) + 15) & ~(size_t)15;
+    return (sizeof(PanelShared<NW, W, TRI>) + 15) & ~(size_t)15;
 }
 
 // panel(s) of one matrix: the whole workgroup.  smem: panel_shared_bytes + 2 * RPT * NT ints.
@@ -356,8 +411,9 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
     constexpr int NW = NT / 64;
     typedef float vecV __attribute__((ext_vector_type(V)));
     typedef int ivecV __attribute__((ext_vector_type(V)));
-    PanelShared<NW, W> &sh = *reinterpret_cast<PanelShared<NW, W> *>(smem);
-    int *s_park = reinterpret_cast<int *>(smem + panel_shared_bytes<NW, W>());  // [2][RPT][NT]
+    constexpr bool TRI = panel_tri(NT, RPT, W, MULTI, FUSED);
+    PanelShared<NW, W, TRI> &sh = *reinterpret_cast<PanelShared<NW, W, TRI> *>(smem);
+    int *s_park = reinterpret_cast<int *>(smem + panel_shared_bytes<NW, W, TRI>());  // [2][RPT][NT]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -554,13 +610,34 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
     __syncthreads();
     MI32_PSTAMP(A.tag_base, 48);
     float *aux = A.aux_out + (size_t)b * kAuxFloats;
-    if (grp == 0)
+    if constexpr (TRI) {
+        // one wave completes the pivot rows left of their pivots (tri_left_rows) and exports them; the others are
+        // on their way to the map stores
+        if (wave_u == 0) {
+            const int c = tid_e < W ? tid_e : W - 1;
+            const float diag = sh.prn_all[c][c];
+            float pl[W];  // pl[m] = prn_m[c]: the diagonal to start with, the rows below it as they are found
+#pragma unroll
+            for (int m = 0; m < W; ++m) pl[m] = (m == c) ? diag : 0.0f;
+            tri_left_rows<W>(pl, sh.raw, c, std::make_integer_sequence<int, W>{});
+            if (tid_e < W) {
+#pragma unroll
+                for (int m = 1; m < W; ++m)
+                    if (c < m) sh.prn_all[m][c] = pl[m];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int i = tid_e; i < W * W; i += 64) aux[i] = sh.prn_all[i / W][i % W];
+        }
+    } else if (grp == 0) {
         for (int i = tid_e; i < W * W; i += NT) {
             aux[i] = sh.prn_all[i / W][i % W];
             if (has_prev) aux[kMaxW * kMaxW + i] = sh.uprev[i / W][i % W];
         }
-    // -- G_s by label at entry (order after s-1: what update(s) reads the working copy in); the row maps
-    float *gt = A.gt_out + (size_t)b * A.tstride;
+    }
+    // -- the row maps; panels with full steps: G_s too, by label at entry (order after s-1: what update(s) reads the
+    //    working copy in).  Triangular steps leave G_s to the update tiles: it is a function of Mt_s and aux.
+    [[maybe_unused]] float *gt = A.gt_out + (size_t)b * A.tstride;
     int *submap = A.submap_out + (size_t)b * np;
     int *invsub = A.invsub_out + (size_t)b * np;
     // positions retired since this map buffer was last written: identity (any earlier position already is)
@@ -574,22 +651,24 @@ __device__ __forceinline__ void panel_body(const SubpanelArgs &A, int b, int grp
 #pragma unroll
             for (int j = 0; j < V; ++j) p0[j] = row + j;
             if (has_prev) p0 = *reinterpret_cast<const ivecV *>(invsub_prev + row);
-            bool contiguous = (p0[0] % V) == 0;
+            if constexpr (!TRI) {
+                bool contiguous = (p0[0] % V) == 0;
 #pragma unroll
-            for (int j = 1; j < V; ++j) contiguous = contiguous && (p0[j] == p0[0] + j);
-            if (contiguous) {
+                for (int j = 1; j < V; ++j) contiguous = contiguous && (p0[j] == p0[0] + j);
+                if (contiguous) {
 #pragma unroll
-                for (int c = 0; c < W; ++c) {
-                    vecV v;
+                    for (int c = 0; c < W; ++c) {
+                        vecV v;
 #pragma unroll
-                    for (int j = 0; j < V; ++j) v[j] = a[g * V + j][c];
-                    *reinterpret_cast<vecV *>(gt + (size_t)c * np + p0[0]) = v;
+                        for (int j = 0; j < V; ++j) v[j] = a[g * V + j][c];
+                        *reinterpret_cast<vecV *>(gt + (size_t)c * np + p0[0]) = v;
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < W; ++c)
+#pragma unroll
+                        for (int j = 0; j < V; ++j) gt[(size_t)c * np + p0[j]] = a[g * V + j][c];
                 }
-            } else {
-#pragma unroll
-                for (int c = 0; c < W; ++c)
-#pragma unroll
-                    for (int j = 0; j < V; ++j) gt[(size_t)c * np + p0[j]] = a[g * V + j][c];
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) {

@@ -354,6 +354,21 @@ int mi32_resolve_route(mi32_handle_t h, int n, int batch, mi32_route_t *route, i
     return MI32_OK;
 }
 
+// tests only: the gj_subpanel_kernel instance that runs panel s of outer block blk of this shape, as blocked_invert
+// itself derives it (panel_instance): out[0 .. 5] = threads, rows per lane, columns, fused, workgroups per panel,
+// triangular steps.
+int mi32_debug_panel_instance(mi32_handle_t h, int n, int batch, int blk, int s, int *out)
+{
+    if (n <= 0 || batch <= 0 || !blocked_supported(n) || !out) return MI32_BAD_SHAPE;
+    Settings st = settings_of(h);
+    st.pivoting = true;
+    const BlockedRoute r = route_of(h, st, n, batch);
+    if (blk < 0 || blk >= r.nblk || s < 0 || (blk * r.bw + (s + 1) * r.wblk[blk]) > r.np) return MI32_BAD_SHAPE;
+    const PanelInstance pi = panel_instance(r, blk, s);
+    out[0] = pi.nt; out[1] = pi.rpt; out[2] = pi.w; out[3] = pi.fused; out[4] = pi.groups; out[5] = pi.tri;
+    return MI32_OK;
+}
+
 int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width)
 {
     if (n <= 0 || !block_width) return MI32_BAD_SHAPE;

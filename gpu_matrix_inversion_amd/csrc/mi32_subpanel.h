@@ -10,7 +10,8 @@ namespace mi32 {
 template <int NT, int RPT, int W, bool FUSED>
 constexpr size_t subpanel_lds_bytes(bool with_strip_tiles = true)
 {
-    const size_t pb = panel_shared_bytes<NT / 64, W>() + (size_t)2 * RPT * NT * sizeof(int);
+    const size_t pb =
+        panel_shared_bytes<NT / 64, W, panel_tri(NT, RPT, W, false, FUSED)>() + (size_t)2 * RPT * NT * sizeof(int);
     const size_t ub = FUSED ? sizeof(UpdateTileShared<W>) * (NT / 256) : 0;
     const size_t ob = with_strip_tiles ? sizeof(OStripShared<W>) * (NT / 256) : 0;  // (they cost the update tiles occupancy)
     const size_t m = pb > ub ? pb : ub;

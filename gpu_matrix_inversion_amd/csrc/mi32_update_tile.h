@@ -31,6 +31,33 @@ __device__ __forceinline__ void above_rows_steps(float (&v)[BK / 4], float (&fm)
     (above_rows_step<BK, Rs>(v, fm, s_prn, q4), ...);
 }
 
+// Step R of a row that WAS in a one-workgroup panel, which leaves the row's entries in the sub-panel's own columns
+// c <= R to the update tiles (panel_step): what fixColumn makes of them, from the row's multiplier of the step
+// (known up front: Mt) and the normalised pivot row.  Column R holds the identity column's 0 when its step runs;
+// the pivot row of the step (ps == R) takes the normalised row itself.  A column c > R is not touched: v[j] is
+// still the 0 it started from when step c reaches it.  The same fmaf, operands and order as the full panel step.
+template <int BK, int R>
+__device__ __forceinline__ void panel_rows_step(float (&v)[BK / 4], const float (&fm)[BK / 4], const float *s_prn,
+                                                int q4, int ps)
+{
+    constexpr int CPT = BK / 4;
+    constexpr int kQuad = (R / CPT) * 0x55;  // quad_perm:[q,q,q,q]
+    const float f = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(fm[R % CPT]), kQuad, 0xf, 0xf, false));
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+        const int c = q4 * CPT + j;
+        const float p = s_prn[R * BK + c];
+        const float t = (ps == R) ? p : __builtin_fmaf(-f, p, v[j]);
+        v[j] = (c <= R) ? t : v[j];
+    }
+}
+template <int BK, int... Rs>
+__device__ __forceinline__ void panel_rows_steps(float (&v)[BK / 4], const float (&fm)[BK / 4], const float *s_prn,
+                                                 int q4, int ps, std::integer_sequence<int, Rs...>)
+{
+    (panel_rows_step<BK, Rs>(v, fm, s_prn, q4, ps), ...);
+}
+
 // ---- update(t): the in-block rank-W update on the fp32 matrix cores ---------------
 // For the columns j of the block that are not sub-panel t's own, 64 x 64 tiles, 256 threads = 4 waves in a 2x2
 // arrangement per tile (NG tiles per workgroup), one 32x32 MFMA tile per wave:
@@ -92,7 +119,7 @@ __device__ __forceinline__ void inblock_update_body(const SubpanelArgs &A, int u
     if (tid < 64) T.s_map[tid] = map[row0 + tid];
     else if (tid < 64 + BK) T.s_pmap[tid - 64] = map[c0 + tid - 64];
     else if (tid >= 128 && tid < 192) T.s_rs[tid - 128] = (A.u_rowsrc + (size_t)b * np)[row0 + tid - 128];
-    if (some_above) {
+    if (some_above || (tx == 0 && A.u_tri)) {  // (the rows of a one-workgroup panel need the pivot rows as well)
         const float *aux = A.u_aux + (size_t)b * kAuxFloats;
         for (int i = tid; i < BK * BK; i += 256) {
             T.s_prn[i] = aux[i];
@@ -136,8 +163,9 @@ __device__ __forceinline__ void inblock_update_body(const SubpanelArgs &A, int u
     }
     {
         // (4) stage A = the tile's rows' multipliers, negated, [k][row]; 4 threads per row, BK/4 columns each.
-        //  * rows that were in panel(t): its compact output mt[k][map[row]] (and gt[k][map[row]] = the row's new
-        //    entries in sub-panel t's own columns);
+        //  * rows that were in panel(t): its compact output mt[k][map[row]].  The row's new entries in sub-panel t's
+        //    own columns: gt[k][map[row]] where the panel stored them (multi-workgroup and no-pivot panels), else
+        //    (u_tri) computed here from the W multipliers and the pivot rows, panel_rows_step;
         //  * rows above (never candidates, never moved): the row's W entries of the panel input Pt_t, brought up
         //    to date with update(t-1) where that was still pending (the chain of the panel prologue: old value -
         //    sum_m f_m[row] * u_m[c], f_m as materialised in mf), then taken through the W pivot steps with the
@@ -154,8 +182,12 @@ __device__ __forceinline__ void inblock_update_body(const SubpanelArgs &A, int u
 #pragma unroll
             for (int j = 0; j < CPT; ++j) fm[j] = mt[(size_t)(q4 * CPT + j) * mtld + T.s_map[rr]];
             if (tx == 0) {
+                if (A.u_tri) {  // (the four threads of a row take this branch together: the multipliers cross the quad)
+                    panel_rows_steps<BK>(v, fm, T.s_prn, q4, grow - c0, std::make_integer_sequence<int, BK>{});
+                } else {
 #pragma unroll
-                for (int j = 0; j < CPT; ++j) v[j] = g[(size_t)(q4 * CPT + j) * np + T.s_map[rr]];
+                    for (int j = 0; j < CPT; ++j) v[j] = g[(size_t)(q4 * CPT + j) * np + T.s_map[rr]];
+                }
             }
         } else {
             const float *pt_in = A.u_pt_in + (size_t)b * A.tstride;

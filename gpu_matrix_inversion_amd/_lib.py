@@ -74,6 +74,8 @@ C_ABI_SYMBOLS = (
     "mi32_inv_det_device_f64",
     "mi32_inv_det_device_vbatched",
     "mi32_inv_det_device_vbatched_f64",
+    "mi32_inv_det_any_device",
+    "mi32_inv_det_any_device_f64",
     "mi32_solve_device",
     "mi32_solve_device_f64",
     "mi32_resolve_solve",
@@ -225,7 +227,8 @@ def load() -> ctypes.CDLL:
     for fn in (lib.mi32_inv_device_vbatched, lib.mi32_inv_device_vbatched_f64):
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    for fn in (lib.mi32_inv_det_device, lib.mi32_inv_det_device_f64):
+    for fn in (lib.mi32_inv_det_device, lib.mi32_inv_det_device_f64, lib.mi32_inv_det_any_device,
+               lib.mi32_inv_det_any_device_f64):
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     for fn in (lib.mi32_inv_det_device_vbatched, lib.mi32_inv_det_device_vbatched_f64):

@@ -437,6 +437,27 @@ class Inverter:
                       ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())), "mi32_inv_det_device")
         return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
 
+    def inv_det_any(self, a, out=None, status=None, want_inverse=True):
+        """``inv_det`` at any order ``inv`` takes.  Up to N = 128 it is ``inv_det``, same kernels and same bits.  Above,
+        the call runs the route ``inv`` runs on this ``Inverter`` (algorithm, blocking, pivoting, look-ahead, batch
+        split) and takes the determinant from that elimination's own pivots: inverse and status are ``inv``'s bit for
+        bit, and the pair ``(det_mant, det_exp)`` follows the recurrence of ``inv_det`` over the pivots in step order.
+        Returns ``(inverse, status, det_mant, det_exp)``.  ``want_inverse=False``: the elimination runs, the final
+        un-permutation and store are skipped, and None is returned for the inverse.  Asynchronous on torch's current
+        stream."""
+        torch = self._torch
+        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse)
+        b, n = a3.shape[0], a3.shape[1]
+        det_mant = torch.empty(b, dtype=torch.float64, device=a3.device)
+        det_exp = torch.empty(b, dtype=torch.int32, device=a3.device)
+        self._bind_stream()
+        fn = self._lib.mi32_inv_det_any_device if a.dtype == torch.float32 else self._lib.mi32_inv_det_any_device_f64
+        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
+                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
+                      ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())),
+                   "mi32_inv_det_any_device")
+        return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
+
     def resolved_solve(self, n: int, nrhs: int, elem_bytes: int = 4):
         """(columns per launch, launches, lanes per member, register rows per thread) of ``solve`` for this shape: a
         call's ``nrhs`` columns are cut into chunks of at most ``64 - n`` (``n <= 32``) or ``128 - n`` columns, one

@@ -81,6 +81,7 @@
 //   mi32_blocked_internal.h          constants, the launches' argument structs, host helpers
 #include "mi32_blocked_block.h"
 #include "mi32_blocked_subpanel.h"
+#include "mi32_det_large.h"
 
 namespace mi32 {
 
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(256) void unpermute_columns_ld_kernel(const float *
 // second stream and overlaps with block b+1's panel phase, which is latency bound on a few CUs.  The
 // next rank-bw update (and the final un-permutation) wait for (B) through an event.
 hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, float *d_inv, int *d_status, void *wsp,
-                          const BlockedExec &ex)
+                          const BlockedExec &ex, const DetRec &det)
 {
     const int batch = p.part_batch[part];
     const bool lookahead = p.lookahead;  // (never for a half of a split batch: plan_route)
@@ -403,6 +404,15 @@ hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, flo
             }
             if (s > 0) { float *t2 = x; x = y; y = t2; }
         }
+        // A det call: the block's pivots into the per-matrix list, pivot(C0 + m) = -mf[rowsrc[C0 + m]][m].  update(t)'s
+        // column-tile-0 tiles wrote the rows of mf for every sub-panel t of the block (single-block plans included), and
+        // the pivot rows of t keep their positions after t.  On this stream, so in front of block blk + 2's update
+        // tiles, the next writers of mf[blk & 1]; the look-ahead half only reads it.
+        if (det.on()) {
+            ProfScope ps(prof, KC_FINISH, stream);
+            launch_det_gather(mf, ws.mfstride, p.bw, p.pivoting ? rsb[fused ? (S - 1) & 1 : 0] : ws.orig, np, C0, kb,
+                              (float *)det.piv, det.pstride, batch, guard, stream);
+        }
         // x now holds the block's own columns; every other column is still valid in `cur` only
         if (kb < np) {
             const int next = C0 + kb;  // first column of the next block
@@ -474,6 +484,9 @@ hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, flo
         if ((e = hipStreamWaitEvent(stream, ex.events[ev], 0)) != hipSuccess) return e;
     }
     ProfScope ps(prof, KC_FINISH, stream);
+    // a det call: every exchanging step is one transposition, so their parity is the parity of the final row map
+    if (det.on() && p.pivoting) launch_det_parity(ws.orig, np, batch, det.parity, guard, stream);
+    if (!d_inv) return hipGetLastError();  // determinant only (det calls): nothing to un-permute
     // over ALL np entries: orig is a permutation of [0, np), so every invp[j] is defined and in range
     launch_invert_perm(ws.orig, ws.invp, np, batch, guard, stream);
     {

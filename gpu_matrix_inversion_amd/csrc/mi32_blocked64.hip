@@ -138,118 +138,20 @@ __global__ __launch_bounds__(kB64Threads) void b64_panel_step_kernel(
     const PivotRec<double> *__restrict__ keys_in, PivotRec<double> *__restrict__ keys_out, int npart,
     int *__restrict__ orig, int *__restrict__ rowmap, int *__restrict__ status)
 {
-    constexpr int TY = kB64Threads / TX;  // rows per pass
-    __shared__ PivotRec<double> s_key[kB64Threads / 64];
-    const int b = blockIdx.z;
-    const int tid = threadIdx.x;
-    const double *src = src_all + (size_t)b * wstride;
-    double *dst = dst_all + (size_t)b * wstride;
-
-    const int tx = tid % TX, ty = tid / TX;
-    const int j4 = col_lo + tx * 4;
-    const int rc = r - j4;  // component of column r inside this thread's group, if 0..3
-    const bool has_r = (rc >= 0 && rc < 4);
-    const int nc = r + 1 - j4;
-    const bool has_next = (nc >= 0 && nc < 4);  // column r + 1 belongs to this window and this thread
-    const int row0 = blockIdx.y * TR;
-
-    // The step is a chain of dependent global-memory round trips (records -> pivot row -> rows): this workgroup's
-    // rows do not depend on the pivot search (but for the one row that receives the old row r), so they are
-    // requested FIRST and arrive while the records are reduced and the pivot row is fetched.
-    constexpr int NP = (TR + TY - 1) / TY;  // passes over the rows
-    double fv[NP];
-    Vec4<double> vv[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int i = row0 + ty + q * TY;
-        const bool ok = (ty + q * TY < TR) && (i < np);
-        fv[q] = ok ? src[(size_t)i * ld + r] : 0.0;
-        vv[q] = ok ? *reinterpret_cast<const Vec4<double> *>(src + (size_t)i * ld + j4) : Vec4<double>{0.0, 0.0, 0.0, 0.0};
-    }
-
-    // finalMaxPivot: reduce the per-row-tile records of column r
-    PivotRec<double> k = PivotRec<double>::none();
-    for (int t = tid; t < npart; t += kB64Threads) {
-        const PivotRec<double> o = keys_in[(size_t)b * npart + t];
-        k = decltype(k)::best_of(o, k);
-    }
-    k = wave_max_rec<double>(k);
-    if ((tid & 63) == 0) s_key[tid >> 6] = k;
-    __syncthreads();
-    {
-        const PivotRec<double> a = PivotRec<double>::best_of(s_key[0], s_key[1]);
-        const PivotRec<double> c = PivotRec<double>::best_of(s_key[2], s_key[3]);
-        k = decltype(k)::best_of(a, c);
-    }
-    const int p = k.row(r);
-    const double piv = src[(size_t)p * ld + r];  // read before the swap, as mat_inv_32.cpp:70,129-130
-
-    // fixRow: the normalised pivot row slice (IEEE division), identity entry -> 1/piv
-    Vec4<double> prn;
-    {
-        const Vec4<double> pr = *reinterpret_cast<const Vec4<double> *>(src + (size_t)p * ld + j4);
-        prn.x = pr.x / piv;
-        prn.y = pr.y / piv;
-        prn.z = pr.z / piv;
-        prn.w = pr.w / piv;
-        if (has_r) {
-            const double one = 1.0 / piv;
-            if (rc == 0) prn.x = one; else if (rc == 1) prn.y = one; else if (rc == 2) prn.z = one; else prn.w = one;
-        }
-    }
-    // pivotElements + fixColumn over this workgroup's rows
-    PivotRec<double> best = PivotRec<double>::none();
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int i = row0 + ty + q * TY;
-        if (!((ty + q * TY < TR) && (i < np))) continue;
-        double f = fv[q];
-        Vec4<double> o = vv[q];
-        if (i == p && p != r) {  // slot p receives the old row r (the swap of pivotElements, done by redirecting the read)
-            f = src[(size_t)r * ld + r];
-            o = *reinterpret_cast<const Vec4<double> *>(src + (size_t)r * ld + j4);
-        }
-        if (i == r) {
-            o = prn;
-        } else {
-            if (has_r) {  // the implicit identity column's entry in this row
-                if (rc == 0) o.x = 0.0; else if (rc == 1) o.y = 0.0; else if (rc == 2) o.z = 0.0; else o.w = 0.0;
-            }
-            if (f != 0.0) {
-                o.x = __builtin_fma(-f, prn.x, o.x);
-                o.y = __builtin_fma(-f, prn.y, o.y);
-                o.z = __builtin_fma(-f, prn.z, o.z);
-                o.w = __builtin_fma(-f, prn.w, o.w);
-            }
-        }
-        *reinterpret_cast<Vec4<double> *>(dst + (size_t)i * ld + j4) = o;
-        if (has_next && i > r) {
-            const double v = (nc == 0) ? o.x : (nc == 1) ? o.y : (nc == 2) ? o.z : o.w;
-            const PivotRec<double> kk = PivotRec<double>::make(v, i);
-            best = decltype(best)::best_of(kk, best);
-        }
-    }
-    // maxPivot record of column r + 1 for the next launch: the TY threads (one tx) that own that column hold
-    // partial results; thread (tx, 0) folds them.  Absent at the last step of a window (column r + 1 then belongs
-    // to the next block: b64_block_prep_kernel writes its records after the rank-bw update).
-    __shared__ PivotRec<double> s_part[TY];
-    if (has_next) s_part[ty] = best;
-    __syncthreads();
-    if (has_next && ty == 0) {
-        PivotRec<double> m = s_part[0];
-#pragma unroll
-        for (int q = 1; q < TY; ++q) m = PivotRec<double>::best_of(s_part[q], m);
-        keys_out[(size_t)b * npart + blockIdx.y] = m;
-    }
-    if (blockIdx.y == 0 && tid == 0) {
-        if (p != r) {
-            int *og = orig + (size_t)b * np;
-            const int t = og[r]; og[r] = og[p]; og[p] = t;
-            int *rm = rowmap + (size_t)b * np;
-            const int t2 = rm[r]; rm[r] = rm[p]; rm[p] = t2;
-        }
-        if (status && (piv == 0.0 || piv - piv != 0.0)) status[b] = MI32_SINGULAR;  // zero, NaN or infinite pivot
-    }
+#include "mi32_b64_step_body.h"
+}
+// The det twin (mi32_inv_det_any_device_f64): the same step, and the pivot of step r to det_piv[b * det_pstride + r], an
+// exchange counted in det_parity[b].  b64_launch_step launches it only for a det call.
+template <int TX, int TR>
+__global__ __launch_bounds__(kB64Threads) void b64_panel_step_det_kernel(
+    const double *__restrict__ src_all, double *__restrict__ dst_all, int np, int ld, size_t wstride, int r, int col_lo,
+    const PivotRec<double> *__restrict__ keys_in, PivotRec<double> *__restrict__ keys_out, int npart,
+    int *__restrict__ orig, int *__restrict__ rowmap, int *__restrict__ status, double *__restrict__ det_piv,
+    size_t det_pstride, int *__restrict__ det_parity)
+{
+#define MI32_STEP_DET
+#include "mi32_b64_step_body.h"
+#undef MI32_STEP_DET
 }
 
 // ---- the rank-bw update on the fp64 matrix cores --------------------------------------------------
@@ -353,9 +255,18 @@ __global__ __launch_bounds__(256) void b64_rank_update_kernel(const double *__re
 template <int TX>
 static void b64_launch_step(const dim3 &grid, hipStream_t stream, const double *x, double *y, const Blocked64Plan &p,
                             size_t wstride, int r, int col_lo, const PivotRec<double> *kin, PivotRec<double> *kout, int *orig,
-                            int *rowmap, int *status)
+                            int *rowmap, int *status, const DetRec &det)
 {
-    if (p.tr == 8)
+    if (det.on()) {  // a det call: the twin, which also records the step's pivot
+        if (p.tr == 8)
+            hipLaunchKernelGGL((b64_panel_step_det_kernel<TX, 8>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld,
+                               wstride, r, col_lo, kin, kout, p.row_tiles, orig, rowmap, status, (double *)det.piv,
+                               det.pstride, det.parity);
+        else
+            hipLaunchKernelGGL((b64_panel_step_det_kernel<TX, 32>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld,
+                               wstride, r, col_lo, kin, kout, p.row_tiles, orig, rowmap, status, (double *)det.piv,
+                               det.pstride, det.parity);
+    } else if (p.tr == 8)
         hipLaunchKernelGGL((b64_panel_step_kernel<TX, 8>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r,
                            col_lo, kin, kout, p.row_tiles, orig, rowmap, status);
     else
@@ -364,7 +275,7 @@ static void b64_launch_step(const dim3 &grid, hipStream_t stream, const double *
 }
 
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *wsp,
-                            hipStream_t stream, Profiler *prof)
+                            hipStream_t stream, Profiler *prof, const DetRec &det)
 {
     B64Ws ws;
     b64_carve(p, batch, wsp, ws);
@@ -392,9 +303,9 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
             ProfScope ps(prof, KC_PANEL, stream);
             const int r = c0 + s;
             switch (kb) {
-                case 64: b64_launch_step<16>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status); break;
-                case 128: b64_launch_step<32>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status); break;
-                default: b64_launch_step<64>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status); break;
+                case 64: b64_launch_step<16>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status, det); break;
+                case 128: b64_launch_step<32>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status, det); break;
+                default: b64_launch_step<64>(step_grid, stream, x, y, p, ws.wstride, r, c0, kin, kout, ws.orig, ws.rowmap, d_status, det); break;
             }
             double *t = x; x = y; y = t;
             PivotRec<double> *tk = kin; kin = kout; kout = tk;
@@ -408,6 +319,7 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
             double *t = cur; cur = oth; oth = t;
         }
     }
+    if (!d_inv) return hipGetLastError();  // determinant only (det calls): nothing to un-permute
     ProfScope ps(prof, KC_FINISH, stream);
     launch_unpermute(cur, p.ld, ws.wstride, ws.orig, ws.invp, np, p.n, batch, d_inv, stream);
     return hipGetLastError();

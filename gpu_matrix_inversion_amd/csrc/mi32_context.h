@@ -77,6 +77,8 @@ struct mi32_context {
     // status words of device-resident calls that pass no status buffer: the kernels always have one to flag
     // a bad pivot or a lost panel partner in (a given-up matrix is then skipped and comes out as NaN)
     DeviceBuffer d_istatus;
+    // det calls above order 128 (mi32_inv_det_any_device*): the recorded pivots, the parity and input-flag words
+    DeviceBuffer det;
     std::mutex mu;
 };
 inline Settings settings_of(const mi32_context *h) { return h ? h->set : Settings(); }

@@ -148,7 +148,7 @@ static int create_streams(mi32_context *h)
 
 extern "C" {
 
-int mi32_version(void) { return 143; }
+int mi32_version(void) { return 144; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)
@@ -180,7 +180,7 @@ int mi32_destroy(mi32_handle_t h)
     if (!h) return MI32_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuffer *b : {&h->ws, &h->d_in, &h->d_out, &h->d_status, &h->d_istatus}) b->release();
+    for (DeviceBuffer *b : {&h->ws, &h->d_in, &h->d_out, &h->d_status, &h->d_istatus, &h->det}) b->release();
     host_copier_destroy(h->copier);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->switch_event) (void)hipEventDestroy(h->switch_event);

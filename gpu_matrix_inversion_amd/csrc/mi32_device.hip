@@ -5,6 +5,7 @@
 
 #include "mi32_apply.h"
 #include "mi32_context.h"
+#include "mi32_det_large.h"
 
 using namespace mi32;
 
@@ -38,7 +39,7 @@ static BlockedExec blocked_exec(mi32_context *h, int n)
 // The two parts of a split batch, the second on the context's split stream; the workspace holds one part per half
 // (ws_bytes_for).
 static int blocked_invert_split(mi32_context *h, const BlockedRoute &r, const BlockedExec &ex, const float *d_a, float *d_inv,
-                                int *d_status)
+                                int *d_status, const DetRec &det = DetRec())
 {
     const int b0 = r.part_batch[0];
     const size_t mat = (size_t)r.n * r.n;
@@ -49,8 +50,15 @@ static int blocked_invert_split(mi32_context *h, const BlockedRoute &r, const Bl
     MI32_HIP(hipStreamWaitEvent(h->split_stream, h->la_events[0], 0));
     BlockedExec ex1 = ex;
     ex1.stream = h->split_stream;
-    hipError_t e = blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex);
-    if (e == hipSuccess) e = blocked_invert(r, 1, d_a + (size_t)b0 * mat, d_inv + (size_t)b0 * mat, d_status + b0, ws1, ex1);
+    // a det call: the second part's pivots and parities follow the first part's; its inverse may be absent
+    DetRec det1 = det;
+    if (det.on()) {
+        det1.piv = (float *)det.piv + (size_t)b0 * det.pstride;
+        det1.parity = det.parity + b0;
+    }
+    float *inv1 = d_inv ? d_inv + (size_t)b0 * mat : nullptr;
+    hipError_t e = blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex, det);
+    if (e == hipSuccess) e = blocked_invert(r, 1, d_a + (size_t)b0 * mat, inv1, d_status + b0, ws1, ex1, det1);
     MI32_HIP(hipEventRecord(h->la_events[1], h->split_stream));
     MI32_HIP(hipStreamWaitEvent(h->stream, h->la_events[1], 0));
     return hip_status(e, "kernel launch");
@@ -118,6 +126,95 @@ static int inv_det_device(mi32_context *h, const T *d_a, int n, int batch, T *d_
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, DetOut{d_det_mant, d_det_exp});
+}
+
+// ---- the determinant above kWorkgroupMaxOrder: the route mi32_inv_device* would run, which records its pivots ----------
+// The context's det memory for this call (grown on demand, never part of the workspace), its flag and parity words
+// zeroed and the input scanned on the main stream.  Two det calls back to back are ordered by that stream: the finish
+// kernel of the first is enqueued there before the memset of the second.
+template <typename T>
+static int det_begin(mi32_context *h, const T *d_a, int n, int np, int batch, DetMem *dm, DetRec *rec)
+{
+    MI32_TRY(h->det.ensure(h, det_bytes(np, batch, sizeof(T))));
+    *dm = det_carve(h->det.ptr, np, batch, sizeof(T));
+    MI32_HIP(hipMemsetAsync(dm->flag, 0, (size_t)((char *)dm->piv - (char *)dm->flag), h->stream));
+    ProfScope ps(h->prof, KC_FINISH, h->stream);
+    launch_det_scan(d_a, n, batch, dm->flag, h->stream);
+    *rec = DetRec{dm->piv, dm->pstride, dm->parity};
+    return MI32_OK;
+}
+// enqueued last on the main stream: the recurrence over the steps first ... first + n - 1 of every list
+template <typename T>
+static int det_end(mi32_context *h, hipError_t route, const DetMem &dm, int first, int n, int batch, const int *d_status,
+                   bool pivoting, const DetOut out)
+{
+    MI32_TRY(hip_status(route, "kernel launch"));
+    ProfScope ps(h->prof, KC_FINISH, h->stream);
+    launch_det_finish((const T *)dm.piv, dm.pstride, first, n, dm.parity, dm.flag, d_status, pivoting, out, batch, h->stream);
+    return hip_status(hipGetLastError(), "kernel launch");
+}
+
+// inv_device with the determinant, n > kWorkgroupMaxOrder (so the sweep or the blocked path); d_inv may be null
+static int inv_det_large(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                         const DetOut out)
+{
+    const int algo = resolve_algo(s, n, sizeof(float));
+    MI32_TRY(h->ws.ensure(h, ws_bytes_for(s, n, batch, algo)));
+    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
+    DetMem dm;
+    DetRec rec;
+    if (algo == MI32_ALGO_SWEEP) {
+        MI32_TRY(det_begin(h, d_a, n, n, batch, &dm, &rec));
+        const hipError_t e =
+            sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting, rec);
+        return det_end<float>(h, e, dm, 0, n, batch, d_status, s.pivoting, out);
+    }
+    const BlockedRoute r = route_of(h, s, n, batch);
+    const BlockedExec ex = blocked_exec(h, n);
+    MI32_TRY(det_begin(h, d_a, n, r.np, batch, &dm, &rec));
+    if (r.parts == 2)
+        MI32_TRY(blocked_invert_split(h, r, ex, d_a, d_inv, d_status, rec));
+    else
+        MI32_TRY(hip_status(blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex, rec), "kernel launch"));
+    // the padding comes first on this path: its steps (pivot 1, no exchange) are skipped by index
+    return det_end<float>(h, hipSuccess, dm, r.np - n, n, batch, d_status, s.pivoting, out);
+}
+
+static int inv_det_large(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                         const DetOut out)
+{
+    const bool blocked = resolve_algo(s, n, sizeof(double)) == MI32_ALGO_BLOCKED;
+    const bool nopivot = blocked && !s.pivoting;
+    const Blocked64Plan bp = make_blocked64_plan(n, block_w64(s));
+    const NoPivot64Plan npp = make_nopivot64_plan(n, block_w64(s));
+    const SweepPlan sp = make_sweep_plan(n);
+    MI32_TRY(h->ws.ensure(h, nopivot ? nopivot64_workspace_bytes(npp, batch)
+                             : blocked ? blocked64_workspace_bytes(bp, batch)
+                                       : sweep_workspace_bytes(sp, batch, sizeof(double))));
+    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
+    DetMem dm;
+    DetRec rec;
+    // the fp64 blocked paths pad behind the matrix: the first n steps are the matrix's
+    MI32_TRY(det_begin(h, d_a, n, nopivot ? npp.np : blocked ? bp.np : n, batch, &dm, &rec));
+    const hipError_t e =
+        nopivot   ? nopivot64_invert(npp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec)
+        : blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec)
+                  : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting, rec);
+    return det_end<double>(h, e, dm, 0, n, batch, d_status, s.pivoting, out);
+}
+
+// the inverse with the determinant at any order (see the header): up to kWorkgroupMaxOrder mi32_inv_det_device*, above
+// the route mi32_inv_device* runs on this context; the arguments are checked before the context is touched
+template <typename T>
+static int inv_det_any_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, double *d_det_mant,
+                              int *d_det_exp)
+{
+    if (!h || !d_a || n <= 0 || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const DetOut out{d_det_mant, d_det_exp};
+    if (n <= kWorkgroupMaxOrder) return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, out);
+    return inv_det_large(h, h->set, d_a, n, batch, d_inv, d_status, out);
 }
 
 // A X = B on the one-launch paths: one launch per chunk of columns (solve_walk); every launch repeats the elimination
@@ -229,6 +326,18 @@ int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch
                             double *d_det_mant, int *d_det_exp)
 {
     return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_any_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                            double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_any_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+}
+
+int mi32_inv_det_any_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                                double *d_det_mant, int *d_det_exp)
+{
+    return inv_det_any_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const float *d_b, int nrhs, float *d_x,

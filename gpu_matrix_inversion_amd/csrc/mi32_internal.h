@@ -195,6 +195,16 @@ inline PanelInstance panel_instance(const BlockedRoute &r, int blk, int s)
     return pi;
 }
 
+// Above kWorkgroupMaxOrder (mi32_inv_det_any_device*, mi32_det_large.h) the pivots are spread over launches: what a det
+// call hands to a sweep / blocked route, which records every step's pivot there.  Empty: a plain call, which enqueues
+// exactly the launches it always did.
+struct DetRec {
+    void *piv = nullptr;    // element type of the route; matrix b's pivot of (padded) step r at piv[b * pstride + r]
+    size_t pstride = 0;     // elements per matrix, >= the route's padded order
+    int *parity = nullptr;  // int[batch], zeroed on the stream before the route runs; bit 0: an odd number of exchanges
+    bool on() const { return piv != nullptr; }
+};
+
 SweepPlan make_sweep_plan(int n);
 
 size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes);
@@ -206,7 +216,7 @@ size_t blocked_workspace_bytes(const BlockedRoute &r, int batch);  // of `batch`
 // pivoting = false: the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10), the diagonal entry is the pivot
 template <typename T>
 hipError_t sweep_invert(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, void *ws,
-                        hipStream_t stream, Profiler *prof, bool pivoting = true);
+                        hipStream_t stream, Profiler *prof, bool pivoting = true, const DetRec &det = DetRec());
 // fp64 blocked path (mi32_blocked64.hip): windowed sweep steps + rank-bw updates on the fp64 matrix cores
 struct Blocked64Plan {
     int n, np, ld;  // matrix order, padded order (multiple of 64, identity padding), row stride in doubles
@@ -217,7 +227,7 @@ struct Blocked64Plan {
 Blocked64Plan make_blocked64_plan(int n, int bw);
 size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch);
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
-                            hipStream_t stream, Profiler *prof);
+                            hipStream_t stream, Profiler *prof, const DetRec &det = DetRec());
 // makeAugmented counterpart of the fp64 blocked paths: w0 <- diag(A, I) (np x np, row stride ld, wstride doubles per
 // matrix), orig <- the identity, status[b] <- MI32_SINGULAR for a non-finite input entry (status may be null)
 void launch_b64_init(const double *d_a, int n, int np, int ld, size_t wstride, double *w0, int *orig, int batch,
@@ -232,7 +242,7 @@ struct NoPivot64Plan {
 NoPivot64Plan make_nopivot64_plan(int n, int bw);
 size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch);
 hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
-                            hipStream_t stream, Profiler *prof);
+                            hipStream_t stream, Profiler *prof, const DetRec &det = DetRec());
 
 // register-resident path (mi32_resident.hip): orders up to kResidentMaxOrder, one launch, no workspace.  A group of
 // resident_lanes(n) lanes (8 / 16 / 32 / 64; 0 when the order is out of range) holds one matrix; d_status must not
@@ -405,8 +415,9 @@ struct BlockedExec {
     Profiler *prof = nullptr;
 };
 // enqueues part `part` of the route: its r.part_batch[part] members at d_a / d_inv / d_status, in the workspace ws
+// det (a det call only): the pivots of the part's members; d_inv may then be null (determinant only)
 hipError_t blocked_invert(const BlockedRoute &r, int part, const float *d_a, float *d_inv, int *d_status, void *ws,
-                          const BlockedExec &ex);
+                          const BlockedExec &ex, const DetRec &det = DetRec());
 // getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths (mi32_sweep.hip).  Working
 // column c holds inverse column orig[c].  orig and invp hold np entries per matrix, np apart.
 // invp <- the inverse of orig; a matrix whose guard word is MI32_RUNTIME_ERROR is skipped (guard may be null).

@@ -333,8 +333,8 @@ __global__ __launch_bounds__(256) void np64_rank_update_kernel(double *__restric
 }
 
 template <int BW>
-static void np64_run_blocks(const NoPivot64Plan &p, const NP64Ws &ws, int batch, int *d_status, hipStream_t stream,
-                            Profiler *prof)
+static hipError_t np64_run_blocks(const NoPivot64Plan &p, const NP64Ws &ws, int batch, int *d_status, hipStream_t stream,
+                                  Profiler *prof, const DetRec &det)
 {
     const int np = p.np;
     for (int c0 = 0; c0 < np; c0 += BW) {
@@ -342,6 +342,14 @@ static void np64_run_blocks(const NoPivot64Plan &p, const NP64Ws &ws, int batch,
             ProfScope ps(prof, KC_PANEL, stream);
             hipLaunchKernelGGL((np64_diag_kernel<BW>), dim3(batch), dim3(8 * BW), 0, stream, ws.w, p.ld, ws.wstride, c0,
                                ws.ft, ws.ub, np, ws.fstride, ws.piv, d_status);
+        }
+        if (det.on()) {  // a det call: the block's pivots (ws.piv, BW per matrix) into the per-matrix list, before the
+                         // next block's diagonal kernel overwrites them
+            ProfScope ps(prof, KC_FINISH, stream);
+            const hipError_t e = hipMemcpy2DAsync((double *)det.piv + c0, det.pstride * sizeof(double), ws.piv,
+                                                  (size_t)BW * sizeof(double), (size_t)BW * sizeof(double), batch,
+                                                  hipMemcpyDeviceToDevice, stream);
+            if (e != hipSuccess) return e;
         }
         if (np == BW) break;  // one block: nothing outside it
         {
@@ -355,10 +363,11 @@ static void np64_run_blocks(const NoPivot64Plan &p, const NP64Ws &ws, int batch,
                                ws.ub, np, p.ld, ws.wstride, ws.fstride, c0, BW);
         }
     }
+    return hipSuccess;
 }
 
 hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *wsp,
-                            hipStream_t stream, Profiler *prof)
+                            hipStream_t stream, Profiler *prof, const DetRec &det)
 {
     NP64Ws ws;
     np64_carve(p, batch, wsp, ws);
@@ -370,10 +379,10 @@ hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d
         ProfScope ps(prof, KC_INIT, stream);  // diag(A, I) into the working copy, non-finite input -> MI32_SINGULAR
         launch_b64_init(d_a, p.n, p.np, p.ld, ws.wstride, ws.w, ws.orig, batch, d_status, stream);
     }
-    if (p.bw == 128)
-        np64_run_blocks<128>(p, ws, batch, d_status, stream, prof);
-    else
-        np64_run_blocks<64>(p, ws, batch, d_status, stream, prof);
+    e = p.bw == 128 ? np64_run_blocks<128>(p, ws, batch, d_status, stream, prof, det)
+                    : np64_run_blocks<64>(p, ws, batch, d_status, stream, prof, det);
+    if (e != hipSuccess) return e;
+    if (!d_inv) return hipGetLastError();  // determinant only (det calls): nothing to copy out
     ProfScope ps(prof, KC_FINISH, stream);  // orig is the identity: a plain copy-out of the N x N corner
     launch_unpermute(ws.w, p.ld, ws.wstride, ws.orig, ws.invp, p.np, p.n, batch, d_inv, stream);
     return hipGetLastError();

@@ -159,97 +159,19 @@ __global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_kernel(const T *_
                                                                        int npart, int *__restrict__ orig,
                                                                        int *__restrict__ status)
 {
-    __shared__ PivotRec<T> s_key[kSweepThreads / 64];
-    const int b = blockIdx.z;
-    const int tid = threadIdx.x;
-    const T *src = src_all + (size_t)b * wstride;
-    T *dst = dst_all + (size_t)b * wstride;
-
-    // 1. finalMaxPivot: reduce the per-row-tile records of column r
-    int p = r;
-    if constexpr (PIVOT) {
-        PivotRec<T> k = PivotRec<T>::none();
-        for (int t = tid; t < npart; t += kSweepThreads) {
-            const PivotRec<T> o = keys_in[(size_t)b * npart + t];
-            k = decltype(k)::best_of(o, k);
-        }
-        k = wave_max_rec<T>(k);
-        if ((tid & 63) == 0) s_key[tid >> 6] = k;
-        __syncthreads();
-        {
-            const PivotRec<T> a = PivotRec<T>::best_of(s_key[0], s_key[1]);
-            const PivotRec<T> c = PivotRec<T>::best_of(s_key[2], s_key[3]);
-            k = decltype(k)::best_of(a, c);
-        }
-        p = k.row(r);
-    }
-    const T piv = src[(size_t)p * ld + r];  // read before the swap, as mat_inv_32.cpp:70,129-130
-
-    const int j4 = (blockIdx.x * kSweepThreads + tid) * 4;
-    const bool active = j4 < ld;
-    const int rc = r - j4;                   // component of column r inside this thread's group, if 0..3
-    const bool has_r = (rc >= 0 && rc < 4);
-    const int nc = r + 1 - j4;               // component of column r+1
-    const bool has_next = PIVOT && (nc >= 0 && nc < 4) && (r + 1 < n);
-    const int row0 = blockIdx.y * TR;
-
-    // 2. fixRow: the normalised pivot row slice (IEEE division), identity entry -> 1/piv
-    const Vec4<T> zero4 = {T(0), T(0), T(0), T(0)};
-    Vec4<T> prn = zero4;
-    if (active) {
-        const Vec4<T> pr = *reinterpret_cast<const Vec4<T> *>(src + (size_t)p * ld + j4);
-        prn.x = pr.x / piv;
-        prn.y = pr.y / piv;
-        prn.z = pr.z / piv;
-        prn.w = pr.w / piv;
-        if (has_r) set_comp<T>(prn, rc, T(1) / piv);
-    }
-
-    // 3. pivotElements + fixColumn over this workgroup's rows
-    PivotRec<T> best = PivotRec<T>::none();
-#pragma unroll
-    for (int u0 = 0; u0 < TR; u0 += 4) {
-        T f[4];
-        Vec4<T> v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = row0 + u0 + u;
-            const int s = (i == p) ? r : i;  // slot p receives the old row r
-            const bool ok = (i < n);
-            f[u] = ok ? src[(size_t)s * ld + r] : T(0);
-            v[u] = (ok && active) ? *reinterpret_cast<const Vec4<T> *>(src + (size_t)s * ld + j4) : zero4;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = row0 + u0 + u;
-            if (i >= n || !active) continue;
-            Vec4<T> o;
-            if (i == r) {
-                o = prn;
-            } else {
-                o = v[u];
-                if (has_r) set_comp<T>(o, rc, T(0));  // the implicit identity column's entry in this row
-                if (f[u] != T(0)) o = fma4_neg<T>(f[u], prn, o);
-            }
-            *reinterpret_cast<Vec4<T> *>(dst + (size_t)i * ld + j4) = o;
-            if (has_next && i > r) {
-                const PivotRec<T> kk = PivotRec<T>::make(comp<T>(o, nc), i);
-                best = decltype(best)::best_of(kk, best);
-            }
-        }
-    }
-    // 4. maxPivot record of column r+1 for the next launch
-    if (has_next && active) keys_out[(size_t)b * npart + blockIdx.y] = best;
-
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-        if (p != r) {
-            int *og = orig + (size_t)b * n;
-            const int t = og[r];
-            og[r] = og[p];
-            og[p] = t;
-        }
-        if (status && (piv == T(0) || piv - piv != T(0))) status[b] = MI32_SINGULAR;  // zero, NaN or infinite pivot
-    }
+#include "mi32_sweep_step_body.h"
+}
+// The det twin (mi32_inv_det_any_device*): the same step, and the pivot of step r to det_piv[b * det_pstride + r], an
+// exchange counted in det_parity[b].  sweep_run launches it only for a det call.
+template <typename T, int TR, bool PIVOT>
+__global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_det_kernel(
+    const T *__restrict__ src_all, T *__restrict__ dst_all, int n, int ld, size_t wstride, int r,
+    const PivotRec<T> *__restrict__ keys_in, PivotRec<T> *__restrict__ keys_out, int npart, int *__restrict__ orig,
+    int *__restrict__ status, T *__restrict__ det_piv, size_t det_pstride, int *__restrict__ det_parity)
+{
+#define MI32_STEP_DET
+#include "mi32_sweep_step_body.h"
+#undef MI32_STEP_DET
 }
 
 // ---- getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths -------------
@@ -301,7 +223,7 @@ template void launch_unpermute(const double *, int, size_t, const int *, int *, 
 
 template <typename T, int TR>
 static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, const SweepWs &ws,
-                            hipStream_t stream, Profiler *prof, bool pivoting)
+                            hipStream_t stream, Profiler *prof, bool pivoting, const DetRec &det)
 {
     const dim3 grid(p.col_tiles, p.row_tiles, batch);
     const dim3 block(kSweepThreads);
@@ -319,7 +241,16 @@ static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batc
     for (int r = 0; r < p.n; ++r) {
         const bool even = (r % 2) == 0;
         ProfScope ps(prof, KC_SWEEP_STEP, stream);
-        if (pivoting)
+        if (det.on()) {  // a det call: the twin, which also records the step's pivot
+            if (pivoting)
+                hipLaunchKernelGGL((gj_sweep_step_det_kernel<T, TR, true>), grid, block, 0, stream, even ? w0 : w1,
+                                   even ? w1 : w0, p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles,
+                                   ws.orig, d_status, (T *)det.piv, det.pstride, det.parity);
+            else
+                hipLaunchKernelGGL((gj_sweep_step_det_kernel<T, TR, false>), grid, block, 0, stream, even ? w0 : w1,
+                                   even ? w1 : w0, p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles,
+                                   ws.orig, d_status, (T *)det.piv, det.pstride, det.parity);
+        } else if (pivoting)
             hipLaunchKernelGGL((gj_sweep_step_kernel<T, TR, true>), grid, block, 0, stream, even ? w0 : w1, even ? w1 : w0,
                                p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles, ws.orig, d_status);
         else
@@ -327,6 +258,7 @@ static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batc
                                p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles, ws.orig, d_status);
     }
     const T *fin = (p.n % 2 == 0) ? w0 : w1;  // the last-written copy (mat_inv_32.cpp:369-372)
+    if (!d_inv) return hipGetLastError();   // determinant only (det calls): nothing to un-permute
     ProfScope ps(prof, KC_FINISH, stream);
     launch_unpermute(fin, p.ld, ws.wstride, ws.orig, ws.invp, p.n, p.n, batch, d_inv, stream);
     return hipGetLastError();
@@ -334,18 +266,20 @@ static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batc
 
 template <typename T>
 hipError_t sweep_invert(const SweepPlan &p, const T *d_a, T *d_inv, int batch, int *d_status, void *wsp,
-                        hipStream_t stream, Profiler *prof, bool pivoting)
+                        hipStream_t stream, Profiler *prof, bool pivoting, const DetRec &det)
 {
     SweepWs ws;
     sweep_carve(p, batch, wsp, ws, sizeof(T));
     switch (p.tr) {
-        case 4: return sweep_run<T, 4>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
-        case 8: return sweep_run<T, 8>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
-        case 16: return sweep_run<T, 16>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
-        default: return sweep_run<T, 32>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting);
+        case 4: return sweep_run<T, 4>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting, det);
+        case 8: return sweep_run<T, 8>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting, det);
+        case 16: return sweep_run<T, 16>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting, det);
+        default: return sweep_run<T, 32>(p, d_a, d_inv, batch, d_status, ws, stream, prof, pivoting, det);
     }
 }
-template hipError_t sweep_invert(const SweepPlan &, const float *, float *, int, int *, void *, hipStream_t, Profiler *, bool);
-template hipError_t sweep_invert(const SweepPlan &, const double *, double *, int, int *, void *, hipStream_t, Profiler *, bool);
+template hipError_t sweep_invert(const SweepPlan &, const float *, float *, int, int *, void *, hipStream_t, Profiler *, bool,
+                                 const DetRec &);
+template hipError_t sweep_invert(const SweepPlan &, const double *, double *, int, int *, void *, hipStream_t, Profiler *, bool,
+                                 const DetRec &);
 
 }  // namespace mi32

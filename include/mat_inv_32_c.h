@@ -205,6 +205,23 @@ int mi32_inv_det_device(mi32_handle_t h, const float *d_a, int n, int batch, flo
                         double *d_det_mant, int *d_det_exp);
 int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
                             double *d_det_mant, int *d_det_exp);
+/* The same pair at ANY order mi32_inv_device* takes.  1 <= n <= 128: exactly mi32_inv_det_device*, same kernels, same
+ * bits.  Above, the call runs the route mi32_inv_device* would run on this context -- the same algorithm setting,
+ * blocking, pivoting setting, look-ahead and batch split -- and adds the determinant: every step's pivot is recorded
+ * in step order (it is in global memory after each launch, or one register away in a step kernel, whose det twin
+ * stores it), and one small kernel per call runs the recurrence above over a member's list.  The row exchanges enter as
+ * one parity at the end, which gives the same bits as a flip per step (IEEE multiplication and frexp are
+ * sign-symmetric); the identity padding's steps (pivot 1, no exchange) are left out.  A member given up with
+ * MI32_RUNTIME_ERROR by a shared panel: (NaN, 0).  Inverse and status are those of mi32_inv_device* bit for bit.
+ * d_inv == NULL: the elimination runs, the final un-permutation and store are skipped.  A null handle, input,
+ * d_det_mant or d_det_exp, n <= 0, batch <= 0 or d_a == d_inv -> MI32_BAD_SHAPE, decided before the context is
+ * touched.  The pivot lists live in memory the context owns for these calls (4 or 8 bytes per padded row and member,
+ * grown on demand; mi32_workspace_bytes and mi32_reserve do not count it); calls on one context are ordered by its
+ * stream.  The added launches are recorded under profiling class 5. */
+int mi32_inv_det_any_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
+                            double *d_det_mant, int *d_det_exp);
+int mi32_inv_det_any_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
+                                double *d_det_mant, int *d_det_exp);
 int mi32_inv_det_device_vbatched(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda,
                                  float *const *d_inv, const int *d_ldinv, int *d_status, double *d_det_mant,
                                  int *d_det_exp);

@@ -378,9 +378,10 @@ class Inverter:
     def reserve(self, n: int, batch: int = 1):
         _lib.check(self._lib.mi32_reserve(self._h, int(n), int(batch)), "mi32_reserve")
 
-    def _batch_args(self, a, out, status, want_inverse=True, max_order=None, too_large=None):
-        """The argument handling ``inv`` and ``inv_det`` share: ``(squeeze, a3, out, status)`` with ``a3`` the contiguous
-        (B,N,N) input, ``out`` the (B,N,N) output (None with ``want_inverse=False``) and ``status`` int32[B]."""
+    def _batch_args(self, a, out, status, want_inverse=True, max_order=None):
+        """The argument handling of ``_dense``: ``(squeeze, a3, out, status)`` with ``a3`` the contiguous (B,N,N) input,
+        ``out`` the (B,N,N) output (None with ``want_inverse=False``) and ``status`` int32[B].  ``max_order``: the
+        largest order ``inv_det`` takes."""
         torch = self._torch
         if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
             raise ValueError("expected a float32 or float64 tensor on the GPU")
@@ -389,7 +390,7 @@ class Inverter:
         if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
             raise ValueError("expected (N,N) or (B,N,N)")
         if max_order is not None and a3.shape[1] > max_order:
-            raise ValueError(too_large)
+            raise ValueError(f"inv_det takes orders up to {max_order}")
         a3 = a3.contiguous()
         b, n = a3.shape[0], a3.shape[1]
         if not want_inverse:
@@ -408,13 +409,27 @@ class Inverter:
     def inv(self, a, out=None, status=None):
         """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin; sweep or blocked as resolved_blocking_f64
         reports) contiguous tensor on this device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
-        squeeze, a3, out, status = self._batch_args(a, out, status)
+        return self._dense("mi32_inv_device", a, out, status)
+
+    def _dense(self, stem, a, out, status, want_inverse=True, max_order=None, det=False):
+        """The one call behind ``inv``, ``inv_det`` and ``inv_det_any``: the arguments checked (``_batch_args``), then
+        the C entry point ``stem`` (float32) or ``stem + "_f64"`` on torch's current stream.  Returns ``(inverse,
+        status)``; with ``det`` the entry point takes the two determinant arrays as well and they are returned behind,
+        the inverse being None with ``want_inverse=False``."""
+        torch = self._torch
+        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse, max_order)
         b, n = a3.shape[0], a3.shape[1]
+        pair = ptrs = ()
+        if det:
+            pair = (torch.empty(b, dtype=torch.float64, device=a3.device),
+                    torch.empty(b, dtype=torch.int32, device=a3.device))
+            ptrs = (ctypes.c_void_p(pair[0].data_ptr()), ctypes.c_void_p(pair[1].data_ptr()))
         self._bind_stream()
-        fn = self._lib.mi32_inv_device if a.dtype == self._torch.float32 else self._lib.mi32_inv_device_f64
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b, ctypes.c_void_p(out.data_ptr()),
-                      ctypes.c_void_p(status.data_ptr())), "mi32_inv_device")
-        return (out[0] if squeeze else out), status
+        fn = getattr(self._lib, stem if a.dtype == torch.float32 else stem + "_f64")
+        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
+                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
+                      *ptrs), stem)
+        return ((None if out is None else out[0] if squeeze else out), status) + pair
 
     def inv_det(self, a, out=None, status=None, want_inverse=True):
         """The inverse and the determinant of every member from one launch.  a: (N,N) or (B,N,N) float32 / float64 on
@@ -425,17 +440,7 @@ class Inverter:
         otherwise.  Inverse and status are those of ``inv`` bit for bit.  Always runs on the register-resident
         (N <= 64) or workgroup-resident kernels, whatever ``algo`` is.  ``want_inverse=False``: the determinant-only
         form, the inverse is not stored and None is returned in its place.  Asynchronous on torch's current stream."""
-        torch = self._torch
-        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse, 128, "inv_det takes orders up to 128")
-        b, n = a3.shape[0], a3.shape[1]
-        det_mant = torch.empty(b, dtype=torch.float64, device=a3.device)
-        det_exp = torch.empty(b, dtype=torch.int32, device=a3.device)
-        self._bind_stream()
-        fn = self._lib.mi32_inv_det_device if a.dtype == torch.float32 else self._lib.mi32_inv_det_device_f64
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
-                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
-                      ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())), "mi32_inv_det_device")
-        return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
+        return self._dense("mi32_inv_det_device", a, out, status, want_inverse, max_order=128, det=True)
 
     def inv_det_any(self, a, out=None, status=None, want_inverse=True):
         """``inv_det`` at any order ``inv`` takes.  Up to N = 128 it is ``inv_det``, same kernels and same bits.  Above,
@@ -445,18 +450,7 @@ class Inverter:
         Returns ``(inverse, status, det_mant, det_exp)``.  ``want_inverse=False``: the elimination runs, the final
         un-permutation and store are skipped, and None is returned for the inverse.  Asynchronous on torch's current
         stream."""
-        torch = self._torch
-        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse)
-        b, n = a3.shape[0], a3.shape[1]
-        det_mant = torch.empty(b, dtype=torch.float64, device=a3.device)
-        det_exp = torch.empty(b, dtype=torch.int32, device=a3.device)
-        self._bind_stream()
-        fn = self._lib.mi32_inv_det_any_device if a.dtype == torch.float32 else self._lib.mi32_inv_det_any_device_f64
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
-                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
-                      ctypes.c_void_p(det_mant.data_ptr()), ctypes.c_void_p(det_exp.data_ptr())),
-                   "mi32_inv_det_any_device")
-        return (None if out is None else out[0] if squeeze else out), status, det_mant, det_exp
+        return self._dense("mi32_inv_det_any_device", a, out, status, want_inverse, det=True)
 
     def resolved_solve(self, n: int, nrhs: int, elem_bytes: int = 4):
         """(columns per launch, launches, lanes per member, register rows per thread) of ``solve`` for this shape: a

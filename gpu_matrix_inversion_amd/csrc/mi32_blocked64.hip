@@ -257,21 +257,16 @@ static void b64_launch_step(const dim3 &grid, hipStream_t stream, const double *
                             size_t wstride, int r, int col_lo, const PivotRec<double> *kin, PivotRec<double> *kout, int *orig,
                             int *rowmap, int *status, const DetRec &det)
 {
-    if (det.on()) {  // a det call: the twin, which also records the step's pivot
-        if (p.tr == 8)
-            hipLaunchKernelGGL((b64_panel_step_det_kernel<TX, 8>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld,
-                               wstride, r, col_lo, kin, kout, p.row_tiles, orig, rowmap, status, (double *)det.piv,
-                               det.pstride, det.parity);
-        else
-            hipLaunchKernelGGL((b64_panel_step_det_kernel<TX, 32>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld,
-                               wstride, r, col_lo, kin, kout, p.row_tiles, orig, rowmap, status, (double *)det.piv,
-                               det.pstride, det.parity);
-    } else if (p.tr == 8)
-        hipLaunchKernelGGL((b64_panel_step_kernel<TX, 8>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r,
-                           col_lo, kin, kout, p.row_tiles, orig, rowmap, status);
+    // the step's arguments, once; rec: what the det twin takes behind them
+    const auto launch = [&](auto kernel, auto... rec) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r, col_lo, kin, kout,
+                           p.row_tiles, orig, rowmap, status, rec...);
+    };
+    if (det.on())  // a det call: the twin, which also records the step's pivot
+        launch(p.tr == 8 ? b64_panel_step_det_kernel<TX, 8> : b64_panel_step_det_kernel<TX, 32>, (double *)det.piv,
+               det.pstride, det.parity);
     else
-        hipLaunchKernelGGL((b64_panel_step_kernel<TX, 32>), grid, dim3(kB64Threads), 0, stream, x, y, p.np, p.ld, wstride, r,
-                           col_lo, kin, kout, p.row_tiles, orig, rowmap, status);
+        launch(p.tr == 8 ? b64_panel_step_kernel<TX, 8> : b64_panel_step_kernel<TX, 32>);
 }
 
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *wsp,

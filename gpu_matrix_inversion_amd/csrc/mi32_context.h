@@ -1,8 +1,10 @@
 // mi32_context.h -- what the host units of libmat_inv_32.so share: the context, the settings launch planning reads,
 // the grow-only device buffer, error reporting, and the declarations that cross unit boundaries.
-//   mi32_plan.hip     launch planning, pure host code: no HIP runtime call, no context
+//   mi32_plan.hip     launch planning, pure host code: no HIP runtime call, no context; a dense call is planned once,
+//                     as a DenseRoute
 //   mi32_context.hip  context life cycle, setters, workspace, profiler
-//   mi32_device.hip   the device-pointer entry points
+//   mi32_device.hip   the device-pointer entry points; one inv_device<T> enqueues every DenseRoute, with or without the
+//                     determinant
 //   mi32_hostptr.hip  the host-pointer entry points and the C++ drop-ins of the reference's headers
 #pragma once
 #include <cstdlib>
@@ -99,8 +101,29 @@ inline mi32::BlockedRoute route_of(const mi32_context *h, const Settings &s, int
 {
     return plan_route(s, n, batch, !h || h->aux_stream, !h || h->split_stream);
 }
-int block_w64(const Settings &s);
-size_t ws_bytes_for(const Settings &s, int n, int batch, int algo);  // fp32
+// How one dense call (a uniform batch at device pointers) runs, decided once: the path, the one plan object that path
+// carves and launches with, the workspace the call ensures, and what a det call must know of the path's pivot list.
+// dense_route composes resolve_algo, plan_route, block_w64 and the make_*_plan functions and holds no rule of its own;
+// mi32_inv_device*, mi32_inv_det_any_device*, mi32_workspace_bytes, mi32_reserve and the mi32_resolve_* queries all
+// read this one description.
+struct DenseRoute {
+    enum Path { RESIDENT, WORKGROUP, SWEEP, BLOCKED32, BLOCKED64, NOPIVOT64 } path;
+    union {  // the member `path` names; none on the two one-launch paths
+        mi32::SweepPlan sweep;
+        mi32::BlockedRoute blocked;
+        mi32::Blocked64Plan blocked64;
+        mi32::NoPivot64Plan nopivot64;
+    };
+    // The path's *_workspace_bytes of the plan above.  fp32: at least the residual check's share; BLOCKED32: the larger
+    // of the whole batch and the two halves of a split, reserved whether or not this call splits.
+    size_t ws_bytes;
+    int det_steps;  // entries of a member's pivot list: the padded step count (0: the one-launch kernels keep no list)
+    int det_first;  // the first real step: BLOCKED32 pads in front of the matrix, the other paths behind it
+    bool one_launch() const { return path == RESIDENT || path == WORKGROUP; }
+};
+// h: the streams a context offers (null: a fresh context's); they reach no field but the blocked fp32 route's look-ahead
+// and parts
+DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batch, size_t elem_bytes);
 void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive);
 
 // An instance of the one-launch kernels: register-resident with `lanes` per member (8 ... 64), or workgroup-resident
@@ -143,9 +166,11 @@ void vsolve_walk(const int *order_begin, int nrhs, const SolveLaunchFn &f);
 bool vsolve_has_columns(const int *order_begin);  // no member of an order without a spare column
 
 // ---- device-pointer calls (mi32_device.hip) ---------------------------------------------------------------------------
-// One inversion with the settings given, whatever the context's own are.  The caller holds h->mu and has checked the
-// arguments.
-int inv_device(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status);
-int inv_device(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status);
+// One inversion with the settings given, whatever the context's own are: the DenseRoute of the call, enqueued.  det:
+// where the determinants go (empty: none); d_inv may be null only with one.  The caller holds h->mu and has checked the
+// arguments.  T = float or double (instantiated in mi32_device.hip).
+template <typename T>
+int inv_device(mi32_context *h, Settings s, const T *d_a, int n, int batch, T *d_inv, int *d_status,
+               mi32::DetOut det = {nullptr, nullptr});
 
 #pragma GCC visibility pop

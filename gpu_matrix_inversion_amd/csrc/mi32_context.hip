@@ -251,7 +251,7 @@ int mi32_reserve(mi32_handle_t h, int n, int batch)
     if (!h || n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
-    return h->ws.ensure(h, ws_bytes_for(h->set, n, batch, resolve_algo(h->set, n, sizeof(float))));
+    return h->ws.ensure(h, dense_route(h, h->set, n, batch, sizeof(float)).ws_bytes);
 }
 
 int mi32_set_profiling(mi32_handle_t h, int enable)

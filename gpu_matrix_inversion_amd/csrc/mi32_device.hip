@@ -1,6 +1,8 @@
 // mi32_device.hip -- the device-pointer entry points of libmat_inv_32.so: what mi32_plan.hip decided, enqueued on the
 // context's streams.
+#include <climits>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "mi32_apply.h"
@@ -37,7 +39,7 @@ static BlockedExec blocked_exec(mi32_context *h, int n)
 }
 
 // The two parts of a split batch, the second on the context's split stream; the workspace holds one part per half
-// (ws_bytes_for).
+// (DenseRoute::ws_bytes).
 static int blocked_invert_split(mi32_context *h, const BlockedRoute &r, const BlockedExec &ex, const float *d_a, float *d_inv,
                                 int *d_status, const DetRec &det = DetRec())
 {
@@ -64,71 +66,7 @@ static int blocked_invert_split(mi32_context *h, const BlockedRoute &r, const Bl
     return hip_status(e, "kernel launch");
 }
 
-int inv_device(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status)
-{
-    MI32_HIP(hipSetDevice(h->device));
-    const int algo = resolve_algo(s, n, sizeof(float));
-    MI32_TRY(h->ws.ensure(h, ws_bytes_for(s, n, batch, algo)));
-    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
-        return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
-    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
-    hipError_t e;
-    if (algo == MI32_ALGO_SWEEP)
-        e = sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting);
-    else {
-        const BlockedRoute r = route_of(h, s, n, batch);
-        const BlockedExec ex = blocked_exec(h, n);
-        if (r.parts == 2) return blocked_invert_split(h, r, ex, d_a, d_inv, d_status);
-        e = blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex);
-    }
-    return hip_status(e, "kernel launch");
-}
-
-int inv_device(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status)
-{
-    MI32_HIP(hipSetDevice(h->device));
-    const int algo = resolve_algo(s, n, sizeof(double));
-    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP)
-        return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, DetOut{nullptr, nullptr});
-    const bool blocked = algo == MI32_ALGO_BLOCKED;
-    const bool nopivot = blocked && !s.pivoting;
-    const Blocked64Plan bp = make_blocked64_plan(n, block_w64(s));
-    const NoPivot64Plan npp = make_nopivot64_plan(n, block_w64(s));
-    const SweepPlan sp = make_sweep_plan(n);
-    MI32_TRY(h->ws.ensure(h, nopivot ? nopivot64_workspace_bytes(npp, batch)
-                             : blocked ? blocked64_workspace_bytes(bp, batch)
-                                       : sweep_workspace_bytes(sp, batch, sizeof(double))));
-    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
-    const hipError_t e =
-        nopivot   ? nopivot64_invert(npp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof)
-        : blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof)
-                  : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting);
-    return hip_status(e, "kernel launch");
-}
-
-// the arguments are checked before the context is touched
-template <typename T>
-static int inv_device_checked(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status)
-{
-    if (!h || !d_a || !d_inv || n <= 0 || batch <= 0 || d_a == d_inv) return MI32_BAD_SHAPE;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return inv_device(h, h->set, d_a, n, batch, d_inv, d_status);
-}
-
-// the inverse with the determinant on the one-launch paths, whatever the context's algorithm (see the header); the
-// arguments are checked before the context is touched
-template <typename T>
-static int inv_det_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, double *d_det_mant,
-                          int *d_det_exp)
-{
-    if (!h || !d_a || n <= 0 || n > kWorkgroupMaxOrder || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp)
-        return MI32_BAD_SHAPE;
-    std::lock_guard<std::mutex> lk(h->mu);
-    MI32_HIP(hipSetDevice(h->device));
-    return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, DetOut{d_det_mant, d_det_exp});
-}
-
-// ---- the determinant above kWorkgroupMaxOrder: the route mi32_inv_device* would run, which records its pivots ----------
+// ---- the determinant above kWorkgroupMaxOrder: the route records its pivots, a finish kernel multiplies them ---------
 // The context's det memory for this call (grown on demand, never part of the workspace), its flag and parity words
 // zeroed and the input scanned on the main stream.  Two det calls back to back are ordered by that stream: the finish
 // kernel of the first is enqueued there before the memset of the second.
@@ -145,76 +83,85 @@ static int det_begin(mi32_context *h, const T *d_a, int n, int np, int batch, De
 }
 // enqueued last on the main stream: the recurrence over the steps first ... first + n - 1 of every list
 template <typename T>
-static int det_end(mi32_context *h, hipError_t route, const DetMem &dm, int first, int n, int batch, const int *d_status,
-                   bool pivoting, const DetOut out)
+static int det_end(mi32_context *h, const DetMem &dm, int first, int n, int batch, const int *d_status, bool pivoting,
+                   const DetOut out)
 {
-    MI32_TRY(hip_status(route, "kernel launch"));
     ProfScope ps(h->prof, KC_FINISH, h->stream);
     launch_det_finish((const T *)dm.piv, dm.pstride, first, n, dm.parity, dm.flag, d_status, pivoting, out, batch, h->stream);
     return hip_status(hipGetLastError(), "kernel launch");
 }
 
-// inv_device with the determinant, n > kWorkgroupMaxOrder (so the sweep or the blocked path); d_inv may be null
-static int inv_det_large(mi32_context *h, Settings s, const float *d_a, int n, int batch, float *d_inv, int *d_status,
-                         const DetOut out)
-{
-    const int algo = resolve_algo(s, n, sizeof(float));
-    MI32_TRY(h->ws.ensure(h, ws_bytes_for(s, n, batch, algo)));
-    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
-    DetMem dm;
-    DetRec rec;
-    if (algo == MI32_ALGO_SWEEP) {
-        MI32_TRY(det_begin(h, d_a, n, n, batch, &dm, &rec));
-        const hipError_t e =
-            sweep_invert(make_sweep_plan(n), d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting, rec);
-        return det_end<float>(h, e, dm, 0, n, batch, d_status, s.pivoting, out);
-    }
-    const BlockedRoute r = route_of(h, s, n, batch);
-    const BlockedExec ex = blocked_exec(h, n);
-    MI32_TRY(det_begin(h, d_a, n, r.np, batch, &dm, &rec));
-    if (r.parts == 2)
-        MI32_TRY(blocked_invert_split(h, r, ex, d_a, d_inv, d_status, rec));
-    else
-        MI32_TRY(hip_status(blocked_invert(r, 0, d_a, d_inv, d_status, h->ws.ptr, ex, rec), "kernel launch"));
-    // the padding comes first on this path: its steps (pivot 1, no exchange) are skipped by index
-    return det_end<float>(h, hipSuccess, dm, r.np - n, n, batch, d_status, s.pivoting, out);
-}
-
-static int inv_det_large(mi32_context *h, Settings s, const double *d_a, int n, int batch, double *d_inv, int *d_status,
-                         const DetOut out)
-{
-    const bool blocked = resolve_algo(s, n, sizeof(double)) == MI32_ALGO_BLOCKED;
-    const bool nopivot = blocked && !s.pivoting;
-    const Blocked64Plan bp = make_blocked64_plan(n, block_w64(s));
-    const NoPivot64Plan npp = make_nopivot64_plan(n, block_w64(s));
-    const SweepPlan sp = make_sweep_plan(n);
-    MI32_TRY(h->ws.ensure(h, nopivot ? nopivot64_workspace_bytes(npp, batch)
-                             : blocked ? blocked64_workspace_bytes(bp, batch)
-                                       : sweep_workspace_bytes(sp, batch, sizeof(double))));
-    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
-    DetMem dm;
-    DetRec rec;
-    // the fp64 blocked paths pad behind the matrix: the first n steps are the matrix's
-    MI32_TRY(det_begin(h, d_a, n, nopivot ? npp.np : blocked ? bp.np : n, batch, &dm, &rec));
-    const hipError_t e =
-        nopivot   ? nopivot64_invert(npp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec)
-        : blocked ? blocked64_invert(bp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec)
-                  : sweep_invert(sp, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting, rec);
-    return det_end<double>(h, e, dm, 0, n, batch, d_status, s.pivoting, out);
-}
-
-// the inverse with the determinant at any order (see the header): up to kWorkgroupMaxOrder mi32_inv_det_device*, above
-// the route mi32_inv_device* runs on this context; the arguments are checked before the context is touched
+// THE dense call: status memset (by the route, or here on the one-launch paths), det memset and input scan, the route,
+// the det finish kernel.
 template <typename T>
-static int inv_det_any_device(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status, double *d_det_mant,
-                              int *d_det_exp)
+int inv_device(mi32_context *h, Settings s, const T *d_a, int n, int batch, T *d_inv, int *d_status, const DetOut det)
 {
-    if (!h || !d_a || n <= 0 || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp) return MI32_BAD_SHAPE;
-    std::lock_guard<std::mutex> lk(h->mu);
+    constexpr bool f32 = std::is_same<T, float>::value;
     MI32_HIP(hipSetDevice(h->device));
+    const DenseRoute dr = dense_route(h, s, n, batch, sizeof(T));
+    MI32_TRY(h->ws.ensure(h, dr.ws_bytes));
+    if (dr.one_launch()) return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, det);
+    MI32_TRY(status_buffer(h, d_status, batch, &d_status));
+    DetMem dm;
+    DetRec rec;  // empty: a plain call
+    if (!det.empty()) MI32_TRY(det_begin(h, d_a, n, dr.det_steps, batch, &dm, &rec));
+    int rc = MI32_OK;
+    switch (dr.path) {
+        case DenseRoute::SWEEP:
+            rc = hip_status(sweep_invert(dr.sweep, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, s.pivoting, rec),
+                            "kernel launch");
+            break;
+        case DenseRoute::BLOCKED32:
+            if constexpr (f32) {
+                const BlockedExec ex = blocked_exec(h, n);
+                rc = dr.blocked.parts == 2
+                         ? blocked_invert_split(h, dr.blocked, ex, d_a, d_inv, d_status, rec)
+                         : hip_status(blocked_invert(dr.blocked, 0, d_a, d_inv, d_status, h->ws.ptr, ex, rec), "kernel launch");
+            }
+            break;
+        case DenseRoute::BLOCKED64:
+            if constexpr (!f32)
+                rc = hip_status(blocked64_invert(dr.blocked64, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec),
+                                "kernel launch");
+            break;
+        case DenseRoute::NOPIVOT64:
+            if constexpr (!f32)
+                rc = hip_status(nopivot64_invert(dr.nopivot64, d_a, d_inv, batch, d_status, h->ws.ptr, h->stream, h->prof, rec),
+                                "kernel launch");
+            break;
+        case DenseRoute::RESIDENT:
+        case DenseRoute::WORKGROUP: break;  // (returned above)
+    }
+    if (rc != MI32_OK || det.empty()) return rc;
+    return det_end<T>(h, dm, dr.det_first, n, batch, d_status, s.pivoting, det);
+}
+template int inv_device(mi32_context *, Settings, const float *, int, int, float *, int *, DetOut);
+template int inv_device(mi32_context *, Settings, const double *, int, int, double *, int *, DetOut);
+
+// the arguments are checked before the context is touched
+template <typename T>
+static int inv_device_checked(mi32_context *h, const T *d_a, int n, int batch, T *d_inv, int *d_status)
+{
+    if (!h || !d_a || !d_inv || n <= 0 || batch <= 0 || d_a == d_inv) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return inv_device(h, h->set, d_a, n, batch, d_inv, d_status);
+}
+
+// The inverse with the determinant (see the header); the arguments are checked before the context is touched.  Up to
+// kWorkgroupMaxOrder the one-launch kernels run, whatever the context's algorithm, and no workspace is ensured;
+// max_order bounds mi32_inv_det_device*, and above kWorkgroupMaxOrder mi32_inv_det_any_device* runs the route
+// mi32_inv_device* runs on this context.
+template <typename T>
+static int inv_det_device(mi32_context *h, int max_order, const T *d_a, int n, int batch, T *d_inv, int *d_status,
+                          double *d_det_mant, int *d_det_exp)
+{
+    if (!h || !d_a || n <= 0 || n > max_order || batch <= 0 || d_a == d_inv || !d_det_mant || !d_det_exp)
+        return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
     const DetOut out{d_det_mant, d_det_exp};
-    if (n <= kWorkgroupMaxOrder) return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, out);
-    return inv_det_large(h, h->set, d_a, n, batch, d_inv, d_status, out);
+    if (n > kWorkgroupMaxOrder) return inv_device(h, h->set, d_a, n, batch, d_inv, d_status, out);
+    MI32_HIP(hipSetDevice(h->device));
+    return one_launch_device(h, h->set.pivoting, d_a, n, batch, d_inv, d_status, out);
 }
 
 // A X = B on the one-launch paths: one launch per chunk of columns (solve_walk); every launch repeats the elimination
@@ -319,25 +266,25 @@ int mi32_inv_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, do
 int mi32_inv_det_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
                         double *d_det_mant, int *d_det_exp)
 {
-    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+    return inv_det_device(h, kWorkgroupMaxOrder, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
                             double *d_det_mant, int *d_det_exp)
 {
-    return inv_det_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+    return inv_det_device(h, kWorkgroupMaxOrder, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_inv_det_any_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
                             double *d_det_mant, int *d_det_exp)
 {
-    return inv_det_any_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+    return inv_det_device(h, INT_MAX, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_inv_det_any_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
                                 double *d_det_mant, int *d_det_exp)
 {
-    return inv_det_any_device(h, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
+    return inv_det_device(h, INT_MAX, d_a, n, batch, d_inv, d_status, d_det_mant, d_det_exp);
 }
 
 int mi32_solve_device(mi32_handle_t h, const float *d_a, int n, int batch, const float *d_b, int nrhs, float *d_x,
@@ -460,7 +407,7 @@ int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, in
     if (!h || !d_a || !d_x || !d_out || n <= 0 || batch <= 0) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
-    MI32_TRY(h->ws.ensure(h, ws_bytes_for(h->set, n, batch, resolve_algo(h->set, n, sizeof(float)))));
+    MI32_TRY(h->ws.ensure(h, dense_route(h, h->set, n, batch, sizeof(float)).ws_bytes));
     return hip_status(residual_launch(d_a, d_x, n, batch, d_out, h->ws.ptr, h->stream), "residual launch");
 }
 

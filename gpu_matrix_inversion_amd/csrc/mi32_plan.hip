@@ -1,6 +1,8 @@
 // mi32_plan.hip -- launch planning of libmat_inv_32.so: which algorithm, which blocking, how much workspace, which
 // kernel instance for which members and columns.  Pure host code: functions of the settings, the environment and the
 // shape, no HIP runtime call and no context -- the mi32_resolve_* entry points answer with what a call would do.
+// A dense call is planned once: dense_route composes the rules below into the DenseRoute (mi32_context.h) that the
+// device entry, the workspace queries and mi32_resolve_blocking_f64 all read.
 #include "mi32_apply.h"
 #include "mi32_context.h"
 
@@ -134,22 +136,51 @@ BlockedRoute plan_route(const Settings &s, int n, int batch, bool aux_stream, bo
     return r;
 }
 
-int block_w64(const Settings &s) { return s.block_w ? s.block_w : env_int("MI32_BLOCK_W64", 0); }
+static int block_w64(const Settings &s) { return s.block_w ? s.block_w : env_int("MI32_BLOCK_W64", 0); }
 
-size_t ws_bytes_for(const Settings &s, int n, int batch, int algo)
+// THE description of a dense call.  Only the plan of the path that runs is built: a one-launch or sweep call plans no
+// blocked route, a blocked fp32 call plans its route once and sizes its workspace from that same object.
+DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batch, size_t elem_bytes)
 {
-    size_t a;
-    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) a = 0;  // no working copy: only the residual check needs a workspace
-    else if (algo == MI32_ALGO_SWEEP) a = sweep_workspace_bytes(make_sweep_plan(n), batch, sizeof(float));
-    else {
-        const BlockedRoute p = plan_route(s, n, batch, true, true);
+    const bool f32 = elem_bytes == sizeof(float);
+    const int algo = resolve_algo(s, n, elem_bytes);
+    DenseRoute d;
+    d.ws_bytes = 0;  // the one-launch paths keep no working copy
+    d.det_steps = d.det_first = 0;
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) {
+        d.path = algo == MI32_ALGO_RESIDENT ? DenseRoute::RESIDENT : DenseRoute::WORKGROUP;
+    } else if (algo == MI32_ALGO_SWEEP) {
+        d.path = DenseRoute::SWEEP;
+        d.sweep = make_sweep_plan(n);
+        d.ws_bytes = sweep_workspace_bytes(d.sweep, batch, elem_bytes);
+        d.det_steps = n;
+    } else if (f32) {
+        d.path = DenseRoute::BLOCKED32;
+        // blocked_carve reads np, ld and bw only, and plan_route derives none of the three from the streams offered
+        // (those reach `lookahead` and the parts): the route the call runs also sizes the workspace of any context
+        const BlockedRoute &r = d.blocked = route_of(h, s, n, batch);
         // a batch that may be split in two halves carves one workspace per half -- reserved whether or not this call splits
-        a = blocked_workspace_bytes(p, (batch + 1) / 2) + blocked_workspace_bytes(p, batch - (batch + 1) / 2);
-        const size_t whole = blocked_workspace_bytes(p, batch);
-        if (whole > a) a = whole;
+        const size_t halves = blocked_workspace_bytes(r, (batch + 1) / 2) + blocked_workspace_bytes(r, batch - (batch + 1) / 2);
+        const size_t whole = blocked_workspace_bytes(r, batch);
+        d.ws_bytes = whole > halves ? whole : halves;
+        d.det_steps = r.np;
+        d.det_first = r.np - n;  // the identity padding comes first on this path: its steps are skipped by index
+    } else if (s.pivoting) {
+        d.path = DenseRoute::BLOCKED64;
+        d.blocked64 = make_blocked64_plan(n, block_w64(s));
+        d.ws_bytes = blocked64_workspace_bytes(d.blocked64, batch);
+        d.det_steps = d.blocked64.np;
+    } else {
+        d.path = DenseRoute::NOPIVOT64;
+        d.nopivot64 = make_nopivot64_plan(n, block_w64(s));
+        d.ws_bytes = nopivot64_workspace_bytes(d.nopivot64, batch);
+        d.det_steps = d.nopivot64.np;
     }
-    const size_t r = residual_workspace_bytes(n, batch);
-    return a > r ? a : r;
+    if (f32) {  // mi32_residual_device checks an fp32 result in the same workspace
+        const size_t res = residual_workspace_bytes(n, batch);
+        if (res > d.ws_bytes) d.ws_bytes = res;
+    }
+    return d;
 }
 
 // The look-ahead half of a single large matrix (blocked_invert): how many CUs it runs on and whether it shares them.
@@ -316,7 +347,7 @@ size_t mi32_workspace_bytes(int n, int batch, int algo)
     if (n <= 0 || batch <= 0) return 0;
     Settings s;
     s.algo = algo;
-    return ws_bytes_for(s, n, batch, resolve_algo(s, n, sizeof(float)));
+    return dense_route(nullptr, s, n, batch, sizeof(float)).ws_bytes;
 }
 
 int mi32_resolve_algo(mi32_handle_t h, int n, int /*batch*/) { return resolve_algo(settings_of(h), n, sizeof(float)); }
@@ -372,9 +403,24 @@ int mi32_debug_panel_instance(mi32_handle_t h, int n, int batch, int blk, int s,
 int mi32_resolve_blocking_f64(mi32_handle_t h, int n, int *block_width)
 {
     if (n <= 0 || !block_width) return MI32_BAD_SHAPE;
-    const Settings s = settings_of(h);
-    if (resolve_algo(s, n, sizeof(double)) != MI32_ALGO_BLOCKED) *block_width = 0;
-    else *block_width = s.pivoting ? make_blocked64_plan(n, block_w64(s)).bw : make_nopivot64_plan(n, block_w64(s)).bw;
+    const DenseRoute d = dense_route(h, settings_of(h), n, 1, sizeof(double));  // (no fp64 decision reads the batch)
+    *block_width = d.path == DenseRoute::BLOCKED64 ? d.blocked64.bw : d.path == DenseRoute::NOPIVOT64 ? d.nopivot64.bw : 0;
+    return MI32_OK;
+}
+
+// tests only: the DenseRoute of this shape on this context (null: a fresh one's), out[0 .. 4] = path (the order of
+// DenseRoute::Path), pivot-list entries, first real step, padded order and block width of the path's plan (0, 0 where it
+// has none or, on the sweep, pads nothing); *ws_bytes (may be null): the workspace of the call.
+int mi32_debug_dense_route(mi32_handle_t h, int n, int batch, int elem_bytes, int *out, size_t *ws_bytes)
+{
+    if (n <= 0 || batch <= 0 || (elem_bytes != 4 && elem_bytes != 8) || !out) return MI32_BAD_SHAPE;
+    const DenseRoute d = dense_route(h, settings_of(h), n, batch, (size_t)elem_bytes);
+    out[0] = d.path; out[1] = d.det_steps; out[2] = d.det_first;
+    out[3] = d.path == DenseRoute::BLOCKED32 ? d.blocked.np : d.path == DenseRoute::BLOCKED64 ? d.blocked64.np
+             : d.path == DenseRoute::NOPIVOT64 ? d.nopivot64.np : 0;
+    out[4] = d.path == DenseRoute::BLOCKED32 ? d.blocked.bw : d.path == DenseRoute::BLOCKED64 ? d.blocked64.bw
+             : d.path == DenseRoute::NOPIVOT64 ? d.nopivot64.bw : 0;
+    if (ws_bytes) *ws_bytes = d.ws_bytes;
     return MI32_OK;
 }
 

@@ -241,21 +241,16 @@ static hipError_t sweep_run(const SweepPlan &p, const T *d_a, T *d_inv, int batc
     for (int r = 0; r < p.n; ++r) {
         const bool even = (r % 2) == 0;
         ProfScope ps(prof, KC_SWEEP_STEP, stream);
-        if (det.on()) {  // a det call: the twin, which also records the step's pivot
-            if (pivoting)
-                hipLaunchKernelGGL((gj_sweep_step_det_kernel<T, TR, true>), grid, block, 0, stream, even ? w0 : w1,
-                                   even ? w1 : w0, p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles,
-                                   ws.orig, d_status, (T *)det.piv, det.pstride, det.parity);
-            else
-                hipLaunchKernelGGL((gj_sweep_step_det_kernel<T, TR, false>), grid, block, 0, stream, even ? w0 : w1,
-                                   even ? w1 : w0, p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles,
-                                   ws.orig, d_status, (T *)det.piv, det.pstride, det.parity);
-        } else if (pivoting)
-            hipLaunchKernelGGL((gj_sweep_step_kernel<T, TR, true>), grid, block, 0, stream, even ? w0 : w1, even ? w1 : w0,
-                               p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles, ws.orig, d_status);
+        // the step's arguments, once; rec: what the det twin takes behind them
+        const auto launch = [&](auto kernel, auto... rec) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, even ? w0 : w1, even ? w1 : w0, p.n, p.ld, ws.wstride, r,
+                               even ? k0 : k1, even ? k1 : k0, p.row_tiles, ws.orig, d_status, rec...);
+        };
+        if (det.on())  // a det call: the twin, which also records the step's pivot
+            launch(pivoting ? gj_sweep_step_det_kernel<T, TR, true> : gj_sweep_step_det_kernel<T, TR, false>, (T *)det.piv,
+                   det.pstride, det.parity);
         else
-            hipLaunchKernelGGL((gj_sweep_step_kernel<T, TR, false>), grid, block, 0, stream, even ? w0 : w1, even ? w1 : w0,
-                               p.n, p.ld, ws.wstride, r, even ? k0 : k1, even ? k1 : k0, p.row_tiles, ws.orig, d_status);
+            launch(pivoting ? gj_sweep_step_kernel<T, TR, true> : gj_sweep_step_kernel<T, TR, false>);
     }
     const T *fin = (p.n % 2 == 0) ? w0 : w1;  // the last-written copy (mat_inv_32.cpp:369-372)
     if (!d_inv) return hipGetLastError();   // determinant only (det calls): nothing to un-permute

@@ -281,18 +281,117 @@ __device__ __forceinline__ void inblock_update_body(const SubpanelArgs &A, int u
 // the sub-panel's last step = where that row's accumulation starts in the rank-bw update (which applies the later
 // sub-panels' steps to it and nothing else: gj_mult_transpose_kernel masks the rest).
 // The tiles ride in the launch of the NEXT panel (or in the block's last in-block update): off the chain of pivot steps.
+//
+// The earlier steps are one accumulation chain per element with m ascending -- what an fp32 MFMA computes with the old
+// value as its C operand (the update tiles above).  Here it is v_mfma_f32_16x16x4_f32: four steps
+// per instruction, 16 rows -- what W = 16 needs -- and a dependent instruction every 40 cycles instead of 64 for two
+// steps; tests/test_gpu_outside_strips.py and tests/test_gpu_subnormal.py hold it to the oracle's bits.  Waves 0 and 1
+// of the group take 32 of the tile's 64 columns each, as two 16-column tiles (two independent chains per wave; two row
+// tiles at W = 32): C = the W pivot rows at the start of the block (rows past W: zero, A = 0, never stored),
+// A = mf[row of kk][m], B = ub[m][column].  No barrier inside the loop: both operands are requested MC steps ahead of
+// the chain, B (one row of ub per 16 lanes) straight into the registers the MFMA reads.  A is one float per lane and
+// step from a different row of mf in every lane: a load in the MFMA's own layout touches W cache lines for 4 W useful
+// bytes and the tiles become bound by those loads.  Each wave therefore reads its A set as 16-byte pieces of rows, four
+// rows per 16 lanes, and turns it through a stage of its own in LDS (s_a[wave]: written and read by that wave alone,
+// in program order, so no barrier).  The result goes through s_x into the quad layout of strip_steps.
+typedef float float4v __attribute__((ext_vector_type(4)));
+
 template <int BK>
 struct __attribute__((aligned(16))) OStripShared {
-    static constexpr int MC = 32;       // earlier steps per round of loads
+    static constexpr int MC = 32;            // earlier steps per set of operands
     static constexpr int LDU = 64 + 4;
     static constexpr int LT = BK + 4;
-    float s_ub[MC * LDU];   // u_m of a round x 64 columns
-    float s_mf[MC * LT];    // -f_m of the W pivot rows in a round, [m][row]
-    float s_x[BK * LDU];    // the W pivot rows x 64 columns at the start of the block; after the strip: u_m
+    static constexpr int RS = BK + BK / 4;   // [step][row] stride of an A set: its writes and its reads hit distinct banks
+    static constexpr int LPR = 64 / BK;      // lanes that share a row of mf in a load of the A set, 4 steps each
+    static constexpr int NLA = BK >= 8 ? BK / 8 : 1;  // such loads per set
+    float s_x[BK * LDU];    // the W pivot rows x 64 columns after the block's earlier steps; after the strip: u_m
     float s_xs[BK * LDU];   // the W pivot rows after the sub-panel's last step
     float s_lt[BK * LT];    // -multipliers of the W pivot rows in the W steps of t, [step][row]
+    float s_a[2][MC * RS];  // per MFMA wave: -f_m of the W pivot rows in the set of steps it is working on
     int s_q[BK], s_idx[BK]; // their row index at the start of the block / in the order before t's swaps
 };
+
+// One set = the (at most MC) steps from m on; mc = the steps left from m on (a multiple of BK; more than MC: a whole
+// set).  Lane l of a wave loads the steps k0 + 4 LPR q ... + 3 of row l / LPR (pa: that row of mf at column m + k0).
+template <int BK>
+__device__ __forceinline__ void ostrip_fetch_a(float4 (&an)[OStripShared<BK>::NLA], const float *pa, int k0, int mc)
+{
+    constexpr int LPR = OStripShared<BK>::LPR, NLA = OStripShared<BK>::NLA;
+#pragma unroll
+    for (int q = 0; q < NLA; ++q) {
+        const int k = k0 + q * 4 * LPR;
+        if (k < 32 && k < mc) an[q] = *reinterpret_cast<const float4 *>(pa + q * 4 * LPR);
+    }
+}
+template <int BK>
+__device__ __forceinline__ void ostrip_stage_a(float *sa, const float4 (&an)[OStripShared<BK>::NLA], int r, int k0, int mc)
+{
+    constexpr int LPR = OStripShared<BK>::LPR, NLA = OStripShared<BK>::NLA, RS = OStripShared<BK>::RS;
+#pragma unroll
+    for (int q = 0; q < NLA; ++q) {
+        const int k = k0 + q * 4 * LPR;
+        if (k < 32 && k < mc) {
+            sa[(k + 0) * RS + r] = an[q].x;
+            sa[(k + 1) * RS + r] = an[q].y;
+            sa[(k + 2) * RS + r] = an[q].z;
+            sa[(k + 3) * RS + r] = an[q].w;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+// b[2 j + ct]: the lane's B value of MFMA j of the set in column tile ct -- steps m + 4j ... m + 4j + 3, quarter lk of
+// the wave takes step m + 4j + lk (pb: the lane's column of ub at row m + lk; np4 = 4 np).  Only whole groups of
+// min(BK, 32) steps are predicated.  The scheduling barrier keeps the loads of a set in front of the chain that runs
+// while they travel.
+template <int BK>
+__device__ __forceinline__ void ostrip_fetch_b(float (&b)[16], const float *pb, unsigned np4, int mc)
+{
+    constexpr int G = BK < 32 ? BK : 32;
+#pragma unroll
+    for (int g0 = 0; g0 < 32; g0 += G) {
+        if (G == 32 || g0 < mc) {
+#pragma unroll
+            for (int j = g0 / 4; j < (g0 + G) / 4; ++j) {
+                b[2 * j] = pb[(size_t)j * np4];
+                b[2 * j + 1] = pb[(size_t)j * np4 + 16];
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// sal: the lane's A values of the staged set, sa + lk RS + li; arow[rt]: the lane has a row in row tile rt, else A = 0.
+// acc[2 rt + ct]: the 16 x 16 tile of rows 16 rt ..., columns 16 ct ... of the wave's 32.
+template <int BK>
+__device__ __forceinline__ void ostrip_chain(float4v (&acc)[BK > 16 ? 4 : 2], const float *sal, const bool (&arow)[2],
+                                             const float (&b)[16], int mc)
+{
+    constexpr int G = BK < 32 ? BK : 32, RS = OStripShared<BK>::RS, RT = BK > 16 ? 2 : 1;
+    float a[8][RT];
+#pragma unroll
+    for (int g0 = 0; g0 < 32; g0 += G) {
+        if (G == 32 || g0 < mc) {
+#pragma unroll
+            for (int j = g0 / 4; j < (g0 + G) / 4; ++j)
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) a[j][rt] = sal[4 * j * RS + 16 * rt];
+        }
+    }
+#pragma unroll
+    for (int g0 = 0; g0 < 32; g0 += G) {
+        if (G == 32 || g0 < mc) {
+#pragma unroll
+            for (int j = g0 / 4; j < (g0 + G) / 4; ++j)
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const float av = arow[rt] ? a[j][rt] : 0.0f;
+                    acc[2 * rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[2 * j], acc[2 * rt], 0, 0, 0);
+                    acc[2 * rt + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[2 * j + 1], acc[2 * rt + 1], 0, 0, 0);
+                }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 template <int BK>
 __device__ __forceinline__ void ostrip_body(const SubpanelArgs &A, int tile, unsigned char *smem_group, int tid)
@@ -316,55 +415,85 @@ __device__ __forceinline__ void ostrip_body(const SubpanelArgs &A, int tile, uns
     const float *mf = A.u_mf + (size_t)b * A.mfstride;
     float *ub = A.os_ub + (size_t)b * A.ubstride;
     float *xs = A.os_xs + (size_t)b * A.ubstride;
-    const int K = c0 - C0;  // the block's steps before this sub-panel
-    // (every group executes the same number of barriers: K is the same for all of them)
+    const int K = c0 - C0;  // the block's steps before this sub-panel, a multiple of BK
+    // (every group executes the same number of barriers: three, whatever K is)
     if (tid < BK) {
         T.s_idx[tid] = (A.u_submap + (size_t)b * np)[c0 + tid];
         T.s_q[tid] = (A.u_rowsrc + (size_t)b * np)[c0 + tid];
     }
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < (BK * 16 + 255) / 256; ++q) {
-        const int idx = tid + q * 256;
-        if (idx < BK * 16)
-            *reinterpret_cast<float4 *>(&T.s_x[(idx / 16) * LDU + (idx % 16) * 4]) =
-                *reinterpret_cast<const float4 *>(cur + (size_t)T.s_q[idx / 16] * ld + col0 + (idx % 16) * 4);
-    }
     for (int i = tid; i < BK * BK; i += 256)
         T.s_lt[(i % BK) * LT + i / BK] = -mt[(size_t)(i % BK) * A.mtld + T.s_idx[i / BK]];
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (wave < 2) {
+        const int lane = tid & 63, li = lane & 15, lk = lane >> 4;
+        const int col = col0 + wave * 32 + li;
+        // register q of accumulator 2 rt + ct: row 16 rt + 4 lk + q of the W pivot rows, column 16 ct + li of the wave's 32
+        constexpr int RT = BK > 16 ? 2 : 1;
+        float4v acc[2 * RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = 16 * rt + 4 * lk + q;
+                acc[2 * rt][q] = 0.0f;
+                acc[2 * rt + 1][q] = 0.0f;
+                if (row < BK) {
+                    const float *src = cur + (size_t)T.s_q[row] * ld + col;
+                    acc[2 * rt][q] = src[0];
+                    acc[2 * rt + 1][q] = src[16];
+                }
+            }
+        const bool arow[2] = {li < BK, 16 + li < BK};
+        const int r = lane / S::LPR, k0 = 4 * (lane % S::LPR);
+        const float *pa = mf + (size_t)T.s_q[r] * A.mf_ld + k0;
+        const float *pb = ub + (size_t)lk * np + col;
+        const unsigned np4 = 4u * (unsigned)np;
+        const size_t bstep = (size_t)MC * np;
+        float *sa = T.s_a[wave];
+        const float *sal = sa + lk * S::RS + li % BK;
+        float4 an[S::NLA];
+        float b0[16], b1[16];
+        __builtin_amdgcn_sched_barrier(0);
+        if (K > 0) {
+            ostrip_fetch_a<BK>(an, pa, k0, K);
+            ostrip_fetch_b<BK>(b0, pb, np4, K);
+        }
+#pragma unroll 1
+        for (int left = K; left > 0; left -= 2 * MC) {  // steps left; two sets of MC per trip
+            ostrip_stage_a<BK>(sa, an, r, k0, left);
+            if (left > MC) {
+                ostrip_fetch_a<BK>(an, pa + MC, k0, left - MC);
+                ostrip_fetch_b<BK>(b1, pb + bstep, np4, left - MC);
+            }
+            ostrip_chain<BK>(acc, sal, arow, b0, left);
+            if (left > MC) {
+                pa += 2 * MC;
+                pb += 2 * bstep;
+                ostrip_stage_a<BK>(sa, an, r, k0, left - MC);
+                if (left > 2 * MC) {
+                    ostrip_fetch_a<BK>(an, pa, k0, left - 2 * MC);
+                    ostrip_fetch_b<BK>(b0, pb, np4, left - 2 * MC);
+                }
+                ostrip_chain<BK>(acc, sal, arow, b1, left - MC);
+            }
+        }
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = 16 * rt + 4 * lk + q;
+                if (row < BK) {
+                    T.s_x[row * LDU + wave * 32 + li] = acc[2 * rt][q];
+                    T.s_x[row * LDU + wave * 32 + 16 + li] = acc[2 * rt + 1][q];
+                }
+            }
+    }
     __syncthreads();
     const int c = tid >> 2, g = tid & 3;
     float x[CPT];
 #pragma unroll
     for (int j = 0; j < CPT; ++j) x[j] = T.s_x[(CPT * g + j) * LDU + c];
-    for (int m0 = 0; m0 < K; m0 += MC) {
-        const int mc = (K - m0 < MC) ? (K - m0) : MC;  // a multiple of BK
-#pragma unroll
-        for (int q = 0; q < MC * 16 / 256; ++q) {
-            const int idx = tid + q * 256;
-            if (idx < mc * 16)
-                *reinterpret_cast<float4 *>(&T.s_ub[(idx / 16) * LDU + (idx % 16) * 4]) =
-                    *reinterpret_cast<const float4 *>(ub + (size_t)(m0 + idx / 16) * np + col0 + (idx % 16) * 4);
-        }
-        for (int idx = tid; idx < BK * (mc / 4); idx += 256) {
-            const int kk = idx / (mc / 4), m4 = (idx % (mc / 4)) * 4;
-            const float4 v = *reinterpret_cast<const float4 *>(mf + (size_t)T.s_q[kk] * A.mf_ld + m0 + m4);
-            T.s_mf[(m4 + 0) * LT + kk] = v.x;
-            T.s_mf[(m4 + 1) * LT + kk] = v.y;
-            T.s_mf[(m4 + 2) * LT + kk] = v.z;
-            T.s_mf[(m4 + 3) * LT + kk] = v.w;
-        }
-        __syncthreads();
-        for (int mm = 0; mm < mc; mm += BK) {
-#pragma unroll
-            for (int i = 0; i < BK; ++i) {
-                const float u = T.s_ub[(mm + i) * LDU + c];
-#pragma unroll
-                for (int j = 0; j < CPT; ++j) x[j] = __builtin_fmaf(T.s_mf[(mm + i) * LT + CPT * g + j], u, x[j]);
-            }
-        }
-        __syncthreads();
-    }
     strip_steps<BK>(x, T.s_lt, LT, g, &T.s_x[c], LDU, std::make_integer_sequence<int, BK>{});
 #pragma unroll
     for (int j = 0; j < CPT; ++j) T.s_xs[(CPT * g + j) * LDU + c] = x[j];

@@ -75,9 +75,11 @@ static size_t b64_carve(const Blocked64Plan &p, int batch, void *base, B64Ws &o)
 size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch) { B64Ws ws; return b64_carve(p, batch, nullptr, ws); }
 
 // ---- makeAugmented counterpart: A -> diag(A, I) in the first working copy --------------------
+// pad: where the matrix starts in the working copy -- 0 here (the padding lies behind it), np - n on the no-pivot path
+// (mi32_nopivot64.hip: the padding comes first)
 __global__ __launch_bounds__(256) void b64_init_kernel(const double *__restrict__ in, int n, int np, int ld, size_t wstride,
                                                         double *__restrict__ w0, int *__restrict__ orig,
-                                                        int *__restrict__ status)
+                                                        int *__restrict__ status, int pad)
 {
     const int b = blockIdx.z;
     const int j = blockIdx.x * 256 + threadIdx.x;
@@ -91,7 +93,8 @@ __global__ __launch_bounds__(256) void b64_init_kernel(const double *__restrict_
             const int i = i0 + u;
             if (i >= np) break;
             double v;
-            if (i < n && j < n) v = a[(size_t)i * n + j];
+            const int ia = i - pad, ja = j - pad;
+            if (ia >= 0 && ia < n && ja >= 0 && ja < n) v = a[(size_t)ia * n + ja];
             else v = (i == j) ? 1.0 : 0.0;
             nonfinite = nonfinite || (v - v != 0.0);
             w[(size_t)i * ld + j] = v;
@@ -102,10 +105,10 @@ __global__ __launch_bounds__(256) void b64_init_kernel(const double *__restrict_
 }
 
 void launch_b64_init(const double *d_a, int n, int np, int ld, size_t wstride, double *w0, int *orig, int batch,
-                     int *status, hipStream_t stream)
+                     int *status, hipStream_t stream, int pad)
 {
     hipLaunchKernelGGL(b64_init_kernel, dim3((np + 255) / 256, (np + 15) / 16, batch), dim3(256), 0, stream, d_a, n, np,
-                       ld, wstride, w0, orig, status);
+                       ld, wstride, w0, orig, status, pad);
 }
 
 // ---- arg-max records of column c over the rows >= c (the first column of a block), row map reset ----
@@ -281,7 +284,7 @@ hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d
     }
     {
         ProfScope ps(prof, KC_INIT, stream);
-        launch_b64_init(d_a, p.n, np, p.ld, ws.wstride, ws.w0, ws.orig, batch, d_status, stream);
+        launch_b64_init(d_a, p.n, np, p.ld, ws.wstride, ws.w0, ws.orig, batch, d_status, stream, 0);
     }
     double *cur = ws.w0, *oth = ws.w1;
     PivotRec<double> *kin = ws.k0, *kout = ws.k1;

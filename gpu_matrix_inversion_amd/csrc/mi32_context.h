@@ -118,7 +118,7 @@ struct DenseRoute {
     // of the whole batch and the two halves of a split, reserved whether or not this call splits.
     size_t ws_bytes;
     int det_steps;  // entries of a member's pivot list: the padded step count (0: the one-launch kernels keep no list)
-    int det_first;  // the first real step: BLOCKED32 pads in front of the matrix, the other paths behind it
+    int det_first;  // the first real step: BLOCKED32 and NOPIVOT64 pad in front of the matrix, BLOCKED64 behind it
     bool one_launch() const { return path == RESIDENT || path == WORKGROUP; }
 };
 // h: the streams a context offers (null: a fresh context's); they reach no field but the blocked fp32 route's look-ahead

@@ -228,10 +228,11 @@ Blocked64Plan make_blocked64_plan(int n, int bw);
 size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch);
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
                             hipStream_t stream, Profiler *prof, const DetRec &det = DetRec());
-// makeAugmented counterpart of the fp64 blocked paths: w0 <- diag(A, I) (np x np, row stride ld, wstride doubles per
-// matrix), orig <- the identity, status[b] <- MI32_SINGULAR for a non-finite input entry (status may be null)
+// makeAugmented counterpart of the fp64 blocked paths: w0 <- diag(A, I) with pad = 0 (the pivoted path) or diag(I, A)
+// with pad = np - n (the no-pivot path: rows and columns [pad, np) hold the matrix); np x np, row stride ld, wstride
+// doubles per matrix; orig <- the identity, status[b] <- MI32_SINGULAR for a non-finite input entry (status may be null)
 void launch_b64_init(const double *d_a, int n, int np, int ld, size_t wstride, double *w0, int *orig, int batch,
-                     int *status, hipStream_t stream);
+                     int *status, hipStream_t stream, int pad);
 // fp64 no-pivot path (mi32_nopivot64.hip): the reference's order element by element, per block of bw steps the
 // diagonal block on one workgroup, the block columns / pivot-row strips of every other row / column, and one
 // rank-bw update on the fp64 matrix cores

@@ -15,14 +15,18 @@
 //       steps k < m, U[m][j] = y / piv_m (IEEE division), then through the steps k > m; U is the B operand of (d);
 //   (d) np64_rank_update_kernel: X[i][j] = fma(-f_m[i], U[m][j], X[i][j]) for m ascending, i and j outside K: one
 //       k-ascending chain of v_mfma_f64_16x16x4_f64 per element whose C operand is the old value.
-// Two departures from the reference, neither of which changes a finite non-zero result:
-//   * a zero multiplier is multiplied through rather than skipped (matrix_inversion_no_pivots.cpp:29), so the sign of
-//     a zero entry can differ;
-//   * the equality assumes finite intermediates (a multiplied-through 0 * inf is a NaN where the reference skips).
+// One departure from the reference: a zero multiplier is multiplied through rather than skipped
+// (matrix_inversion_no_pivots.cpp:29).  With every intermediate finite only the sign of a zero entry can differ; once a
+// pivot row holds an infinity (an inverse that overflows: status 0, the pivots are finite) fma(-0, +-inf, x) is a NaN
+// where the reference keeps x.  The result is then, entry by entry, that of the oracle's steps with the zero multiplier
+// multiplied through (oracle/gj_oracle.c, GJO_ZEROS_THROUGH): tests/test_gpu_overflow.py, test_no_pivot_blocked.
 //
-// Working matrix: the N x N in-place form padded with an identity block to a multiple of bw (a padded step divides an
-// identity row by 1 and eliminates nothing), so that no kernel needs a bounds check.  No row is ever swapped: the
-// result is copied out through the identity column map.
+// Working matrix: diag(I, A), the N x N in-place form BEHIND an identity block that pads it to a multiple of bw, so
+// that no kernel needs a bounds check.  The padded steps come first: each divides an identity row by 1 and multiplies
+// exact zeros through finite rows, which changes no bit.  By the time a real pivot row holds an infinity the padded
+// rows are retired -- they take the NaN of 0 * inf, and so do the padded columns, but nothing reads either again.
+// (With the padding behind the matrix its steps ran last, on rows that held those NaNs, and carried them into every
+// real row of the column.)  No row is ever swapped: the result is copied out of the corner through the identity map.
 #include "mi32_internal.h"
 #include "mi32_sweep_common.h"
 
@@ -376,15 +380,16 @@ hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d
         if ((e = hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)batch, stream)) != hipSuccess) return e;
     }
     {
-        ProfScope ps(prof, KC_INIT, stream);  // diag(A, I) into the working copy, non-finite input -> MI32_SINGULAR
-        launch_b64_init(d_a, p.n, p.np, p.ld, ws.wstride, ws.w, ws.orig, batch, d_status, stream);
+        ProfScope ps(prof, KC_INIT, stream);  // diag(I, A) into the working copy, non-finite input -> MI32_SINGULAR
+        launch_b64_init(d_a, p.n, p.np, p.ld, ws.wstride, ws.w, ws.orig, batch, d_status, stream, p.np - p.n);
     }
     e = p.bw == 128 ? np64_run_blocks<128>(p, ws, batch, d_status, stream, prof, det)
                     : np64_run_blocks<64>(p, ws, batch, d_status, stream, prof, det);
     if (e != hipSuccess) return e;
     if (!d_inv) return hipGetLastError();  // determinant only (det calls): nothing to copy out
-    ProfScope ps(prof, KC_FINISH, stream);  // orig is the identity: a plain copy-out of the N x N corner
-    launch_unpermute(ws.w, p.ld, ws.wstride, ws.orig, ws.invp, p.np, p.n, batch, d_inv, stream);
+    ProfScope ps(prof, KC_FINISH, stream);  // orig is the identity: a plain copy-out of the N x N corner behind the padding
+    const int pad = p.np - p.n;
+    launch_unpermute(ws.w + (size_t)pad * p.ld + pad, p.ld, ws.wstride, ws.orig, ws.invp, p.np, p.n, batch, d_inv, stream);
     return hipGetLastError();
 }
 

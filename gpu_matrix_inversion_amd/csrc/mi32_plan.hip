@@ -175,6 +175,7 @@ DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batc
         d.nopivot64 = make_nopivot64_plan(n, block_w64(s));
         d.ws_bytes = nopivot64_workspace_bytes(d.nopivot64, batch);
         d.det_steps = d.nopivot64.np;
+        d.det_first = d.nopivot64.np - n;  // the identity padding comes first here too
     }
     if (f32) {  // mi32_residual_device checks an fp32 result in the same workspace
         const size_t res = residual_workspace_bytes(n, batch);

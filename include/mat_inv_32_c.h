@@ -25,6 +25,14 @@
 extern "C" {
 #endif
 
+/* The status looks at the input's entries and at the pivots only.  MI32_OK therefore does not say that the inverse is
+ * finite: where the RESULT overflows with every pivot finite it holds +-inf and NaN.  With every intermediate finite
+ * all routes return the oracle's bits.  Once a pivot row holds an infinity they part in a documented way
+ * (tests/test_gpu_overflow.py): the sweep and the one-launch routes skip an exact-zero multiplier, as the reference
+ * does; the blocked fp32 route and the blocked fp64 no-pivot route multiply it through, and fma(-0, +-inf, x) is a NaN
+ * -- on a block-structured input they can return NaN columns where the sweep returns zeros and infinities; the
+ * blocked fp64 route follows its composite order (oracle: gjo_matrix_inv_64_blocked), which near that boundary can
+ * meet a non-finite pivot, and report MI32_SINGULAR, on an input the sweep inverts with MI32_OK. */
 typedef enum mi32_status {
     MI32_OK = 0,
     MI32_BAD_SHAPE = 1,     /* reference: returns {} (mat_inv_32.cpp:206-215)                 */

@@ -16,6 +16,7 @@ from .oracle import (  # noqa: F401
     STATUS_BAD_SHAPE,
     STATUS_OK,
     STATUS_SINGULAR,
+    ZEROS,
     build,
     fill_hollow_msvc,
     frobenius_metric,

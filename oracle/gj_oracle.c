@@ -251,7 +251,8 @@ int gjo_matrix_inv_32(const float *in, size_t in_len, int n, float *out, int piv
  * original index of the pivot row of step r).  Every skipped operation in
  * this form is one that the augmented form performs on an exact 0 or 1, so the
  * stored values are identical. */
-static int inv32_inplace_impl(const float *in, size_t in_len, int n, float *out, int arith_mode, int *pivots, int pivoting)
+static int inv32_inplace_impl(const float *in, size_t in_len, int n, float *out, int arith_mode, int *pivots, int pivoting,
+                              int zeros)
 {
     if (!shape_ok(in_len, n)) return GJO_BAD_SHAPE;
     const size_t ld = (size_t)n;
@@ -292,7 +293,7 @@ static int inv32_inplace_impl(const float *in, size_t in_len, int n, float *out,
             float *mi = m + (size_t)i * ld;
             const float cir = mi[r];
             mi[r] = 0.0f; /* the identity column's entry in this row */
-            if (cir != 0.0f)
+            if (cir != 0.0f || zeros == GJO_ZEROS_THROUGH)
                 for (int j = 0; j < n; ++j) mi[j] = elim(mi[j], cir, rowr[j], arith_mode);
         }
     }
@@ -310,7 +311,7 @@ static int inv32_inplace_impl(const float *in, size_t in_len, int n, float *out,
  * fp32 library) is the same five-kernel step in double; here the in-place N x N form of it with true partial
  * pivoting (largest |a|, lowest row among equals), IEEE division and one fused multiply-add per element
  * (exact-zero multipliers skipped, matrix_inversion_FP64.cpp:28). */
-static int inv64_inplace_impl(const double *in, size_t in_len, int n, double *out, int *pivots, int pivoting)
+static int inv64_inplace_impl(const double *in, size_t in_len, int n, double *out, int *pivots, int pivoting, int zeros)
 {
     if (!shape_ok(in_len, n)) return GJO_BAD_SHAPE;
     const size_t ld = (size_t)n;
@@ -350,7 +351,7 @@ static int inv64_inplace_impl(const double *in, size_t in_len, int n, double *ou
             double *mi = m + (size_t)i * ld;
             const double cir = mi[r];
             mi[r] = 0.0;
-            if (cir != 0.0)
+            if (cir != 0.0 || zeros == GJO_ZEROS_THROUGH)
                 for (int j = 0; j < n; ++j) mi[j] = fma(-cir, rowr[j], mi[j]);
         }
     }
@@ -362,11 +363,11 @@ static int inv64_inplace_impl(const double *in, size_t in_len, int n, double *ou
 
 int gjo_matrix_inv_32_inplace(const float *in, size_t in_len, int n, float *out, int arith_mode, int *pivots)
 {
-    return inv32_inplace_impl(in, in_len, n, out, arith_mode, pivots, 1);
+    return inv32_inplace_impl(in, in_len, n, out, arith_mode, pivots, 1, GJO_ZEROS_SKIP);
 }
 int gjo_matrix_inv_64_inplace(const double *in, size_t in_len, int n, double *out, int *pivots)
 {
-    return inv64_inplace_impl(in, in_len, n, out, pivots, 1);
+    return inv64_inplace_impl(in, in_len, n, out, pivots, 1, GJO_ZEROS_SKIP);
 }
 /* The reference's no-pivot variant, matrix_inversion_no_pivots.cpp:10 (kernels :13-70, loop :482-560): per step
  * findCrr (the diagonal entry, no search, no swap), fixRow (IEEE division), copyCirColumn + fixColumn (skip zero
@@ -374,11 +375,28 @@ int gjo_matrix_inv_64_inplace(const double *in, size_t in_len, int n, double *ou
  * returns {} when the reduced left half is not exactly I, :670). */
 int gjo_matrix_inv_64_nopivot(const double *in, size_t in_len, int n, double *out)
 {
-    return inv64_inplace_impl(in, in_len, n, out, NULL, 0);
+    return inv64_inplace_impl(in, in_len, n, out, NULL, 0, GJO_ZEROS_SKIP);
 }
 int gjo_matrix_inv_32_nopivot(const float *in, size_t in_len, int n, float *out, int arith_mode)
 {
-    return inv32_inplace_impl(in, in_len, n, out, arith_mode, NULL, 0);
+    return inv32_inplace_impl(in, in_len, n, out, arith_mode, NULL, 0, GJO_ZEROS_SKIP);
+}
+/* The same four entry points with the rule for an exact-zero multiplier as an argument (gj_oracle.h). */
+int gjo_matrix_inv_32_inplace_z(const float *in, size_t in_len, int n, float *out, int arith_mode, int *pivots, int zeros)
+{
+    return inv32_inplace_impl(in, in_len, n, out, arith_mode, pivots, 1, zeros);
+}
+int gjo_matrix_inv_64_inplace_z(const double *in, size_t in_len, int n, double *out, int *pivots, int zeros)
+{
+    return inv64_inplace_impl(in, in_len, n, out, pivots, 1, zeros);
+}
+int gjo_matrix_inv_64_nopivot_z(const double *in, size_t in_len, int n, double *out, int zeros)
+{
+    return inv64_inplace_impl(in, in_len, n, out, NULL, 0, zeros);
+}
+int gjo_matrix_inv_32_nopivot_z(const float *in, size_t in_len, int n, float *out, int arith_mode, int zeros)
+{
+    return inv32_inplace_impl(in, in_len, n, out, arith_mode, NULL, 0, zeros);
 }
 
 /* ---- blocked restatement (CPU mirror of the HIP blocked path) ---------- */

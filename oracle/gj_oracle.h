@@ -83,6 +83,19 @@ int gjo_matrix_inv_64_blocked(const double *in, size_t in_len, int n, double *ou
 int gjo_matrix_inv_64_nopivot(const double *in, size_t in_len, int n, double *out);
 int gjo_matrix_inv_32_nopivot(const float *in, size_t in_len, int n, float *out, int arith_mode);
 
+/* What a row update does with an exact-zero multiplier a[i][r] (mat_inv_32.cpp:28, matrix_inversion_FP64.cpp:28,
+ * matrix_inversion_no_pivots.cpp:29 skip it).  On finite data the two rules differ in the sign of a zero only; once
+ * the pivot row holds an infinity, fma(-0, +-inf, x) is a NaN where the reference keeps x.  THROUGH is what a kernel
+ * computes that multiplies every multiplier through (the matrix-core paths): the tests' reference for those. */
+enum {
+    GJO_ZEROS_SKIP = 0,    /* the reference's rule, and what every entry point above does */
+    GJO_ZEROS_THROUGH = 1  /* the row update is applied for a zero multiplier too        */
+};
+int gjo_matrix_inv_32_inplace_z(const float *in, size_t in_len, int n, float *out, int arith_mode, int *pivots, int zeros);
+int gjo_matrix_inv_64_inplace_z(const double *in, size_t in_len, int n, double *out, int *pivots, int zeros);
+int gjo_matrix_inv_64_nopivot_z(const double *in, size_t in_len, int n, double *out, int zeros);
+int gjo_matrix_inv_32_nopivot_z(const float *in, size_t in_len, int n, float *out, int arith_mode, int zeros);
+
 /* Blocked (rank-b delayed update) restatement of the same elimination: the
  * CPU mirror of the HIP blocked path's operation order (panel of width w
  * factored with partial pivoting, then one rank-w update of every other

@@ -22,6 +22,8 @@ ARITH_UNFUSED = 1
 STATUS_OK = 0
 STATUS_BAD_SHAPE = 1
 STATUS_SINGULAR = 2
+# what a row update does with an exact-zero multiplier (gj_oracle.h): "skip" is the reference's rule and the default
+ZEROS = {"skip": 0, "through": 1}
 
 _lib = None
 
@@ -79,6 +81,14 @@ def _load():
     lib.gjo_matrix_inv_64_nopivot.argtypes = [dp, ctypes.c_size_t, ctypes.c_int, dp]
     lib.gjo_matrix_inv_32_nopivot.restype = ctypes.c_int
     lib.gjo_matrix_inv_32_nopivot.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp, ctypes.c_int]
+    lib.gjo_matrix_inv_32_inplace_z.restype = ctypes.c_int
+    lib.gjo_matrix_inv_32_inplace_z.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp, ctypes.c_int, ip, ctypes.c_int]
+    lib.gjo_matrix_inv_64_inplace_z.restype = ctypes.c_int
+    lib.gjo_matrix_inv_64_inplace_z.argtypes = [dp, ctypes.c_size_t, ctypes.c_int, dp, ip, ctypes.c_int]
+    lib.gjo_matrix_inv_64_nopivot_z.restype = ctypes.c_int
+    lib.gjo_matrix_inv_64_nopivot_z.argtypes = [dp, ctypes.c_size_t, ctypes.c_int, dp, ctypes.c_int]
+    lib.gjo_matrix_inv_32_nopivot_z.restype = ctypes.c_int
+    lib.gjo_matrix_inv_32_nopivot_z.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp, ctypes.c_int, ctypes.c_int]
     lib.gjo_matrix_inv_32_blocked_exact.restype = ctypes.c_int
     lib.gjo_matrix_inv_32_blocked_exact.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp, ctypes.c_int, ip]
     lib.gjo_matrix_inv_32_blocked2w.restype = ctypes.c_int
@@ -126,7 +136,8 @@ def matrix_inv_32(vec, n: int, pivot_mode: int = PIVOT_TRUE_PARTIAL, arith_mode:
     return out
 
 
-def matrix_inv_32_inplace(vec, n: int, arith_mode: int = ARITH_FMA, return_info: bool = False):
+def matrix_inv_32_inplace(vec, n: int, arith_mode: int = ARITH_FMA, return_info: bool = False, zeros: str = "skip"):
+    """``zeros="through"``: the row update is applied for an exact-zero multiplier too (gj_oracle.h, GJO_ZEROS_THROUGH)."""
     lib = _load()
     v = _f32(vec)
     n = int(n)
@@ -135,15 +146,16 @@ def matrix_inv_32_inplace(vec, n: int, arith_mode: int = ARITH_FMA, return_info:
         return (empty, {"status": STATUS_BAD_SHAPE}) if return_info else empty
     out = np.empty(n * n, dtype=np.float32)
     piv = np.empty(n, dtype=np.int32)
-    st = lib.gjo_matrix_inv_32_inplace(_fp(v), v.size, n, _fp(out), arith_mode,
-                                       piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    st = lib.gjo_matrix_inv_32_inplace_z(_fp(v), v.size, n, _fp(out), arith_mode,
+                                         piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ZEROS[zeros])
     if return_info:
         return out, {"status": st, "pivots": piv}
     return out
 
 
-def matrix_inv_64(vec, n: int, return_info: bool = False):
-    """fp64 twin (the reference's matrix_inversion_FP64 call shape): flat row-major in, flat inverse out."""
+def matrix_inv_64(vec, n: int, return_info: bool = False, zeros: str = "skip"):
+    """fp64 twin (the reference's matrix_inversion_FP64 call shape): flat row-major in, flat inverse out.
+    ``zeros`` as in ``matrix_inv_32_inplace``."""
     lib = _load()
     v = np.ascontiguousarray(np.asarray(vec, dtype=np.float64).reshape(-1))
     n = int(n)
@@ -153,8 +165,8 @@ def matrix_inv_64(vec, n: int, return_info: bool = False):
     out = np.empty(n * n, dtype=np.float64)
     piv = np.empty(n, dtype=np.int32)
     dp = ctypes.POINTER(ctypes.c_double)
-    st = lib.gjo_matrix_inv_64_inplace(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp),
-                                       piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    st = lib.gjo_matrix_inv_64_inplace_z(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp),
+                                         piv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ZEROS[zeros])
     if return_info:
         return out, {"status": st, "pivots": piv}
     return out
@@ -192,9 +204,10 @@ def matrix_inv_64_blocked(vec, n: int, bw: int, return_info: bool = False):
     return (out, {"status": st, "pivots": piv}) if return_info else out
 
 
-def matrix_inversion_no_pivots(vec, n: int, return_info: bool = False):
+def matrix_inversion_no_pivots(vec, n: int, return_info: bool = False, zeros: str = "skip"):
     """The reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10): fp64 for a float64 input (as the
-    reference ships it), the same steps in fp32 for a float32 input.  Flat inverse, or an empty array on a shape error."""
+    reference ships it), the same steps in fp32 for a float32 input.  Flat inverse, or an empty array on a shape error.
+    ``zeros`` as in ``matrix_inv_32_inplace``."""
     lib = _load()
     f64 = np.asarray(vec).dtype == np.float64
     dt = np.float64 if f64 else np.float32
@@ -206,9 +219,9 @@ def matrix_inversion_no_pivots(vec, n: int, return_info: bool = False):
     out = np.empty(n * n, dtype=dt)
     if f64:
         dp = ctypes.POINTER(ctypes.c_double)
-        st = lib.gjo_matrix_inv_64_nopivot(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp))
+        st = lib.gjo_matrix_inv_64_nopivot_z(v.ctypes.data_as(dp), v.size, n, out.ctypes.data_as(dp), ZEROS[zeros])
     else:
-        st = lib.gjo_matrix_inv_32_nopivot(_fp(v), v.size, n, _fp(out), ARITH_FMA)
+        st = lib.gjo_matrix_inv_32_nopivot_z(_fp(v), v.size, n, _fp(out), ARITH_FMA, ZEROS[zeros])
     return (out, {"status": st}) if return_info else out
 
 

@@ -106,6 +106,37 @@ def test_fast_and_portable_oracle_builds_are_bit_identical(oracle):
             assert lib.gjo_matrix_inv_32_blocked_exact(a.ctypes.data_as(fp), a.size, n, out.ctypes.data_as(fp), 128, None) == 0
             outs.append(out)
         assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32)), n
+    # ... and the step-by-step restatement under both rules for a zero multiplier (gj_oracle.h, GJO_ZEROS_*), on inputs
+    # whose inverse overflows: the same bits, infinities and NaN included, pivoted and not, fp32 and fp64
+    import overflow_cases as C
+
+    dp = ctypes.POINTER(ctypes.c_double)
+    for c in (C.case("rows_down", np.float32, 64), C.case("block_diag", np.float32, (40, 24)),
+              C.case("rows_down", np.float64, 64), C.case("block_diag", np.float64, (40, 24), first=False),
+              C.case("rows_down", np.float32, 100, False), C.case("block_diag", np.float64, (75, 25), False)):
+        a, n = np.ascontiguousarray(C.matrix(c).reshape(-1)), C.order(c)
+        f32 = c.dtype == np.float32
+        ptr = fp if f32 else dp
+        for zeros in (0, 1):
+            outs = []
+            for lib in libs:
+                out = np.empty(n * n, c.dtype)
+                args = [a.ctypes.data_as(ptr), ctypes.c_size_t(a.size), ctypes.c_int(n), out.ctypes.data_as(ptr)]
+                if c.pivoting:
+                    fn = lib.gjo_matrix_inv_32_inplace_z if f32 else lib.gjo_matrix_inv_64_inplace_z
+                    args += ([ctypes.c_int(0)] if f32 else []) + [ip()]
+                else:
+                    fn = lib.gjo_matrix_inv_32_nopivot_z if f32 else lib.gjo_matrix_inv_64_nopivot_z
+                    args += [ctypes.c_int(0)] if f32 else []
+                fn.restype = ctypes.c_int
+                assert fn(*args, ctypes.c_int(zeros)) == 0
+                outs.append(out)
+            assert not np.isfinite(outs[0]).all() and C.same_with_nonfinite(outs[0], outs[1]), (c, zeros)
+            u = np.uint32 if f32 else np.uint64
+            fin = np.isfinite(outs[0])
+            assert np.array_equal(outs[0].view(u)[fin], outs[1].view(u)[fin]), (c, zeros)
+            want = C.reference(oracle, c, ("skip", "through")[zeros])[0]
+            assert C.same_with_nonfinite(outs[1], want), (c, zeros)
 
 
 def test_oracle_digest_4096_reproduced_here(oracle):

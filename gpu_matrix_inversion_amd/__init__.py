@@ -9,6 +9,7 @@ from ._lib import (  # noqa: F401
     ALGO_BLOCKED,
     ALGO_RESIDENT,
     ALGO_SWEEP,
+    ALGO_WIDE,
     ALGO_WORKGROUP,
     MI32_BAD_SHAPE,
     MI32_OK,

@@ -25,8 +25,9 @@ ALGO_SWEEP = 1
 ALGO_BLOCKED = 2
 ALGO_RESIDENT = 3
 ALGO_WORKGROUP = 4
+ALGO_WIDE = 5
 ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "resident": ALGO_RESIDENT,
-              "workgroup": ALGO_WORKGROUP}
+              "workgroup": ALGO_WORKGROUP, "wide": ALGO_WIDE}
 # the eight kernel classes of a variable-size batch: the largest order each takes (mi32_vbatch_bin)
 VBATCH_CLASS_TOPS = (8, 16, 32, 64, 80, 96, 112, 128)
 KERNEL_CLASSES = ("init", "sweep_step", "panel", "update_in_block", "update_rank_bw", "finish", "panel_transpose")
@@ -64,6 +65,7 @@ C_ABI_SYMBOLS = (
     "mi32_resolve_route",
     "mi32_resolve_resident",
     "mi32_resolve_workgroup",
+    "mi32_resolve_wide",
     "mi32_vbatch_bin",
     "mi32_vbatch_create",
     "mi32_vbatch_destroy",
@@ -216,6 +218,8 @@ def load() -> ctypes.CDLL:
     lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
     lib.mi32_resolve_workgroup.restype = ctypes.c_int
     lib.mi32_resolve_workgroup.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
+    lib.mi32_resolve_wide.restype = ctypes.c_int
+    lib.mi32_resolve_wide.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
     lib.mi32_vbatch_bin.restype = ctypes.c_int
     lib.mi32_vbatch_bin.argtypes = [ip, ctypes.c_int, ip, ip]
     lib.mi32_vbatch_create.restype = ctypes.c_int

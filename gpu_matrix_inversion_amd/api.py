@@ -22,8 +22,8 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import (ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_RESIDENT, ALGO_SWEEP, ALGO_WORKGROUP, MI32_OK, MI32_SINGULAR,
-                   Mi32Error)
+from ._lib import (ALGO_AUTO, ALGO_BLOCKED, ALGO_NAMES, ALGO_RESIDENT, ALGO_SWEEP, ALGO_WIDE, ALGO_WORKGROUP, MI32_OK,
+                   MI32_SINGULAR, Mi32Error)
 
 
 def _algo_id(algo) -> int:
@@ -358,6 +358,16 @@ class Inverter:
                                                     ctypes.byref(rows), ctypes.byref(top)), "mi32_resolve_workgroup")
         return threads.value, rows.value, top.value
 
+    def resolved_wide(self, n: int, elem_bytes: int = 4):
+        """(threads per matrix, register rows per thread, largest order) of the wide workgroup-resident path
+        (``algo="wide"``, fp32 only): 768 threads and 40 / 48 rows for ``129 <= n <= 192``, 1024 threads and 56 / 64
+        rows for ``193 <= n <= 256``; (0, 0, 256) outside and for ``elem_bytes=8``, where that algorithm resolves to
+        ``resident`` (``n <= 64``), ``workgroup`` (``n <= 128``) or to what ``auto`` resolves to."""
+        threads, rows, top = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._lib.mi32_resolve_wide(self._h, int(n), int(elem_bytes), ctypes.byref(threads),
+                                               ctypes.byref(rows), ctypes.byref(top)), "mi32_resolve_wide")
+        return threads.value, rows.value, top.value
+
     def resolved_panel_widths(self, n: int, batch: int = 1):
         """Sub-panel width of every outer block (narrow while many rows are still candidates)."""
         nb = ctypes.c_int()
@@ -448,8 +458,9 @@ class Inverter:
         split) and takes the determinant from that elimination's own pivots: inverse and status are ``inv``'s bit for
         bit, and the pair ``(det_mant, det_exp)`` follows the recurrence of ``inv_det`` over the pivots in step order.
         Returns ``(inverse, status, det_mant, det_exp)``.  ``want_inverse=False``: the elimination runs, the final
-        un-permutation and store are skipped, and None is returned for the inverse.  Asynchronous on torch's current
-        stream."""
+        un-permutation and store are skipped, and None is returned for the inverse.  With ``algo="wide"`` a float32
+        batch of order 129 ... 256 takes the pair from the one launch of that path, as ``inv_det`` does below 129.
+        Asynchronous on torch's current stream."""
         return self._dense("mi32_inv_det_any_device", a, out, status, want_inverse, det=True)
 
     def resolved_solve(self, n: int, nrhs: int, elem_bytes: int = 4):

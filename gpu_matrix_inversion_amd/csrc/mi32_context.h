@@ -107,8 +107,8 @@ inline mi32::BlockedRoute route_of(const mi32_context *h, const Settings &s, int
 // mi32_inv_device*, mi32_inv_det_any_device*, mi32_workspace_bytes, mi32_reserve and the mi32_resolve_* queries all
 // read this one description.
 struct DenseRoute {
-    enum Path { RESIDENT, WORKGROUP, SWEEP, BLOCKED32, BLOCKED64, NOPIVOT64 } path;
-    union {  // the member `path` names; none on the two one-launch paths
+    enum Path { RESIDENT, WORKGROUP, SWEEP, BLOCKED32, BLOCKED64, NOPIVOT64, WIDE } path;
+    union {  // the member `path` names; none on the one-launch paths
         mi32::SweepPlan sweep;
         mi32::BlockedRoute blocked;
         mi32::Blocked64Plan blocked64;
@@ -119,7 +119,7 @@ struct DenseRoute {
     size_t ws_bytes;
     int det_steps;  // entries of a member's pivot list: the padded step count (0: the one-launch kernels keep no list)
     int det_first;  // the first real step: BLOCKED32 and NOPIVOT64 pad in front of the matrix, BLOCKED64 behind it
-    bool one_launch() const { return path == RESIDENT || path == WORKGROUP; }
+    bool one_launch() const { return path == RESIDENT || path == WORKGROUP || path == WIDE; }
 };
 // h: the streams a context offers (null: a fresh context's); they reach no field but the blocked fp32 route's look-ahead
 // and parts

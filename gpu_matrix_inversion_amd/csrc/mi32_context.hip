@@ -215,7 +215,7 @@ int mi32_set_stream(mi32_handle_t h, void *hip_stream)
 
 int mi32_set_algo(mi32_handle_t h, int algo)
 {
-    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_WORKGROUP) return MI32_BAD_SHAPE;
+    if (!h || algo < MI32_ALGO_AUTO || algo > MI32_ALGO_WIDE) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     h->set.algo = algo;
     return MI32_OK;

@@ -12,16 +12,18 @@
 using namespace mi32;
 
 // A uniform batch on the one-launch paths: the register-resident kernels up to kResidentMaxOrder rows, the
-// workgroup-resident ones above (n <= kWorkgroupMaxOrder is the caller's business).  det: where the determinants go,
-// empty for none; d_inv may be null only with one.  The caller holds h->mu and has set the device.
+// workgroup-resident ones up to kWorkgroupMaxOrder, the wide ones (fp32 only) above (that the order has an instance is
+// the caller's business: above kWorkgroupMaxOrder only a DenseRoute::WIDE call comes here).  det: where the
+// determinants go, empty for none; d_inv may be null only with one.  The caller holds h->mu and has set the device.
 template <typename T>
 static int one_launch_device(mi32_context *h, bool pivoting, const T *d_a, int n, int batch, T *d_inv, int *d_status,
                              const DetOut det)
 {
     MI32_TRY(zeroed_status_buffer(h, d_status, batch, &d_status));
-    const hipError_t e = n <= kResidentMaxOrder
-                             ? resident_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting)
-                             : workgroup_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting);
+    hipError_t e = hipErrorInvalidValue;  // (an fp64 order above kWorkgroupMaxOrder: no instance)
+    if (n <= kResidentMaxOrder) e = resident_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting);
+    else if (n <= kWorkgroupMaxOrder) e = workgroup_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting);
+    else if constexpr (std::is_same<T, float>::value) e = wide_invert(d_a, d_inv, n, batch, d_status, det, h->stream, h->prof, pivoting);
     return hip_status(e, "kernel launch");
 }
 
@@ -130,7 +132,8 @@ int inv_device(mi32_context *h, Settings s, const T *d_a, int n, int batch, T *d
                                 "kernel launch");
             break;
         case DenseRoute::RESIDENT:
-        case DenseRoute::WORKGROUP: break;  // (returned above)
+        case DenseRoute::WORKGROUP:
+        case DenseRoute::WIDE: break;  // (returned above)
     }
     if (rc != MI32_OK || det.empty()) return rc;
     return det_end<T>(h, dm, dr.det_first, n, batch, d_status, s.pivoting, det);
@@ -150,7 +153,7 @@ static int inv_device_checked(mi32_context *h, const T *d_a, int n, int batch, T
 // The inverse with the determinant (see the header); the arguments are checked before the context is touched.  Up to
 // kWorkgroupMaxOrder the one-launch kernels run, whatever the context's algorithm, and no workspace is ensured;
 // max_order bounds mi32_inv_det_device*, and above kWorkgroupMaxOrder mi32_inv_det_any_device* runs the route
-// mi32_inv_device* runs on this context.
+// mi32_inv_device* runs on this context (the wide one-launch path's det twin included).
 template <typename T>
 static int inv_det_device(mi32_context *h, int max_order, const T *d_a, int n, int batch, T *d_inv, int *d_status,
                           double *d_det_mant, int *d_det_exp)

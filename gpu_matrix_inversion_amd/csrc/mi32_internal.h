@@ -257,6 +257,14 @@ int resident_lanes(int n);
 static constexpr int kWorkgroupMaxOrder = 128;
 int workgroup_rows_per_thread(int n);
 
+// wide workgroup-resident path (mi32_wide.hip): fp32 orders kWorkgroupMaxOrder + 1 ... kWideMaxOrder, one launch, no
+// workspace.  One workgroup of wide_threads(n) threads (768 / 1024: 4 slabs of 192 / 256 column lanes) holds one matrix
+// in registers, wide_rows_per_thread(n) rows per thread (40 / 48 / 56 / 64; both 0 when the order is out of range);
+// d_status must not be null.  Bit-identical to the sweep path.
+static constexpr int kWideMaxOrder = 256;
+int wide_rows_per_thread(int n);
+int wide_threads(int n);
+
 // variable-size batches (mi32_vbatch_*): members of any orders 1 ... kWorkgroupMaxOrder, each at its own pointer and
 // leading dimensions, on the two paths above.  Everything here is device memory.  `members` is the plan's list of
 // member indices sorted by order; a launch takes the `count` members from `first` on, which all belong to one kernel
@@ -350,6 +358,9 @@ hipError_t workgroup_invert(const T *d_a, T *d_inv, int n, int batch, int *d_sta
 template <typename T>
 hipError_t workgroup_vinvert(int rows_per_thread, const VbatchArgs<T> &v, DetOut det, int first, int count,
                              hipStream_t stream, Profiler *prof, bool pivoting);
+// the wide path: a uniform fp32 batch only
+hipError_t wide_invert(const float *d_a, float *d_inv, int n, int batch, int *d_status, DetOut det, hipStream_t stream,
+                       Profiler *prof, bool pivoting);
 
 // ---- A X = B on the two paths above, without the inverse (mi32_solve_device*) ----------------------------------------
 // A lane (register-resident) or column (workgroup-resident) j >= n of a member holds zeros, is read by no step and never

@@ -21,6 +21,10 @@ int resolve_algo(const Settings &s, int n, size_t elem_bytes)
     // serves orders on both sides of 64; above 128 it resolves to what AUTO resolves to
     if (algo == MI32_ALGO_WORKGROUP && n <= kWorkgroupMaxOrder)
         return n <= kResidentMaxOrder ? MI32_ALGO_RESIDENT : MI32_ALGO_WORKGROUP;
+    // MI32_ALGO_WIDE up to 256 rows in fp32: the two paths above take the orders they hold, so that one setting serves
+    // every small order; above 256, and in fp64 above 128, it resolves to what AUTO resolves to
+    if (algo == MI32_ALGO_WIDE && n <= (f32 ? kWideMaxOrder : kWorkgroupMaxOrder))
+        return n <= kResidentMaxOrder ? MI32_ALGO_RESIDENT : n <= kWorkgroupMaxOrder ? MI32_ALGO_WORKGROUP : MI32_ALGO_WIDE;
     const int cross = !s.pivoting ? 512 : f32 ? 32 : 256;
     if (algo != MI32_ALGO_SWEEP && algo != MI32_ALGO_BLOCKED) algo = (n >= cross) ? MI32_ALGO_BLOCKED : MI32_ALGO_SWEEP;
     if (f32 && algo == MI32_ALGO_BLOCKED && !blocked_supported(n)) algo = MI32_ALGO_SWEEP;  // panel would not fit in registers
@@ -147,8 +151,8 @@ DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batc
     DenseRoute d;
     d.ws_bytes = 0;  // the one-launch paths keep no working copy
     d.det_steps = d.det_first = 0;
-    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP) {
-        d.path = algo == MI32_ALGO_RESIDENT ? DenseRoute::RESIDENT : DenseRoute::WORKGROUP;
+    if (algo == MI32_ALGO_RESIDENT || algo == MI32_ALGO_WORKGROUP || algo == MI32_ALGO_WIDE) {
+        d.path = algo == MI32_ALGO_RESIDENT ? DenseRoute::RESIDENT : algo == MI32_ALGO_WORKGROUP ? DenseRoute::WORKGROUP : DenseRoute::WIDE;
     } else if (algo == MI32_ALGO_SWEEP) {
         d.path = DenseRoute::SWEEP;
         d.sweep = make_sweep_plan(n);
@@ -444,6 +448,16 @@ int mi32_resolve_workgroup(mi32_handle_t /*h*/, int n, int elem_bytes, int *thre
     return MI32_OK;
 }
 
+int mi32_resolve_wide(mi32_handle_t /*h*/, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread, int *max_order)
+{
+    if (n <= 0 || (elem_bytes != 4 && elem_bytes != 8)) return MI32_BAD_SHAPE;
+    const bool f32 = elem_bytes == 4;  // no fp64 instance: the register file holds no 256 x 256 fp64 matrix
+    if (threads_per_matrix) *threads_per_matrix = f32 ? wide_threads(n) : 0;
+    if (rows_per_thread) *rows_per_thread = f32 ? wide_rows_per_thread(n) : 0;
+    if (max_order) *max_order = kWideMaxOrder;
+    return MI32_OK;
+}
+
 int mi32_resolve_solve(mi32_handle_t /*h*/, int n, int nrhs, int elem_bytes, int *chunk_cols, int *launches, int *lanes,
                        int *rows_per_thread)
 {
@@ -461,7 +475,8 @@ int mi32_resolve_solve(mi32_handle_t /*h*/, int n, int nrhs, int elem_bytes, int
 
 const char *mi32_dominant_kernel(int algo)
 {
-    return algo == MI32_ALGO_WORKGROUP ? "gj_workgroup_kernel"
+    return algo == MI32_ALGO_WIDE ? "gj_wide_kernel"
+           : algo == MI32_ALGO_WORKGROUP ? "gj_workgroup_kernel"
            : algo == MI32_ALGO_RESIDENT ? "gj_resident_kernel"
            : algo == MI32_ALGO_SWEEP  ? "gj_sweep_step_kernel"
                                       : "gj_rank_bw2_kernel";

@@ -67,7 +67,16 @@ typedef enum mi32_algo {
      * any batch size the buffers hold.  The arithmetic of SWEEP, element by element: bit-identical to the CPU
      * oracle, in fp32 and fp64, with and without pivoting.  Never chosen by AUTO; n <= 64 resolves to RESIDENT
      * (one setting serves orders on both sides of 64), n > 128 to what AUTO resolves to. */
-    MI32_ALGO_WORKGROUP = 4
+    MI32_ALGO_WORKGROUP = 4,
+    /* Large batches of fp32 matrices of order 129 ... 256: one launch in which one workgroup of 768 (orders up to 192)
+     * or 1024 threads keeps one matrix in its registers (4 slabs of 192 / 256 column lanes, 40 / 48 / 56 / 64 rows per
+     * thread for orders up to 160 / 192 / 224 / 256) from the load to the un-permuted inverse -- one global read and
+     * one global write per element, no workspace, any batch size the buffers hold.  The arithmetic of SWEEP, element
+     * by element: bit-identical to the CPU oracle, with and without pivoting.  fp32 only: a 256 x 256 fp64 matrix is
+     * the whole register file of a compute unit.  Never chosen by AUTO; n <= 64 resolves to RESIDENT and 65 ... 128 to
+     * WORKGROUP (one setting serves every small order), n > 256 and every fp64 call above 128 to what AUTO resolves
+     * to.  mi32_solve_device* (orders up to 127) and the variable-size calls (orders up to 128) do not reach it. */
+    MI32_ALGO_WIDE = 5
 } mi32_algo;
 
 typedef struct mi32_context *mi32_handle_t;
@@ -225,7 +234,9 @@ int mi32_inv_det_device_f64(mi32_handle_t h, const double *d_a, int n, int batch
  * d_det_mant or d_det_exp, n <= 0, batch <= 0 or d_a == d_inv -> MI32_BAD_SHAPE, decided before the context is
  * touched.  The pivot lists live in memory the context owns for these calls (4 or 8 bytes per padded row and member,
  * grown on demand; mi32_workspace_bytes and mi32_reserve do not count it); calls on one context are ordered by its
- * stream.  The added launches are recorded under profiling class 5. */
+ * stream.  The added launches are recorded under profiling class 5.  On a context set to MI32_ALGO_WIDE an fp32 batch
+ * of order 129 ... 256 is one launch here too: that path's determinant twin accumulates the pair in its registers, as
+ * the kernels below 129 do -- no pivot list, no added launch, (+0.0, 0) / (NaN, 0) for a flagged member as above. */
 int mi32_inv_det_any_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status,
                             double *d_det_mant, int *d_det_exp);
 int mi32_inv_det_any_device_f64(mi32_handle_t h, const double *d_a, int n, int batch, double *d_inv, int *d_status,
@@ -410,6 +421,14 @@ int mi32_resolve_resident(mi32_handle_t h, int n, int elem_bytes, int *lanes_per
  * anything else, or n <= 0, is MI32_BAD_SHAPE.  The output pointers are optional. */
 int mi32_resolve_workgroup(mi32_handle_t h, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
                            int *max_order);
+/* The wide workgroup-resident path (MI32_ALGO_WIDE), answered without a device (h may be NULL): *threads_per_matrix =
+ * threads that hold one matrix of this order (768 for 129 <= n <= 192, 1024 for 193 <= n <= 256 at elem_bytes 4; 0
+ * outside and for every order at elem_bytes 8: WIDE resolves to RESIDENT / WORKGROUP below and to AUTO's choice above
+ * and in fp64), *rows_per_thread = register rows per thread (40 / 48 / 56 / 64 for orders up to 160 / 192 / 224 / 256,
+ * 0 where *threads_per_matrix is), *max_order = the largest order it takes (256).  elem_bytes: 4 (fp32) or 8 (fp64);
+ * anything else, or n <= 0, is MI32_BAD_SHAPE.  The output pointers are optional. */
+int mi32_resolve_wide(mi32_handle_t h, int n, int elem_bytes, int *threads_per_matrix, int *rows_per_thread,
+                      int *max_order);
 /* How mi32_solve_device* would run this shape, answered without a device (h may be NULL): *chunk_cols = the most columns
  * one launch takes (64 - n for n <= 32, 128 - n for 33 <= n <= 127), *launches = ceil(nrhs / *chunk_cols), and the
  * first chunk's kernel: *lanes = lanes per member (8 / 16 / 32 / 64) of the register-resident instance, 0 when the chunk

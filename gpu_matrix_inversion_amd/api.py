@@ -210,6 +210,99 @@ def vbatch_bin(orders):
     return perm, begin
 
 
+def _check_tensor(t, device, dtype, what, numel=None):
+    """ValueError unless ``t`` is a contiguous 1-D tensor of ``dtype`` on ``device`` (of ``numel`` entries)."""
+    if t.device != device:
+        raise ValueError(f"{what} is on {t.device}, expected {device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what} is {t.dtype}, expected {dtype}")
+    if t.dim() != 1 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise ValueError(f"{what}: expected a contiguous 1-D tensor" + (f" of {numel} entries" if numel else ""))
+
+
+def _overlap(a, b):
+    """Whether the storage spans of two contiguous tensors of one device meet."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def check_dense_args(device, a, out=None, status=None, *, b=None, want_inverse=True, max_order=None):
+    """The argument handling of the dense calls, ``inv`` / ``inv_det`` / ``inv_det_any`` and, with ``b`` given,
+    ``solve``: pure torch, no handle and no GPU (``device`` is the Inverter's; CPU tensors with
+    ``torch.device("cpu")`` pass).  Everything a kernel would read or write is checked here, before any address is
+    handed to the library; a refusal is a ValueError.
+
+    * ``a``: float32 / float64 on ``device``, (N,N) or (B,N,N); a non-contiguous ``a`` is copied.
+    * ``b`` (solve): a's dtype and device and a's batch dimension, then (N,) or (N,K).
+    * ``out``: a's dtype on ``device``, contiguous, of ``B*N*N`` elements (solve: of b's shape); its storage span must
+      not meet that of ``a`` anywhere.  In ``solve``, ``out`` may be ``b`` itself or cover exactly b's memory (in
+      place); a partial overlap of the two is refused.
+    * ``status``: a contiguous 1-D int32 tensor of ``B`` entries on ``device``.
+
+    Returns ``(squeeze, a3, rhs, out3, status)``: the contiguous (B,N,N) input, the contiguous (B,N,K) right-hand side
+    (None without ``b``), the output in that shape (allocated where ``out`` is None; None with
+    ``want_inverse=False``) and the status tensor (allocated where None).  ``max_order``: the largest order
+    ``inv_det`` takes."""
+    import torch
+
+    if a.dtype not in (torch.float32, torch.float64) or a.device != device:
+        raise ValueError("expected a float32 or float64 tensor on the GPU" +
+                         (f": a is on {a.device}, this Inverter on {device}" if a.device != device else ""))
+    squeeze = a.dim() == 2
+    a3 = a.unsqueeze(0) if squeeze else a
+    if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
+        raise ValueError("expected (N,N) or (B,N,N)")
+    bsz, n = a3.shape[0], a3.shape[1]
+    if b is None:
+        if max_order is not None and n > max_order:
+            raise ValueError(f"inv_det takes orders up to {max_order}")
+        b3 = None
+    else:
+        if n > 127:
+            raise ValueError("solve takes orders up to 127")
+        if b.dtype != a.dtype or b.device != a.device:
+            raise ValueError(f"b is {b.dtype} on {b.device}, expected a's {a.dtype} on {a.device}")
+        b3 = b.unsqueeze(-1) if b.dim() == a.dim() - 1 else b
+        if squeeze:
+            b3 = b3.unsqueeze(0)
+        if b3.dim() != 3 or b3.shape[0] != bsz or b3.shape[1] != n or b3.shape[2] == 0:
+            raise ValueError("b: expected a's batch dimension, then (N,) or (N,K)")
+    if status is not None:
+        _check_tensor(status, device, torch.int32, "status", bsz)
+    if out is not None:
+        if not want_inverse:
+            raise ValueError("out given with want_inverse=False")
+        if out.dtype != a.dtype or out.device != device:
+            raise ValueError(f"out is {out.dtype} on {out.device}, expected {a.dtype} on {device}")
+    a3 = a3.contiguous()
+    if b is None:
+        rhs = None
+        if not want_inverse:
+            out3 = None
+        elif out is None:
+            out3 = torch.empty_like(a3)
+        else:
+            if out.numel() != a3.numel():
+                raise ValueError(f"out holds {out.numel()} elements, the result {a3.numel()}")
+            if not out.is_contiguous() or _overlap(out, a3):
+                raise ValueError("out must be contiguous and must not alias the input")
+            out3 = out.view(bsz, n, n)
+    elif out is None:
+        rhs, out3 = b3.contiguous(), torch.empty(b3.shape, dtype=b.dtype, device=b.device)
+    else:
+        if out.shape != b.shape or not out.is_contiguous():
+            raise ValueError("out: b itself or a contiguous tensor of b's shape, dtype and device")
+        out3 = out.view(b3.shape)
+        rhs = out3 if out is b else b3.contiguous()
+        if _overlap(out3, a3):
+            raise ValueError("out must not alias a")
+        if rhs.data_ptr() != out3.data_ptr() and _overlap(out3, rhs):
+            raise ValueError("out may be b itself (in place), not a part of b's memory")
+    if status is None:
+        status = torch.empty(bsz, dtype=torch.int32, device=device)
+    return squeeze, a3, rhs, out3, status
+
+
 class RaggedPlan:
     """A batch of members of mixed orders 1 ... 128 (``Inverter.plan_ragged``): the orders, binned once into the eight
     kernel classes and uploaded to the device.  Immutable; usable any number of times and from any ``Inverter`` on
@@ -388,46 +481,25 @@ class Inverter:
     def reserve(self, n: int, batch: int = 1):
         _lib.check(self._lib.mi32_reserve(self._h, int(n), int(batch)), "mi32_reserve")
 
-    def _batch_args(self, a, out, status, want_inverse=True, max_order=None):
-        """The argument handling of ``_dense``: ``(squeeze, a3, out, status)`` with ``a3`` the contiguous (B,N,N) input,
-        ``out`` the (B,N,N) output (None with ``want_inverse=False``) and ``status`` int32[B].  ``max_order``: the
-        largest order ``inv_det`` takes."""
-        torch = self._torch
-        if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
-            raise ValueError("expected a float32 or float64 tensor on the GPU")
-        squeeze = a.dim() == 2
-        a3 = a.unsqueeze(0) if squeeze else a
-        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
-            raise ValueError("expected (N,N) or (B,N,N)")
-        if max_order is not None and a3.shape[1] > max_order:
-            raise ValueError(f"inv_det takes orders up to {max_order}")
-        a3 = a3.contiguous()
-        b, n = a3.shape[0], a3.shape[1]
-        if not want_inverse:
-            if out is not None:
-                raise ValueError("out given with want_inverse=False")
-        elif out is None:
-            out = torch.empty_like(a3)
-        else:
-            out = out.view(b, n, n)
-            if not out.is_contiguous() or out.data_ptr() == a3.data_ptr():
-                raise ValueError("out must be contiguous and must not alias the input")
-        if status is None:
-            status = torch.empty(b, dtype=torch.int32, device=a3.device)
-        return squeeze, a3, out, status
-
     def inv(self, a, out=None, status=None):
         """a: (N,N) or (B,N,N) float32 (or float64: the fp64 twin; sweep or blocked as resolved_blocking_f64
-        reports) contiguous tensor on this device.  Asynchronous on torch's current stream.  Returns (inverse, status int32[B] tensor)."""
+        reports) tensor on this device; a non-contiguous view is copied first, ``a`` is never modified.  ``out``
+        (optional): a contiguous tensor of a's dtype on this device holding ``B*N*N`` elements, whose memory meets a's
+        nowhere; it is returned, viewed as (B,N,N).  ``status`` (optional): a contiguous 1-D int32 tensor of ``B``
+        entries on this device.  Anything else raises ValueError before the library is called
+        (``check_dense_args``).  Element alignment is all ``a`` and ``out`` need, and nothing outside them, ``status``
+        and the determinant pair is read or written.  Asynchronous on torch's current stream.  Returns (inverse,
+        status int32[B] tensor)."""
         return self._dense("mi32_inv_device", a, out, status)
 
     def _dense(self, stem, a, out, status, want_inverse=True, max_order=None, det=False):
-        """The one call behind ``inv``, ``inv_det`` and ``inv_det_any``: the arguments checked (``_batch_args``), then
-        the C entry point ``stem`` (float32) or ``stem + "_f64"`` on torch's current stream.  Returns ``(inverse,
-        status)``; with ``det`` the entry point takes the two determinant arrays as well and they are returned behind,
-        the inverse being None with ``want_inverse=False``."""
+        """The one call behind ``inv``, ``inv_det`` and ``inv_det_any``: the arguments checked
+        (``check_dense_args``), then the C entry point ``stem`` (float32) or ``stem + "_f64"`` on torch's current
+        stream.  Returns ``(inverse, status)``; with ``det`` the entry point takes the two determinant arrays as well
+        and they are returned behind, the inverse being None with ``want_inverse=False``."""
         torch = self._torch
-        squeeze, a3, out, status = self._batch_args(a, out, status, want_inverse, max_order)
+        squeeze, a3, _, out, status = check_dense_args(self.device, a, out, status, want_inverse=want_inverse,
+                                                       max_order=max_order)
         b, n = a3.shape[0], a3.shape[1]
         pair = ptrs = ()
         if det:
@@ -443,7 +515,7 @@ class Inverter:
 
     def inv_det(self, a, out=None, status=None, want_inverse=True):
         """The inverse and the determinant of every member from one launch.  a: (N,N) or (B,N,N) float32 / float64 on
-        this device, N <= 128 (a larger N raises ValueError).  Returns ``(inverse, status, det_mant, det_exp)``:
+        this device, N <= 128 (a larger N raises ValueError); ``out`` and ``status`` as for ``inv``.  Returns ``(inverse, status, det_mant, det_exp)``:
         ``det = det_mant * 2**det_exp`` with ``det_mant`` float64[B], ``|det_mant|`` in [0.5, 1), and ``det_exp``
         int32[B] (``slogdet_from_frexp`` / ``det_from_frexp`` turn the pair into log-determinant and sign, or the value).
         A singular member's pair is ``(0.0, 0)`` where an exactly zero pivot was met with pivoting on, ``(NaN, 0)``
@@ -479,43 +551,20 @@ class Inverter:
         """X with A X = B for every member, without forming the inverse: Gauss-Jordan on [A | B] in the one-launch
         batch kernels.  a: (N,N) or (B,N,N) float32 / float64 on this device, N <= 127 (a larger N raises ValueError).
         b: a's dtype and device and a's batch dimension, then (N,) -- one vector per member, the result keeps that
-        shape -- or (N,K).  ``out`` may be ``b`` itself (in place) or a contiguous tensor of b's shape; it must not
-        alias ``a``.  Returns ``(x, status int32[B])``; x of a member whose status is not 0 is unspecified.  With
+        shape -- or (N,K).  ``out`` may be ``b`` itself (in place) or a contiguous tensor of b's shape, dtype and device;
+        its memory must meet a's nowhere, and b's either wholly (in place) or not at all.  ``status`` (optional): a
+        contiguous 1-D int32 tensor of ``B`` entries on this device.  Anything else raises ValueError before the library
+        is called (``check_dense_args``).  ``a`` is never modified, ``b`` only in place; element alignment is all the
+        three need.  Returns ``(x, status int32[B])``; x of a member whose status is not 0 is unspecified.  With
         ``b`` the identity, x is ``inv``'s result bit for bit.  More than ``resolved_solve(N, K)[0]`` columns take one
         launch per chunk, and every launch repeats the elimination of A.  Always runs on the register-resident or
         workgroup-resident kernels, whatever ``algo`` is.  Asynchronous on torch's current stream."""
         torch = self._torch
-        if a.dtype not in (torch.float32, torch.float64) or not a.is_cuda:
-            raise ValueError("expected a float32 or float64 tensor on the GPU")
-        squeeze = a.dim() == 2
-        a3 = a.unsqueeze(0) if squeeze else a
-        if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[0] == 0 or a3.shape[1] == 0:
-            raise ValueError("expected (N,N) or (B,N,N)")
+        _, a3, rhs, out3, status = check_dense_args(self.device, a, out, status, b=b)
         bsz, n = a3.shape[0], a3.shape[1]
-        if n > 127:
-            raise ValueError("solve takes orders up to 127")
-        if b.dtype != a.dtype or b.device != a.device:
-            raise ValueError(f"b is {b.dtype} on {b.device}, expected a's {a.dtype} on {a.device}")
-        b3 = b.unsqueeze(-1) if b.dim() == a.dim() - 1 else b
-        if squeeze:
-            b3 = b3.unsqueeze(0)
-        if b3.dim() != 3 or b3.shape[0] != bsz or b3.shape[1] != n or b3.shape[2] == 0:
-            raise ValueError("b: expected a's batch dimension, then (N,) or (N,K)")
-        a3 = a3.contiguous()
-        if out is None:
-            rhs, out3 = b3.contiguous(), torch.empty(b3.shape, dtype=b.dtype, device=b.device)
-        else:
-            if out.shape != b.shape or out.dtype != b.dtype or out.device != b.device or not out.is_contiguous():
-                raise ValueError("out: b itself or a contiguous tensor of b's shape, dtype and device")
-            out3 = out.view(b3.shape)
-            rhs = out3 if out is b else b3.contiguous()
-            if out3.data_ptr() == a3.data_ptr():
-                raise ValueError("out must not alias a")
-        if status is None:
-            status = torch.empty(bsz, dtype=torch.int32, device=a3.device)
         self._bind_stream()
         fn = self._lib.mi32_solve_device if a.dtype == torch.float32 else self._lib.mi32_solve_device_f64
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, bsz, ctypes.c_void_p(rhs.data_ptr()), b3.shape[2],
+        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, bsz, ctypes.c_void_p(rhs.data_ptr()), rhs.shape[2],
                       ctypes.c_void_p(out3.data_ptr()), ctypes.c_void_p(status.data_ptr())), "mi32_solve_device")
         return out3.view(b.shape), status
 
@@ -531,12 +580,7 @@ class Inverter:
             raise ValueError(f"the plan lives on {plan.device}, this Inverter on {self.device}")
 
     def _check_tensor(self, t, dtype, what, numel=None):
-        if t.device != self.device:
-            raise ValueError(f"{what} is on {t.device}, expected {self.device}")
-        if t.dtype != dtype:
-            raise ValueError(f"{what} is {t.dtype}, expected {dtype}")
-        if t.dim() != 1 or not t.is_contiguous() or (numel is not None and t.numel() != numel):
-            raise ValueError(f"{what}: expected a contiguous 1-D tensor" + (f" of {numel} entries" if numel else ""))
+        _check_tensor(t, self.device, dtype, what, numel)
 
     def inv_pointers(self, plan, a_ptrs, out_ptrs, dtype, lda=None, ldout=None, status=None, *, det=False):
         """The low-level form: ``a_ptrs`` / ``out_ptrs`` are int64 device tensors of ``plan.batch`` member addresses
@@ -742,11 +786,7 @@ class Inverter:
         _lib.check(fn(self._h, plan._p, ptr(x_ptrs), ptr(ldx), ptr(r_ptrs), ptr(ldr), int(nrhs), ptr(z_ptrs), ptr(ldz)),
                    "mi32_apply_device_vbatched")
 
-    @staticmethod
-    def _overlap(a, b):
-        """Whether the storage spans of two contiguous tensors of one device meet."""
-        a0, b0 = a.data_ptr(), b.data_ptr()
-        return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+    _overlap = staticmethod(_overlap)
 
     def apply_ragged(self, plan, x_flat, r, out=None):
         """``z = blockdiag(X) r`` for members of mixed orders 1 ... 128 in one call: with ``x_flat`` the inverses

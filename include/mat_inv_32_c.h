@@ -127,7 +127,19 @@ int mi32_reserve(mi32_handle_t h, int n, int batch);
  * not modified, d_inv may not alias d_a.  d_status: device int[batch] (may be
  * NULL: the context then keeps the status words itself).  Asynchronous: everything is enqueued on the context's stream and the
  * call returns without synchronising.  The call shape, minus the host copies,
- * of mat_inv_32.cpp:292-376 (makeAugmented -> N pivot steps -> getInverted). */
+ * of mat_inv_32.cpp:292-376 (makeAugmented -> N pivot steps -> getInverted).
+ *
+ * The memory contract of the dense device calls -- mi32_inv_device*, mi32_inv_det_device*,
+ * mi32_inv_det_any_device*, mi32_solve_device* and mi32_residual_device -- on every route (sweep, blocked, the
+ * one-launch paths, either precision, with pivoting and without, a batch split in two halves included):
+ *   - element alignment is all d_a, d_inv, d_b, d_x, d_status, d_det_mant and d_det_exp need;
+ *   - nothing outside batch * n * n elements of d_a and d_inv (batch * n * nrhs of d_b and d_x), batch status words
+ *     and batch determinant pairs is read or written: padded rows and columns, tail groups and tail workgroups stay
+ *     inside the context's workspace or in registers.  With d_inv == NULL (the determinant-only forms) and with
+ *     d_status == NULL nothing is stored in their place;
+ *   - d_a is not modified on any route, and d_b only when d_x == d_b.
+ * tests/test_gpu_memory_contract.py pins this with views carved out of larger buffers, one element off a 256-byte
+ * boundary, between NaN margins (inputs) and sentinel margins (outputs, status, determinant pair). */
 int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status);
 
 /* ---- fp64 (the reference's matrix_inversion_FP64, matrix_inversion/headers.h:9) ---------------- */

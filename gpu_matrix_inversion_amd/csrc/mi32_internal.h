@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mat_inv_32_c.h"
 
 namespace mi32 {
@@ -264,6 +266,26 @@ int workgroup_rows_per_thread(int n);
 static constexpr int kWideMaxOrder = 256;
 int wide_rows_per_thread(int n);
 int wide_threads(int n);
+
+// f(value, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time pair picks
+// a kernel instance of the one-launch batch paths.  false: `value` is none of Vs, and f was not called.
+template <int... Vs, typename F>
+static bool pick_instance(int value, bool pivoting, F f)
+{
+    const auto pick = [&](auto c) {
+        if (value != decltype(c)::value) return false;
+        if (pivoting) f(c, std::true_type{});
+        else f(c, std::false_type{});
+        return true;
+    };
+    return (pick(std::integral_constant<int, Vs>{}) || ...);
+}
+// the instances of slab_member (mi32_slab.h) on both paths above, by their rows per thread
+template <typename F>
+static bool slab_instance(int rows_per_thread, bool pivoting, F f)
+{
+    return pick_instance<40, 48, 56, 64>(rows_per_thread, pivoting, f);
+}
 
 // variable-size batches (mi32_vbatch_*): members of any orders 1 ... kWorkgroupMaxOrder, each at its own pointer and
 // leading dimensions, on the two paths above.  Everything here is device memory.  `members` is the plan's list of

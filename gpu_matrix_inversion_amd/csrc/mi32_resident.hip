@@ -427,23 +427,11 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_vkernel(co
     if (bad) v.status[m] = MI32_SINGULAR;
 }
 
-// f(lanes, pivot), both as compile-time constants (std::integral_constant): the one place where a run-time pair picks
-// a kernel instance.  false: no instance has that many lanes per matrix.
+// the instances by their lanes per matrix (pick_instance of mi32_internal.h)
 template <typename F>
 static bool resident_instance(int lanes, bool pivoting, F f)
 {
-    const auto pick = [&](auto l) {
-        if (pivoting) f(l, std::true_type{});
-        else f(l, std::false_type{});
-        return true;
-    };
-    switch (lanes) {
-        case 8: return pick(std::integral_constant<int, 8>{});
-        case 16: return pick(std::integral_constant<int, 16>{});
-        case 32: return pick(std::integral_constant<int, 32>{});
-        case 64: return pick(std::integral_constant<int, 64>{});
-        default: return false;
-    }
+    return pick_instance<8, 16, 32, 64>(lanes, pivoting, f);
 }
 
 template <typename T>

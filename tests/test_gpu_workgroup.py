@@ -12,9 +12,9 @@ import pytest
 
 from batch_helpers import assert_members_equal, median_ms
 from conftest import gate_matrix
-from workgroup_cases import (BIG_BATCH, BIG_DISTINCT, BIG_ORDER, FP64_ORDERS, KINDS, MEMBERS, ORDERS, TIE_ORDERS,
-                             TIMED_SHAPES, big_distinct, big_index, dominant, dominant_batch, family_batch, mixed_batch,
-                             oracle_batch, run, tie_batch, zero_diagonal_entry)
+from workgroup_cases import (BIG_BATCH, BIG_DISTINCT, BIG_ORDER, FP64_ORDERS, KINDS, MEMBERS, ORDERS, SLOT_ORDERS,
+                             TIE_ORDERS, TIMED_SHAPES, big_distinct, big_index, dominant, dominant_batch, family_batch,
+                             mixed_batch, oracle_batch, run, slot_batch_of_three, tie_batch, zero_diagonal_entry)
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +85,22 @@ def test_ties_the_lowest_row_wins(oracle, inv_wg, n):
     got, st = run(inv_wg, mats)
     assert list(st) == [0] * 16
     assert_members_equal(got, want, n)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("n", SLOT_ORDERS)
+def test_the_pivot_in_every_slab_and_slot(oracle, inv_wg, n, dtype):
+    """Member 1 is the anti-diagonal permutation: the pivot of step r sits in register slot n - 1 - r, so every case of
+    the pick / put switch of both slabs and both label registers is visited.  Member 0 is a signed power-of-two
+    permutation; both inverses are exact and known in closed form, and the oracle agrees with them.  Member 2 is a
+    dense matrix.  The wide path's test of this name (tests/test_gpu_wide.py) runs the same loops of the same body."""
+    mats, exact = slot_batch_of_three(n, dtype)
+    assert mats.shape == (3, n, n) and mats.dtype == dtype
+    want, want_st = oracle_batch(oracle.matrix_inv_32 if dtype == np.float32 else oracle.matrix_inv_64, mats, n)
+    assert list(want_st) == [0, 0, 0] and np.array_equal(want[:2], exact)
+    got, st = run(inv_wg, mats)
+    assert got.dtype == dtype and list(st) == [0, 0, 0]
+    assert_members_equal(got, want, (n, dtype))
 
 
 def test_invalid_members_among_valid_ones(oracle, inv_wg):

@@ -6,9 +6,9 @@ import numpy as np
 import overflow_cases as ovf
 import subnormal_cases as sub
 from conftest import gate_matrix
-from degenerate_cases import duplicate_rows, signed_pow2_permutation, zero_column
+from degenerate_cases import duplicate_rows, zero_column
 from resident_cases import dist_matrix, dominant, oracle_batch, run, tie_batch  # noqa: F401
-from workgroup_cases import mixed_batch, zero_diagonal_entry  # noqa: F401
+from workgroup_cases import anti_diagonal, mixed_batch, slot_batch, zero_diagonal_entry  # noqa: F401
 
 KINDS = ("gate", "ref100", "rand", "hollow")
 ORDERS = list(range(129, 257))
@@ -44,20 +44,6 @@ def family_batch(kind, n, members=MEMBERS):
 
 def dominant_batch(n, dtype=np.float32, members=MEMBERS):
     return np.stack([dominant(n, 700 + n + b, dtype) for b in range(members)])
-
-
-def anti_diagonal(n):
-    """The exchange matrix: the pivot of step r is the 1 of row n - 1 - r, which never leaves register slot n - 1 - r
-    (rows are relabelled, not moved), so the n steps visit every slot of every slab and every label register."""
-    return np.ascontiguousarray(np.eye(n, dtype=np.float32)[::-1])
-
-
-def slot_batch(n):
-    """(batch, exact inverses): a signed power-of-two permutation matrix and the anti-diagonal one; both inverses are
-    known in closed form."""
-    a, x = signed_pow2_permutation(n, 4300 + n)
-    j = anti_diagonal(n)
-    return np.stack([a, j]), np.stack([x, j])
 
 
 def late_singular_batch(n):

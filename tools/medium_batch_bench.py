@@ -69,7 +69,7 @@ def timed(torch, inv, a, warmup, calls):
         if i >= warmup:
             ts.append((time.perf_counter() - t0) * 1e3)
     bad = int((st != 0).sum())
-    return statistics.median(ts), min(ts), out, bad
+    return statistics.median(ts), (min(ts), max(ts)), out, bad
 
 
 def leg(ms, n, batch, elem_bytes):
@@ -96,7 +96,8 @@ def measure(torch, n, batch, dtype, pivoting, with_parent, warmup, calls):
         ms, best, x_wg, bad = timed(torch, wg, a, warmup, calls)
     finally:
         wg.close()
-    row["workgroup"] = dict(leg(ms, n, batch, elem), min_ms=round(best, 4), nonzero_status=bad,
+    row["workgroup"] = dict(leg(ms, n, batch, elem), min_ms=round(best[0], 4), max_ms=round(best[1], 4),
+                            nonzero_status=bad,
                             workspace_bytes=int(lib.mi32_workspace_bytes(n, batch, _lib.ALGO_WORKGROUP)),
                             rows_per_thread=rows_per_thread(n, elem))
     if not with_parent:
@@ -117,7 +118,8 @@ def measure(torch, n, batch, dtype, pivoting, with_parent, warmup, calls):
         ms_p, best_p, x_par, bad_p = timed(torch, auto, a, warmup, calls)
     finally:
         auto.close()
-    row["parent"] = dict(leg(ms_p, n, batch, elem), min_ms=round(best_p, 4), nonzero_status=bad_p,
+    row["parent"] = dict(leg(ms_p, n, batch, elem), min_ms=round(best_p[0], 4), max_ms=round(best_p[1], 4),
+                         nonzero_status=bad_p,
                          algo=ALGO_LABEL[algo], workspace_bytes=ws)
     row["speedup"] = round(ms_p / ms, 2)
     row["same_values"] = bool(torch.equal(x_wg, x_par))

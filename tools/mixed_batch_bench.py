@@ -74,7 +74,8 @@ def timed_pair(torch, one, loop, warmup, calls):
 
 def leg(ts, members, bytes_moved):
     ms = statistics.median(ts)
-    return {"ms": round(ms, 4), "min_ms": round(min(ts), 4), "members_per_s": round(members / (ms * 1e-3)),
+    return {"ms": round(ms, 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
+            "members_per_s": round(members / (ms * 1e-3)),
             "effective_GBps": round(bytes_moved / (ms * 1e-3) / 1e9, 1)}
 
 

@@ -72,7 +72,7 @@ def timed(torch, inv, a, warmup, calls):
         if i >= warmup:
             ts.append((time.perf_counter() - t0) * 1e3)
     bad = int((st != 0).sum())
-    return statistics.median(ts), min(ts), out, bad
+    return statistics.median(ts), (min(ts), max(ts)), out, bad
 
 
 def leg(ms, n, batch):
@@ -98,7 +98,7 @@ def measure(torch, n, batch, warmup, calls):
     finally:
         wide.close()
     threads, rows = wide_class(n)
-    row["wide"] = dict(leg(ms, n, batch), min_ms=round(best, 4), nonzero_status=bad,
+    row["wide"] = dict(leg(ms, n, batch), min_ms=round(best[0], 4), max_ms=round(best[1], 4), nonzero_status=bad,
                        workspace_bytes=int(lib.mi32_workspace_bytes(n, batch, _lib.ALGO_WIDE)), threads=threads,
                        rows_per_thread=rows)
     ws = int(lib.mi32_workspace_bytes(n, batch, _lib.ALGO_AUTO))
@@ -118,7 +118,8 @@ def measure(torch, n, batch, warmup, calls):
         ms_p, best_p, x_par, bad_p = timed(torch, auto, a, warmup, calls)
     finally:
         auto.close()
-    row["parent"] = dict(leg(ms_p, n, batch), min_ms=round(best_p, 4), nonzero_status=bad_p, algo=ALGO_LABEL[algo],
+    row["parent"] = dict(leg(ms_p, n, batch), min_ms=round(best_p[0], 4), max_ms=round(best_p[1], 4),
+                         nonzero_status=bad_p, algo=ALGO_LABEL[algo],
                          workspace_bytes=ws)
     row["speedup"] = round(ms_p / ms, 2)
     row["same_values"] = bool(torch.equal(x_wide, x_par))

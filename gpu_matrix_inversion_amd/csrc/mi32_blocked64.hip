@@ -134,17 +134,134 @@ __global__ __launch_bounds__(64) void b64_block_prep_kernel(const double *__rest
 
 // ---- one pivot step on the block's columns [col_lo, col_lo + 4 * TX) ---------------------------
 // The fused step of mi32_sweep.hip (same arithmetic, see there) on a window: TX column threads (4 columns each) x
-// 256 / TX rows per pass, TR rows per workgroup.
+// 256 / TX rows per pass, TR rows per workgroup.  The body of b64_panel_step_kernel and of its det twin
+// b64_panel_step_det_kernel below.  DET: the thread that updates the maps and the status also stores the step's pivot
+// to det_piv[b * det_pstride + r] and counts an exchange in det_parity[b] (mi32_det_large.h); the three det arguments
+// are not read otherwise.
+template <int TX, int TR, bool DET>
+__device__ __forceinline__ void b64_step(const double *__restrict__ src_all, double *__restrict__ dst_all, int np, int ld,
+                                         size_t wstride, int r, int col_lo,
+                                         const PivotRec<double> *__restrict__ keys_in,
+                                         PivotRec<double> *__restrict__ keys_out, int npart, int *__restrict__ orig,
+                                         int *__restrict__ rowmap, int *__restrict__ status,
+                                         double *__restrict__ det_piv, size_t det_pstride, int *__restrict__ det_parity)
+{
+    constexpr int TY = kB64Threads / TX;  // rows per pass
+    const int b = blockIdx.z;
+    const int tid = threadIdx.x;
+    const double *src = src_all + (size_t)b * wstride;
+    double *dst = dst_all + (size_t)b * wstride;
+
+    const int tx = tid % TX, ty = tid / TX;
+    const int j4 = col_lo + tx * 4;
+    const int rc = r - j4;  // component of column r inside this thread's group, if 0..3
+    const bool has_r = (rc >= 0 && rc < 4);
+    const int nc = r + 1 - j4;
+    const bool has_next = (nc >= 0 && nc < 4);  // column r + 1 belongs to this window and this thread
+    const int row0 = blockIdx.y * TR;
+
+    // The step is a chain of dependent global-memory round trips (records -> pivot row -> rows): this workgroup's
+    // rows do not depend on the pivot search (but for the one row that receives the old row r), so they are
+    // requested FIRST and arrive while the records are reduced and the pivot row is fetched.
+    constexpr int NP = (TR + TY - 1) / TY;  // passes over the rows
+    double fv[NP];
+    Vec4<double> vv[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = row0 + ty + q * TY;
+        const bool ok = (ty + q * TY < TR) && (i < np);
+        fv[q] = ok ? src[(size_t)i * ld + r] : 0.0;
+        vv[q] = ok ? *reinterpret_cast<const Vec4<double> *>(src + (size_t)i * ld + j4) : Vec4<double>{0.0, 0.0, 0.0, 0.0};
+    }
+
+    // finalMaxPivot: reduce the per-row-tile records of column r
+    PivotRec<double> k = PivotRec<double>::none();
+    for (int t = tid; t < npart; t += kB64Threads) {
+        const PivotRec<double> o = keys_in[(size_t)b * npart + t];
+        k = decltype(k)::best_of(o, k);
+    }
+    const int p = block_max_rec<double, kB64Threads>(k).row(r);
+    const double piv = src[(size_t)p * ld + r];  // read before the swap, as mat_inv_32.cpp:70,129-130
+
+    // fixRow: the normalised pivot row slice (IEEE division), identity entry -> 1/piv
+    Vec4<double> prn;
+    {
+        const Vec4<double> pr = *reinterpret_cast<const Vec4<double> *>(src + (size_t)p * ld + j4);
+        prn.x = pr.x / piv;
+        prn.y = pr.y / piv;
+        prn.z = pr.z / piv;
+        prn.w = pr.w / piv;
+        // (the picks by rc / nc stay spelled out here: set_comp / comp of mi32_sweep_common.h give this kernel another
+        // register allocation -- fewer SGPRs, one VGPR more at TX = 64, TR = 32)
+        if (has_r) {
+            const double one = 1.0 / piv;
+            if (rc == 0) prn.x = one; else if (rc == 1) prn.y = one; else if (rc == 2) prn.z = one; else prn.w = one;
+        }
+    }
+    // pivotElements + fixColumn over this workgroup's rows
+    PivotRec<double> best = PivotRec<double>::none();
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int i = row0 + ty + q * TY;
+        if (!((ty + q * TY < TR) && (i < np))) continue;
+        double f = fv[q];
+        Vec4<double> o = vv[q];
+        if (i == p && p != r) {  // slot p receives the old row r (the swap of pivotElements, done by redirecting the read)
+            f = src[(size_t)r * ld + r];
+            o = *reinterpret_cast<const Vec4<double> *>(src + (size_t)r * ld + j4);
+        }
+        if (i == r) {
+            o = prn;
+        } else {
+            if (has_r) {  // the implicit identity column's entry in this row
+                if (rc == 0) o.x = 0.0; else if (rc == 1) o.y = 0.0; else if (rc == 2) o.z = 0.0; else o.w = 0.0;
+            }
+            if (f != 0.0) o = fma4_neg<double>(f, prn, o);
+        }
+        *reinterpret_cast<Vec4<double> *>(dst + (size_t)i * ld + j4) = o;
+        if (has_next && i > r) {
+            const double v = (nc == 0) ? o.x : (nc == 1) ? o.y : (nc == 2) ? o.z : o.w;
+            const PivotRec<double> kk = PivotRec<double>::make(v, i);
+            best = decltype(best)::best_of(kk, best);
+        }
+    }
+    // maxPivot record of column r + 1 for the next launch: the TY threads (one tx) that own that column hold
+    // partial results; thread (tx, 0) folds them.  Absent at the last step of a window (column r + 1 then belongs
+    // to the next block: b64_block_prep_kernel writes its records after the rank-bw update).
+    __shared__ PivotRec<double> s_part[TY];
+    if (has_next) s_part[ty] = best;
+    __syncthreads();
+    if (has_next && ty == 0) {
+        PivotRec<double> m = s_part[0];
+#pragma unroll
+        for (int q = 1; q < TY; ++q) m = PivotRec<double>::best_of(s_part[q], m);
+        keys_out[(size_t)b * npart + blockIdx.y] = m;
+    }
+    if (blockIdx.y == 0 && tid == 0) {
+        if (p != r) {
+            int *og = orig + (size_t)b * np;
+            const int t = og[r]; og[r] = og[p]; og[p] = t;
+            int *rm = rowmap + (size_t)b * np;
+            const int t2 = rm[r]; rm[r] = rm[p]; rm[p] = t2;
+        }
+        if (status && pivot_unusable(piv)) status[b] = MI32_SINGULAR;
+        if constexpr (DET) {  // this thread owns the parity word and the launches are ordered
+            det_piv[(size_t)b * det_pstride + r] = piv;
+            if (p != r) det_parity[b] ^= 1;
+        }
+    }
+}
+
 template <int TX, int TR>
 __global__ __launch_bounds__(kB64Threads) void b64_panel_step_kernel(
     const double *__restrict__ src_all, double *__restrict__ dst_all, int np, int ld, size_t wstride, int r, int col_lo,
     const PivotRec<double> *__restrict__ keys_in, PivotRec<double> *__restrict__ keys_out, int npart,
     int *__restrict__ orig, int *__restrict__ rowmap, int *__restrict__ status)
 {
-#include "mi32_b64_step_body.h"
+    b64_step<TX, TR, false>(src_all, dst_all, np, ld, wstride, r, col_lo, keys_in, keys_out, npart, orig, rowmap, status,
+                            nullptr, 0, nullptr);
 }
-// The det twin (mi32_inv_det_any_device_f64): the same step, and the pivot of step r to det_piv[b * det_pstride + r], an
-// exchange counted in det_parity[b].  b64_launch_step launches it only for a det call.
+// The det twin (mi32_inv_det_any_device_f64): b64_launch_step launches it only for a det call.
 template <int TX, int TR>
 __global__ __launch_bounds__(kB64Threads) void b64_panel_step_det_kernel(
     const double *__restrict__ src_all, double *__restrict__ dst_all, int np, int ld, size_t wstride, int r, int col_lo,
@@ -152,9 +269,8 @@ __global__ __launch_bounds__(kB64Threads) void b64_panel_step_det_kernel(
     int *__restrict__ orig, int *__restrict__ rowmap, int *__restrict__ status, double *__restrict__ det_piv,
     size_t det_pstride, int *__restrict__ det_parity)
 {
-#define MI32_STEP_DET
-#include "mi32_b64_step_body.h"
-#undef MI32_STEP_DET
+    b64_step<TX, TR, true>(src_all, dst_all, np, ld, wstride, r, col_lo, keys_in, keys_out, npart, orig, rowmap, status,
+                           det_piv, det_pstride, det_parity);
 }
 
 // ---- the rank-bw update on the fp64 matrix cores --------------------------------------------------

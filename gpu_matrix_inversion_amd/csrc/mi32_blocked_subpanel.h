@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void gj_diag_panel_kernel(SubpanelArgs A)
     bool singular = false;
     for (int m = 0; m < W; ++m) {
         const float piv = s_d[m * W + m];
-        if (piv == 0.0f || piv - piv != 0.0f) singular = true;
+        if (pivot_unusable(piv)) singular = true;
         // fixRow (IEEE division); the identity column's entry 1 becomes 1/piv
         for (int c = tid; c < W; c += 256) s_prn[m * W + c] = (c == m ? 1.0f : s_d[m * W + c]) / piv;
         __syncthreads();

@@ -1,9 +1,10 @@
 // mi32_det_large.h -- the determinant beside the inverse above order kWorkgroupMaxOrder (mi32_inv_det_any_device*), on
 // the sweep and blocked paths.  The pivots of those paths are spread over launches: every route records them, in step
 // order, into a per-matrix list the context owns for det calls, and one finish kernel runs the recurrence of
-// mi32_internal.h (det_accumulate) over the list.  No elimination kernel changes: the step kernels that hold a pivot
-// in a register only (sweep, fp64 blocked with pivoting) have a det twin that shares their body (mi32_sweep_step_body.h,
-// mi32_b64_step_body.h: included into both kernels, the det lines behind MI32_STEP_DET).
+// mi32_internal.h (det_accumulate) over the list.  A plain call runs the kernels it always ran: the step kernels that
+// hold a pivot in a register only (sweep, fp64 blocked with pivoting) have a det twin, a second __global__ entry point
+// of the same body (sweep_step in mi32_sweep.hip, b64_step in mi32_blocked64.hip: one template with a bool DET, the
+// det lines under `if constexpr (DET)`).
 //
 // Two facts about the sign.  (1) IEEE multiplication and frexp are sign-symmetric, so the per-step flips `if (swap) m =
 // -m` may all be applied at the end as one parity: the pair is bit-identical.  (2) Every exchanging step is one

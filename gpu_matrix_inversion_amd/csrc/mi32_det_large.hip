@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64) void det_finish_kernel(const T *__restrict__ pi
         for (int base = 0; base < n; base += 64) {
             const int cnt = (n - base < 64) ? n - base : 64;
             const T v = (lane < cnt) ? piv[base + lane] : T(1);
-            const bool bad = v == T(0) || v - v != T(0);  // zero, NaN or infinite
+            const bool bad = pivot_unusable(v);
             const double pd = (double)v;                  // exact
             const double pm = __builtin_amdgcn_frexp_mant(pd);
             const int pe = __builtin_amdgcn_frexp_exp(pd);

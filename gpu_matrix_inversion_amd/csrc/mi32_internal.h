@@ -25,6 +25,9 @@ __device__ __forceinline__ int pivot_key_row(unsigned long long key, int fallbac
 {
     return key == 0ull ? fallback_row : (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
 }
+// the pivot that flags its matrix MI32_SINGULAR on every path: zero, NaN or infinite
+template <typename T>
+__device__ __forceinline__ bool pivot_unusable(T piv) { return piv == T(0) || piv - piv != T(0); }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
 {

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(8 * BW) void np64_diag_kernel(double *__restrict__ 
             ftm += np;
             if (t == 0) {
                 pv[m] = piv;
-                bad = bad || piv == 0.0 || piv - piv != 0.0;  // zero, NaN or infinite pivot
+                bad = bad || pivot_unusable(piv);
             }
             if (m + 1 < BW) {
                 const int s1 = (s + 1) % RPT, g1 = (s + 1 == RPT) ? gm + 1 : gm;

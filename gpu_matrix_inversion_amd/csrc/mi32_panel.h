@@ -205,7 +205,7 @@ __device__ __forceinline__ void panel_step(float (&a)[RPT][W], unsigned (&npl)[R
             // (the steps below leave columns <= R alone).  Should it win, the register takes to LDS what the epilogue
             // needs instead: lanes < R the multiplier as found, lane W the pivot.
             if constexpr (TRI) qv = (lane < R) ? num : (lane == W ? cpiv : qv);
-            cand_bad = (cpiv == 0.0f || cpiv - cpiv != 0.0f);
+            cand_bad = pivot_unusable(cpiv);
             if (kSub) MI32_PSTAMP(pg.tag_base, 37);
             if (lane < W) sh.prn[par][wave_u][lane] = qv;
             if (lane == 0)

@@ -127,29 +127,108 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_init_kernel(const T *__re
 }
 
 // ---- one pivot step ---------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ Vec4<T> fma4_neg(T f, Vec4<T> a, Vec4<T> c)
-{
-    Vec4<T> o;
-    o.x = fma_t(-f, a.x, c.x);
-    o.y = fma_t(-f, a.y, c.y);
-    o.z = fma_t(-f, a.z, c.z);
-    o.w = fma_t(-f, a.w, c.w);
-    return o;
-}
-template <typename T>
-__device__ __forceinline__ T comp(const Vec4<T> &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-template <typename T>
-__device__ __forceinline__ void set_comp(Vec4<T> &v, int c, T x)
-{
-    if (c == 0) v.x = x;
-    else if (c == 1) v.y = x;
-    else if (c == 2) v.z = x;
-    else v.w = x;
-}
-
+// The body of gj_sweep_step_kernel and of its det twin gj_sweep_step_det_kernel below.
 // PIVOT = false: the reference's no-pivot variant (matrix_inversion_no_pivots.cpp:10): the pivot of step r is the
 // diagonal entry (findCrr, :41-45) -- no arg-max records are read or written, no row is swapped.
+// DET: the thread that updates orig and the status also stores the step's pivot to det_piv[b * det_pstride + r] and
+// counts an exchange in det_parity[b] (mi32_det_large.h); the three det arguments are not read otherwise.
+template <typename T, int TR, bool PIVOT, bool DET>
+__device__ __forceinline__ void sweep_step(const T *__restrict__ src_all, T *__restrict__ dst_all, int n, int ld,
+                                           size_t wstride, int r, const PivotRec<T> *__restrict__ keys_in,
+                                           PivotRec<T> *__restrict__ keys_out, int npart, int *__restrict__ orig,
+                                           int *__restrict__ status, T *__restrict__ det_piv, size_t det_pstride,
+                                           int *__restrict__ det_parity)
+{
+    const int b = blockIdx.z;
+    const int tid = threadIdx.x;
+    const T *src = src_all + (size_t)b * wstride;
+    T *dst = dst_all + (size_t)b * wstride;
+
+    // 1. finalMaxPivot: reduce the per-row-tile records of column r
+    int p = r;
+    if constexpr (PIVOT) {
+        PivotRec<T> k = PivotRec<T>::none();
+        for (int t = tid; t < npart; t += kSweepThreads) {
+            const PivotRec<T> o = keys_in[(size_t)b * npart + t];
+            k = decltype(k)::best_of(o, k);
+        }
+        p = block_max_rec<T, kSweepThreads>(k).row(r);
+    }
+    const T piv = src[(size_t)p * ld + r];  // read before the swap, as mat_inv_32.cpp:70,129-130
+
+    const int j4 = (blockIdx.x * kSweepThreads + tid) * 4;
+    const bool active = j4 < ld;
+    const int rc = r - j4;                   // component of column r inside this thread's group, if 0..3
+    const bool has_r = (rc >= 0 && rc < 4);
+    const int nc = r + 1 - j4;               // component of column r+1
+    const bool has_next = PIVOT && (nc >= 0 && nc < 4) && (r + 1 < n);
+    const int row0 = blockIdx.y * TR;
+
+    // 2. fixRow: the normalised pivot row slice (IEEE division), identity entry -> 1/piv
+    Vec4<T> prn = {T(0), T(0), T(0), T(0)};
+    if (active) {
+        const Vec4<T> pr = *reinterpret_cast<const Vec4<T> *>(src + (size_t)p * ld + j4);
+        prn.x = pr.x / piv;
+        prn.y = pr.y / piv;
+        prn.z = pr.z / piv;
+        prn.w = pr.w / piv;
+        if (has_r) set_comp<T>(prn, rc, T(1) / piv);
+    }
+
+    // 3. pivotElements + fixColumn over this workgroup's rows
+    PivotRec<T> best = PivotRec<T>::none();
+#pragma unroll
+    for (int u0 = 0; u0 < TR; u0 += 4) {
+        T f[4];
+        Vec4<T> v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = row0 + u0 + u;
+            const int s = (i == p) ? r : i;  // slot p receives the old row r
+            const bool ok = (i < n);
+            f[u] = ok ? src[(size_t)s * ld + r] : T(0);
+            // the other arm is a value: selecting between the row and a named zero object would select between two
+            // ADDRESSES and keep that object in scratch memory
+            v[u] = (ok && active) ? *reinterpret_cast<const Vec4<T> *>(src + (size_t)s * ld + j4)
+                                  : Vec4<T>{T(0), T(0), T(0), T(0)};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = row0 + u0 + u;
+            if (i >= n || !active) continue;
+            Vec4<T> o;
+            if (i == r) {
+                o = prn;
+            } else {
+                o = v[u];
+                if (has_r) set_comp<T>(o, rc, T(0));  // the implicit identity column's entry in this row
+                if (f[u] != T(0)) o = fma4_neg<T>(f[u], prn, o);
+            }
+            *reinterpret_cast<Vec4<T> *>(dst + (size_t)i * ld + j4) = o;
+            if (has_next && i > r) {
+                const PivotRec<T> kk = PivotRec<T>::make(comp<T>(o, nc), i);
+                best = decltype(best)::best_of(kk, best);
+            }
+        }
+    }
+    // 4. maxPivot record of column r+1 for the next launch
+    if (has_next && active) keys_out[(size_t)b * npart + blockIdx.y] = best;
+
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+        if (p != r) {
+            int *og = orig + (size_t)b * n;
+            const int t = og[r];
+            og[r] = og[p];
+            og[p] = t;
+        }
+        if (status && pivot_unusable(piv)) status[b] = MI32_SINGULAR;
+        if constexpr (DET) {  // this thread owns the parity word and the launches are ordered
+            det_piv[(size_t)b * det_pstride + r] = piv;
+            if (p != r) det_parity[b] ^= 1;
+        }
+    }
+}
+
 template <typename T, int TR, bool PIVOT>
 __global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_kernel(const T *__restrict__ src_all,
                                                                        T *__restrict__ dst_all, int n, int ld,
@@ -159,19 +238,18 @@ __global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_kernel(const T *_
                                                                        int npart, int *__restrict__ orig,
                                                                        int *__restrict__ status)
 {
-#include "mi32_sweep_step_body.h"
+    sweep_step<T, TR, PIVOT, false>(src_all, dst_all, n, ld, wstride, r, keys_in, keys_out, npart, orig, status, nullptr,
+                                    0, nullptr);
 }
-// The det twin (mi32_inv_det_any_device*): the same step, and the pivot of step r to det_piv[b * det_pstride + r], an
-// exchange counted in det_parity[b].  sweep_run launches it only for a det call.
+// The det twin (mi32_inv_det_any_device*): sweep_run launches it only for a det call.
 template <typename T, int TR, bool PIVOT>
 __global__ __launch_bounds__(kSweepThreads) void gj_sweep_step_det_kernel(
     const T *__restrict__ src_all, T *__restrict__ dst_all, int n, int ld, size_t wstride, int r,
     const PivotRec<T> *__restrict__ keys_in, PivotRec<T> *__restrict__ keys_out, int npart, int *__restrict__ orig,
     int *__restrict__ status, T *__restrict__ det_piv, size_t det_pstride, int *__restrict__ det_parity)
 {
-#define MI32_STEP_DET
-#include "mi32_sweep_step_body.h"
-#undef MI32_STEP_DET
+    sweep_step<T, TR, PIVOT, true>(src_all, dst_all, n, ld, wstride, r, keys_in, keys_out, npart, orig, status, det_piv,
+                                   det_pstride, det_parity);
 }
 
 // ---- getInvertedMatrix counterpart (mat_inv_32.cpp:195-203), shared by the three paths -------------

@@ -745,6 +745,44 @@ def test_sweep_2048_bit_identical_to_oracle(oracle, inv_sweep):
     assert st[0] == 0 and np.array_equal(got.reshape(-1), want)
 
 
+def _assert_runs_the_sweep_at(inv, n, tr):
+    """The call of order n on `inv` resolves to the sweep, and the sweep's plan gives a workgroup `tr` rows: the
+    workspace ([W0][W1][keys0][keys1][orig][invp], each region a multiple of 256 bytes, one 16-byte arg-max record slot
+    per row tile) has ceil(n / tr) record slots -- and would have twice as many at tr / 2."""
+    def ws(rows):
+        a256 = lambda x: (x + 255) & ~255
+        return 2 * a256(n * ((n + 3) & ~3) * 4) + 2 * a256(-(-n // rows) * 16) + 2 * a256(n * 4)
+
+    assert inv.resolved_algo(n, 1) == g.ALGO_SWEEP
+    got = _lib.load().mi32_workspace_bytes(n, 1, g.ALGO_SWEEP)
+    assert got == ws(tr) != ws(tr // 2), (n, tr, got, ws(tr), ws(tr // 2))
+
+
+def test_sweep_2731_eight_rows_per_workgroup_bit_identical_to_oracle(oracle, inv_sweep):
+    """The smallest order at which the sweep gives a workgroup 8 rows (4 up to 2730)."""
+    n = 2731
+    _assert_runs_the_sweep_at(inv_sweep, n - 1, 4)
+    _assert_runs_the_sweep_at(inv_sweep, n, 8)
+    a = gate_matrix(n, 20_001)
+    got, st = run(inv_sweep, a)
+    want = oracle_inverse(oracle, a, n)
+    assert st[0] == 0 and np.array_equal(got.reshape(-1), want)
+
+
+def test_sweep_5462_thirty_two_rows_per_workgroup_equals_the_blocked_route(inv_sweep, inv_blocked):
+    """The smallest order at which the sweep gives a workgroup 32 rows (16 up to 5461), against the blocked route's
+    result for the same input, which is pinned to the oracle up to the sign of a zero."""
+    n = 5462
+    _assert_runs_the_sweep_at(inv_sweep, n - 1, 16)
+    _assert_runs_the_sweep_at(inv_sweep, n, 32)
+    assert inv_blocked.resolved_algo(n, 1) == g.ALGO_BLOCKED
+    a = gate_matrix(n, 20_002)
+    got, st = run(inv_sweep, a)
+    want, st_blocked = run(inv_blocked, a)
+    assert st[0] == 0 and st_blocked[0] == 0
+    assert canonical_bytes(got) == canonical_bytes(want)
+
+
 def test_c2_real_shape_64_x_2048(oracle):
     """BASELINE configs[2] at its real shape: 64 x 2048^2 on one GPU, default plan -> outer block width 128 and the
     two-stream batch split (32 + 32).  Residual gate on all 64, the exact size-independent properties on the whole

@@ -413,7 +413,8 @@ template <typename T>
 hipError_t workgroup_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *prof, bool pivoting);
 
 // ---- A X = B for a variable-size batch (mi32_solve_device_vbatched*) -------------------------------------------------
-// The solve kernels' variable-size twins (gj_resident_solve_vkernel / gj_workgroup_solve_vkernel): a launch takes the
+// The solve kernels' variable-size twins (gj_resident_solve_vkernel / gj_workgroup_solve_vkernel; each pair shares its
+// member body, resident_solve_member of mi32_resident.hip and slab_member of mi32_slab.h): a launch takes the
 // `count` members from `first` on of the plan's sorted list, which all run the columns col0 ... col0 + cols - 1 of their
 // B on one kernel instance (lanes per member by the width n + cols, or rows per thread by the order), and looks up the
 // member's order, pointers and leading dimensions by the member index.  Everything here is device memory.

@@ -30,8 +30,11 @@
 // instances), so there r is a run-time, wave-uniform value that is only ever compared with the compile-time row
 // index or used as a lane index.
 //
-// gj_resident_vkernel is the same body for a variable-size batch (mi32_inv_device_vbatched): every group looks up its
-// member's order, pointers and leading dimensions, and the groups of a wave may differ in order.
+// Every kernel of the file is made of one load (resident_load), one step loop (resident_steps) and one store
+// (resident_store): the inverse and determinant kernels through resident_member, the A X = B kernels through
+// resident_solve_member.  The variable-size kernels (mi32_inv_device_vbatched, mi32_solve_device_vbatched) are the same
+// bodies: every group looks up its member's order, pointers and leading dimensions (resident_vgroup), and the groups of
+// a wave may differ in order.
 #include <type_traits>
 
 #include "mi32_internal.h"
@@ -135,39 +138,34 @@ __device__ __forceinline__ void resident_step(T (&a)[L], const int r, const int 
     }
 }
 
-// One member from the load to the un-permuted inverse, shared by the uniform and the variable-size kernel.  `in` /
-// `out`: the member's first element, rows lda / ldo elements apart; n: this GROUP's order (the same in its L lanes,
-// 0 for a group that owns no member: it neither loads nor stores); nmax: the largest order in the wave, wave-uniform.
-// With UNIFORM_N every group of the wave has the order nmax (or none: the steps then run on zeros) and the step loop
-// is the uniform kernel's; without, a group sits out the steps past its own order -- a step on a finished group would
-// flag it and destroy its result -- and every cross-lane operation of resident_step stays inside its group of L
-// lanes, all of them in or all of them out.  Every element is in registers before the first store.  DET: the group's
-// first lane also stores the member's determinant to *det_mant / *det_exp, and a null `out` skips the inverse's stores.
-template <typename T, int L, bool PIVOT, bool UNIFORM_N, bool DET>
-__device__ __forceinline__ void resident_member(const T *in, T *out, const int n, const int nmax, const int lda,
-                                                const int ldo, const int j, const bool mine, int *status_word,
-                                                double *det_mant = nullptr, int *det_exp = nullptr)
+// The three pieces every kernel of this file is made of.  n: this GROUP's order (the same in its L lanes, 0 for a group
+// that owns no member); nmax: the largest order in the wave, wave-uniform.
+//
+// The load: this lane's column, `col` its first element, rows ld elements apart.  A lane that is not `mine` (past the
+// member's width, or in a group without a member) holds zeros and reads nothing.  Boundary rule: a NaN / inf anywhere
+// in the input is an invalid member (`bad`).
+template <typename T, int L>
+__device__ __forceinline__ void resident_load(T (&a)[L], const T *col, const int ld, const int n, const bool mine, bool &bad)
 {
-    T a[L];
-    bool bad = false;  // boundary rule: a NaN / inf anywhere in the input is an invalid matrix
 #pragma unroll
     for (int i = 0; i < L; ++i) {
         if (i < n) {
-            a[i] = mine ? in[(size_t)i * lda + j] : T(0);
+            a[i] = mine ? col[(size_t)i * ld] : T(0);
             bad = bad || (a[i] - a[i] != T(0));
         } else {
             a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
         }
     }
-    int orig = j;
-    DetAcc det = det_start(false);
-    if constexpr (DET) {
-        // a non-finite input entry, seen by the lane of its column alone: the group's accumulation never starts
-        const unsigned long long flagged = __builtin_amdgcn_ballot_w64(bad);
-        const int g0 = (int)(__lane_id() & ~(unsigned)(L - 1));  // the group's first lane in the wave
-        const unsigned long long group = L == 64 ? ~0ull : ((1ull << (L & 63)) - 1ull) << g0;
-        det = det_start((flagged & group) != 0ull);
-    }
+}
+
+// The step loop.  With UNIFORM_N every group of the wave has the order nmax (or none: the steps then run on zeros);
+// without, a group sits out the steps past its own order -- a step on a finished group would flag it and destroy its
+// result, and in a solve lane n of a finished group holds a column of B and would become a pivot column -- and every
+// cross-lane operation of resident_step stays inside its group of L lanes, all of them in or all of them out.
+template <typename T, int L, bool PIVOT, bool UNIFORM_N, bool DET>
+__device__ __forceinline__ void resident_steps(T (&a)[L], const int n, const int nmax, const int j, int &orig, bool &bad,
+                                               DetAcc &det)
+{
     if constexpr (L <= 16) {
 #pragma unroll
         for (int r = 0; r < L; ++r) {
@@ -186,6 +184,39 @@ __device__ __forceinline__ void resident_member(const T *in, T *out, const int n
             else if (r < n) resident_step<T, L, PIVOT, DET>(a, r, j, orig, bad, det);
         }
     }
+}
+
+// The store of this lane's rows < n to the column whose first element is `col`, rows ld elements apart.
+template <typename T, int L>
+__device__ __forceinline__ void resident_store(const T (&a)[L], T *col, const int ld, const int n)
+{
+#pragma unroll
+    for (int i = 0; i < L; ++i)
+        if (i < n) col[(size_t)i * ld] = a[i];
+}
+
+// One member from the load to the un-permuted inverse, shared by the uniform and the variable-size kernel.  `col`: this
+// lane's column of the member, rows lda elements apart; `out`: the inverse's first element, rows ldo apart.  A group
+// that owns no member neither loads nor stores.  Every element is in registers before the first store.  DET: the group's
+// first lane also stores the member's determinant to *det_mant / *det_exp, and a null `out` skips the inverse's stores.
+template <typename T, int L, bool PIVOT, bool UNIFORM_N, bool DET>
+__device__ __forceinline__ void resident_member(const T *col, T *out, const int n, const int nmax, const int lda,
+                                                const int ldo, const int j, const bool mine, int *status_word,
+                                                double *det_mant = nullptr, int *det_exp = nullptr)
+{
+    T a[L];
+    bool bad = false;
+    resident_load<T, L>(a, col, lda, n, mine, bad);
+    int orig = j;
+    DetAcc det = det_start(false);
+    if constexpr (DET) {
+        // a non-finite input entry, seen by the lane of its column alone: the group's accumulation never starts
+        const unsigned long long flagged = __builtin_amdgcn_ballot_w64(bad);
+        const int g0 = (int)(__lane_id() & ~(unsigned)(L - 1));  // the group's first lane in the wave
+        const unsigned long long group = L == 64 ? ~0ull : ((1ull << (L & 63)) - 1ull) << g0;
+        det = det_start((flagged & group) != 0ull);
+    }
+    resident_steps<T, L, PIVOT, UNIFORM_N, DET>(a, n, nmax, j, orig, bad, det);
     if (!mine) return;
     if constexpr (DET) {
         if (j == 0) {
@@ -195,11 +226,7 @@ __device__ __forceinline__ void resident_member(const T *in, T *out, const int n
     }
     bool store = true;
     if constexpr (DET) store = out != nullptr;  // determinant only: status and determinant are all that is written
-    if (store) {
-#pragma unroll
-        for (int i = 0; i < L; ++i)
-            if (i < n) out[(size_t)i * ldo + orig] = a[i];
-    }
+    if (store) resident_store<T, L>(a, out + orig, ldo, n);  // the store applies the column permutation
     // the status word was zeroed (MI32_OK) by the host before this launch; every writer stores the same value
     if (bad) *status_word = MI32_SINGULAR;
 }
@@ -219,10 +246,10 @@ __device__ __forceinline__ void resident_umember(const T *in, T *out, const int 
     const size_t mat = mine ? (size_t)b * (size_t)n * (size_t)n : 0;
     if constexpr (DET) {
         const size_t w = mine ? (size_t)b : 0;
-        resident_member<T, L, PIVOT, true, true>(in + mat, out ? out + mat : nullptr, n, n, n, n, j, mine, status + w,
+        resident_member<T, L, PIVOT, true, true>(in + mat + j, out ? out + mat : nullptr, n, n, n, n, j, mine, status + w,
                                                  det_mant + w, det_exp + w);
     } else {
-        resident_member<T, L, PIVOT, true, false>(in + mat, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
+        resident_member<T, L, PIVOT, true, false>(in + mat + j, out + mat, n, n, n, n, j, mine, status + (mine ? b : 0));
     }
 }
 
@@ -243,21 +270,28 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_det_kernel(const
     resident_umember<T, L, PIVOT, true>(in, out, n, batch, status, det_mant, det_exp);
 }
 
-// The variable-size kernel: group g of the launch takes member members[first + g] of the plan's sorted list and reads
-// that member's order, pointers and leading dimensions (a null lda / ldinv: the order).  The list is sorted by order,
-// so the groups of a wave almost always share one; where they do not the wave loops to its largest.  For L = 64 the
-// group is the wave.  The member pointers carry no __restrict__: a member may be inverted in place.
-template <typename T, int L, bool PIVOT, bool DET>
-__device__ __forceinline__ void resident_vmember(const VbatchArgs<T> &v, const int first, const int count, double *det_mant,
-                                                 int *det_exp)
+// A group's member in a variable-size launch: group g takes member members[first + g] of the plan's sorted list.  The
+// list is sorted by order, so the groups of a wave almost always share one; where they do not the wave loops to its
+// largest (nmax).  A group past the end of the range has no member (valid false, m = n = 0).  For L = 64 the group is
+// the wave and the group index, the member index and the order are scalar values, hence so is everything a kernel
+// looks up by them (pointers, leading dimensions).
+struct ResidentGroup {
+    bool valid;
+    int m, n, nmax;
+};
+template <int L>
+__device__ __forceinline__ ResidentGroup resident_vgroup(const int *orders, const int *members, const int first,
+                                                         const int count)
 {
-    constexpr int kGroups = kResidentThreads / L;
-    const int j = threadIdx.x & (L - 1);
-    const long long g = (long long)blockIdx.x * kGroups + threadIdx.x / L;
+    constexpr int kGroups = kResidentThreads / L;  // members per workgroup
+    int grp = threadIdx.x / L;
+    if constexpr (L == 64) grp = __builtin_amdgcn_readfirstlane(grp);  // the group is the wave
+    const long long g = (long long)blockIdx.x * kGroups + grp;
     const bool valid = g < (long long)count;
-    const int m = valid ? v.members[(size_t)first + (size_t)g] : 0;
-    int n = valid ? v.orders[m] : 0;
-    if constexpr (L == 64) n = __builtin_amdgcn_readfirstlane(n);  // the group is the wave
+    int m = valid ? members[(size_t)first + (size_t)g] : 0;
+    if constexpr (L == 64) m = __builtin_amdgcn_readfirstlane(m);
+    int n = valid ? orders[m] : 0;
+    if constexpr (L == 64) n = __builtin_amdgcn_readfirstlane(n);
     int nmax = n;
     if constexpr (L < 64) {
 #pragma unroll
@@ -267,20 +301,33 @@ __device__ __forceinline__ void resident_vmember(const VbatchArgs<T> &v, const i
         }
         nmax = __builtin_amdgcn_readfirstlane(nmax);
     }
-    const bool mine = valid && j < n;
-    const T *in = nullptr;
+    return {valid, m, n, nmax};
+}
+
+// The variable-size kernel pair's body: the group reads its member's pointers and leading dimensions (a null lda /
+// ldinv: the order).  The member pointers carry no __restrict__: a member may be inverted in place.  The guarded step
+// loop also at L = 64, where n is nmax: the uniform loop costs these instances up to 60 registers.
+template <typename T, int L, bool PIVOT, bool DET>
+__device__ __forceinline__ void resident_vmember(const VbatchArgs<T> &v, const int first, const int count, double *det_mant,
+                                                 int *det_exp)
+{
+    const int j = threadIdx.x & (L - 1);
+    const ResidentGroup grp = resident_vgroup<L>(v.orders, v.members, first, count);
+    const int m = grp.m, n = grp.n;
+    const bool mine = grp.valid && j < n;
+    const T *col = nullptr;
     T *out = nullptr;
     int lda = n, ldo = n;
     if (mine) {
-        in = v.a[m];
+        col = v.a[m] + j;
         if (!DET || v.inv) out = v.inv[m];
         if (v.lda) lda = v.lda[m];
         if (v.ldinv) ldo = v.ldinv[m];
     }
     // the determinant lands at the caller's member index, like the status word
-    if constexpr (DET) resident_member<T, L, PIVOT, false, true>(in, out, n, nmax, lda, ldo, j, mine, v.status + m,
+    if constexpr (DET) resident_member<T, L, PIVOT, false, true>(col, out, n, grp.nmax, lda, ldo, j, mine, v.status + m,
                                                                  det_mant + m, det_exp + m);
-    else resident_member<T, L, PIVOT, false, false>(in, out, n, nmax, lda, ldo, j, mine, v.status + m);
+    else resident_member<T, L, PIVOT, false, false>(col, out, n, grp.nmax, lda, ldo, j, mine, v.status + m);
 }
 
 template <typename T, int L, bool PIVOT>
@@ -302,7 +349,36 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_det_vkernel(cons
 // cols - 1 the columns col0 ... of the member's B, and the steps are resident_step's, unchanged: a lane >= n is never
 // column r, so it takes the row exchange, prn = b[p] / piv, the update by column r's multipliers and b[r] = prn.  The
 // rows are exchanged physically, so register row i of such a lane is row i of X; the lanes < n store nothing and the
-// column bookkeeping (`orig`) is dead.  B and X carry no __restrict__: X may be B (a lane stores the column it loaded).
+// column bookkeeping (`orig`) is dead.  `col`: this lane's column of A or B, rows ld elements apart; rhs: the lane holds
+// a column of B.  x_of() gives the lane's column of X and its leading dimension; it is called after the step loop, so
+// that what it reads is not held in registers across the steps.  A boundary rule as above: a NaN / inf anywhere in A
+// or B is an invalid member.  The uniform and the variable-size kernel share this body.
+template <typename T>
+struct ResidentColumn {
+    T *first;  // the column's first element
+    int ld;    // its rows are ld elements apart
+};
+template <typename T, int L, bool PIVOT, bool UNIFORM_N, typename XOf>
+__device__ __forceinline__ void resident_solve_member(const T *col, const int ld, const int n, const int nmax, const int j,
+                                                      const bool mine, const bool rhs, int *status_word, XOf x_of)
+{
+    T a[L];
+    bool bad = false;
+    resident_load<T, L>(a, col, ld, n, mine, bad);
+    int orig = j;
+    DetAcc det = det_start(false);
+    resident_steps<T, L, PIVOT, UNIFORM_N, false>(a, n, nmax, j, orig, bad, det);
+    if (!mine) return;
+    if (rhs) {
+        const ResidentColumn<T> x = x_of();
+        resident_store<T, L>(a, x.first, x.ld, n);
+    }
+    // the status word was zeroed (MI32_OK) by the host before the call's first launch; every writer stores the same value
+    if (bad) *status_word = MI32_SINGULAR;
+}
+
+// The uniform solve kernel: group m of the launch takes member m of the batch.  B and X carry no __restrict__: X may
+// be B (a lane stores the column it loaded).
 template <typename T, int L, bool PIVOT>
 __global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_kernel(const SolveArgs<T> s)
 {
@@ -315,123 +391,54 @@ __global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_kernel(con
     const bool rhs = j >= n;
     const size_t member = mine ? (size_t)m : 0;
     const size_t rhs_at = member * (size_t)n * (size_t)s.nrhs + (size_t)(s.col0 + (rhs ? j - n : 0));
-    const T *in = rhs ? s.b + rhs_at : s.a + (member * (size_t)n * (size_t)n + (size_t)j);
-    const int ld = rhs ? s.nrhs : n;
-    T a[L];
-    bool bad = false;  // boundary rule: a NaN / inf anywhere in A or B is an invalid member
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        if (i < n) {
-            a[i] = mine ? in[(size_t)i * ld] : T(0);
-            bad = bad || (a[i] - a[i] != T(0));
-        } else {
-            a[i] = not_a_candidate(T(0));
-        }
-    }
-    int orig = j;
-    DetAcc det = det_start(false);
-    if constexpr (L <= 16) {
-#pragma unroll
-        for (int r = 0; r < L; ++r)
-            if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);  // n is wave-uniform: a scalar branch
-    } else {
-#pragma unroll 1
-        for (int r = 0; r < n; ++r) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
-    }
-    if (!mine) return;
-    if (rhs) {
-        T *out = s.x + rhs_at;
-#pragma unroll
-        for (int i = 0; i < L; ++i)
-            if (i < n) out[(size_t)i * s.nrhs] = a[i];
-    }
-    if (bad) s.status[member] = MI32_SINGULAR;
+    const T *col = rhs ? s.b + rhs_at : s.a + (member * (size_t)n * (size_t)n + (size_t)j);
+    resident_solve_member<T, L, PIVOT, true>(col, rhs ? s.nrhs : n, n, n, j, mine, rhs, s.status + member,
+                                             [&] { return ResidentColumn<T>{s.x + rhs_at, s.nrhs}; });
 }
 
 // A X = B for a variable-size batch: group g of the launch takes member members[first + g] of the plan's sorted list
 // and the columns col0 ... col0 + cols - 1 of its B; every member of the launch has a width n + cols of this lane class.
-// A sibling of gj_resident_solve_kernel, not a rewrite of it (sharing the step loop moved the registers of the uniform
-// instances).  The groups of a wave may differ in order, so B sits in a different lane in each, and a group sits out
-// the steps past its own order: here that guard carries the result, because lane n of a finished group holds a column
-// of B and would otherwise become a pivot column.  For L = 64 the group is the wave and the member index, the order,
-// the pointers and the leading dimensions are scalar values.  No pointer carries __restrict__: X may be B.
+// The groups of a wave may differ in order, so B sits in a different lane in each, and a group sits out the steps past
+// its own order: here that guard of resident_steps carries the result.  For L = 64 the group is the wave, n is nmax
+// and the step loop is the uniform one: the guard, never false there, is not left for the compiler to fold, because
+// whether it folds it decides the schedule of the step (unfolded: 3 % slower here).  X's pointer
+// and leading dimension are looked up after the steps.  No pointer carries __restrict__: X may be B.
 template <typename T, int L, bool PIVOT>
 __global__ __launch_bounds__(kResidentThreads) void gj_resident_solve_vkernel(const VsolveArgs<T> v, const int first,
                                                                               const int count)
 {
-    constexpr int kGroups = kResidentThreads / L;  // members per workgroup
     const int j = threadIdx.x & (L - 1);
-    int grp = threadIdx.x / L;
-    if constexpr (L == 64) grp = __builtin_amdgcn_readfirstlane(grp);  // the group is the wave
-    const long long g = (long long)blockIdx.x * kGroups + grp;
-    const bool valid = g < (long long)count;
-    int m = valid ? v.members[(size_t)first + (size_t)g] : 0;
-    if constexpr (L == 64) m = __builtin_amdgcn_readfirstlane(m);
-    int n = valid ? v.orders[m] : 0;
-    if constexpr (L == 64) n = __builtin_amdgcn_readfirstlane(n);
-    int nmax = n;  // the largest order in the wave
-    if constexpr (L < 64) {
-#pragma unroll
-        for (int off = L; off < 64; off <<= 1) {
-            const int o = __shfl_xor(nmax, off, 64);
-            nmax = o > nmax ? o : nmax;
-        }
-        nmax = __builtin_amdgcn_readfirstlane(nmax);
-    }
+    const ResidentGroup grp = resident_vgroup<L>(v.orders, v.members, first, count);
+    const int m = grp.m, n = grp.n;
     // a group past the end of the range, and a lane past the member's width, hold zeros and neither load nor store
-    const bool mine = valid && j < n + v.cols;
+    const bool mine = grp.valid && j < n + v.cols;
     const bool rhs = j >= n;
-    const int col = v.col0 + (rhs ? j - n : 0);  // this lane's column of B and X
-    const T *in = nullptr;
+    const int xcol = v.col0 + (rhs ? j - n : 0);  // this lane's column of B and X
+    const T *col = nullptr;
     int ld = 0;
     if (mine) {
         const int lda = v.lda ? v.lda[m] : n;
         const int ldb = v.ldb ? v.ldb[m] : v.nrhs;
-        in = rhs ? v.b[m] + col : v.a[m] + j;
+        col = rhs ? v.b[m] + xcol : v.a[m] + j;
         ld = rhs ? ldb : lda;
     }
-    T a[L];
-    bool bad = false;  // boundary rule: a NaN / inf anywhere in A or B is an invalid member
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        if (i < n) {
-            a[i] = mine ? in[(size_t)i * ld] : T(0);
-            bad = bad || (a[i] - a[i] != T(0));
-        } else {
-            a[i] = not_a_candidate(T(0));  // a padded row stays NaN in every column and never wins a pivot search
-        }
-    }
-    int orig = j;
-    DetAcc det = det_start(false);
-    if constexpr (L <= 16) {
-#pragma unroll
-        for (int r = 0; r < L; ++r) {
-            if (r < nmax) {  // wave-uniform: no wave walks through the steps none of its groups takes
-                if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
-            }
-        }
-    } else {
-#pragma unroll 1
-        for (int r = 0; r < nmax; ++r)
-            if (r < n) resident_step<T, L, PIVOT, false>(a, r, j, orig, bad, det);
-    }
-    if (!mine) return;
-    if (rhs) {
-        T *out = v.x[m] + col;
-        const int ldx = v.ldx ? v.ldx[m] : v.nrhs;
-#pragma unroll
-        for (int i = 0; i < L; ++i)
-            if (i < n) out[(size_t)i * ldx] = a[i];
-    }
-    // the status word was zeroed (MI32_OK) by the host before the call's first launch; every writer stores the same value
-    if (bad) v.status[m] = MI32_SINGULAR;
+    resident_solve_member<T, L, PIVOT, L == 64>(col, ld, n, grp.nmax, j, mine, rhs, v.status + m, [&] {
+        return ResidentColumn<T>{v.x[m] + xcol, v.ldx ? v.ldx[m] : v.nrhs};
+    });
 }
 
-// the instances by their lanes per matrix (pick_instance of mi32_internal.h)
+// The one launch helper: picks the instance by its lanes per matrix (pick_instance of mi32_internal.h) and hands
+// `launch` L and PIVOT as compile-time constants and the grid for `groups` groups of L lanes (a 64-bit count: no batch
+// index in blockIdx.y / .z).  hipErrorInvalidValue when `lanes` names no instance.
 template <typename F>
-static bool resident_instance(int lanes, bool pivoting, F f)
+static hipError_t resident_launch(int lanes, bool pivoting, int groups, hipStream_t stream, Profiler *prof, F launch)
 {
-    return pick_instance<8, 16, 32, 64>(lanes, pivoting, f);
+    ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
+    const bool found = pick_instance<8, 16, 32, 64>(lanes, pivoting, [&](auto l, auto pivot) {
+        constexpr int kGroups = kResidentThreads / decltype(l)::value;
+        launch(l, pivot, dim3((unsigned)(((long long)groups + kGroups - 1) / kGroups)), dim3(kResidentThreads));
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 template <typename T>
@@ -440,20 +447,15 @@ hipError_t resident_invert(const T *d_a, T *d_inv, int n, int batch, int *d_stat
 {
     const int lanes = resident_lanes(n);
     if (lanes == 0 || batch <= 0 || !d_status || !det.valid() || (!d_inv && det.empty())) return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_PANEL, stream);  // pivot steps on a register-resident panel: the whole matrix
-    resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+    return resident_launch(lanes, pivoting, batch, stream, prof, [&](auto l, auto pivot, dim3 grid, dim3 block) {
         constexpr int L = decltype(l)::value;
         constexpr bool PIVOT = decltype(pivot)::value;
-        constexpr int kGroups = kResidentThreads / L;
-        const dim3 grid((unsigned)(((long long)batch + kGroups - 1) / kGroups));
         if (det.empty())
-            hipLaunchKernelGGL((gj_resident_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv, n,
-                               batch, d_status);
+            hipLaunchKernelGGL((gj_resident_kernel<T, L, PIVOT>), grid, block, 0, stream, d_a, d_inv, n, batch, d_status);
         else
-            hipLaunchKernelGGL((gj_resident_det_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, d_a, d_inv,
-                               n, batch, d_status, det.mant, det.exp);
+            hipLaunchKernelGGL((gj_resident_det_kernel<T, L, PIVOT>), grid, block, 0, stream, d_a, d_inv, n, batch, d_status,
+                               det.mant, det.exp);
     });
-    return hipGetLastError();
 }
 template hipError_t resident_invert(const float *, float *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
 template hipError_t resident_invert(const double *, double *, int, int, int *, DetOut, hipStream_t, Profiler *, bool);
@@ -464,19 +466,12 @@ hipError_t resident_vinvert(int lanes, const VbatchArgs<T> &v, const DetOut det,
 {
     if (count <= 0 || first < 0 || !v.status || !det.valid() || (!v.inv && det.empty())) return hipErrorInvalidValue;
     const VbatchDetArgs<T> vd{v, det.mant, det.exp};
-    ProfScope ps(prof, KC_PANEL, stream);
-    const bool found = resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
+    return resident_launch(lanes, pivoting, count, stream, prof, [&](auto l, auto pivot, dim3 grid, dim3 block) {
         constexpr int L = decltype(l)::value;
         constexpr bool PIVOT = decltype(pivot)::value;
-        constexpr int kGroups = kResidentThreads / L;
-        const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
-        if (det.empty())
-            hipLaunchKernelGGL((gj_resident_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, v, first, count);
-        else
-            hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, vd, first,
-                               count);
+        if (det.empty()) hipLaunchKernelGGL((gj_resident_vkernel<T, L, PIVOT>), grid, block, 0, stream, v, first, count);
+        else hipLaunchKernelGGL((gj_resident_det_vkernel<T, L, PIVOT>), grid, block, 0, stream, vd, first, count);
     });
-    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 template hipError_t resident_vinvert(int, const VbatchArgs<float> &, DetOut, int, int, hipStream_t, Profiler *, bool);
 template hipError_t resident_vinvert(int, const VbatchArgs<double> &, DetOut, int, int, hipStream_t, Profiler *, bool);
@@ -487,15 +482,10 @@ hipError_t resident_solve(const SolveArgs<T> &s, hipStream_t stream, Profiler *p
     const int lanes = s.n >= 1 && s.cols >= 1 ? resident_lanes(s.n + s.cols) : 0;
     if (lanes == 0 || s.batch <= 0 || s.col0 < 0 || s.col0 + s.cols > s.nrhs || !s.a || !s.b || !s.x || !s.status)
         return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_PANEL, stream);
-    resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
-        constexpr int L = decltype(l)::value;
-        constexpr bool PIVOT = decltype(pivot)::value;
-        constexpr int kGroups = kResidentThreads / L;
-        const dim3 grid((unsigned)(((long long)s.batch + kGroups - 1) / kGroups));
-        hipLaunchKernelGGL((gj_resident_solve_kernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, s);
+    return resident_launch(lanes, pivoting, s.batch, stream, prof, [&](auto l, auto pivot, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((gj_resident_solve_kernel<T, decltype(l)::value, decltype(pivot)::value>), grid, block, 0, stream,
+                           s);
     });
-    return hipGetLastError();
 }
 template hipError_t resident_solve(const SolveArgs<float> &, hipStream_t, Profiler *, bool);
 template hipError_t resident_solve(const SolveArgs<double> &, hipStream_t, Profiler *, bool);
@@ -507,16 +497,10 @@ hipError_t resident_vsolve(int lanes, const VsolveArgs<T> &v, int first, int cou
     if (count <= 0 || first < 0 || v.cols < 1 || v.cols >= lanes || v.col0 < 0 || v.col0 + v.cols > v.nrhs || !v.orders ||
         !v.members || !v.a || !v.b || !v.x || !v.status)
         return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_PANEL, stream);
-    const bool found = resident_instance(lanes, pivoting, [&](auto l, auto pivot) {
-        constexpr int L = decltype(l)::value;
-        constexpr bool PIVOT = decltype(pivot)::value;
-        constexpr int kGroups = kResidentThreads / L;
-        const dim3 grid((unsigned)(((long long)count + kGroups - 1) / kGroups));
-        hipLaunchKernelGGL((gj_resident_solve_vkernel<T, L, PIVOT>), grid, dim3(kResidentThreads), 0, stream, v, first,
-                           count);
+    return resident_launch(lanes, pivoting, count, stream, prof, [&](auto l, auto pivot, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((gj_resident_solve_vkernel<T, decltype(l)::value, decltype(pivot)::value>), grid, block, 0, stream,
+                           v, first, count);
     });
-    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 template hipError_t resident_vsolve(int, const VsolveArgs<float> &, int, int, hipStream_t, Profiler *, bool);
 template hipError_t resident_vsolve(int, const VsolveArgs<double> &, int, int, hipStream_t, Profiler *, bool);

@@ -202,6 +202,80 @@ def test_asynchronous_pure_and_deterministic(inv_res):
     assert rc == 0 and torch.equal(out64, w64)
 
 
+ONE_BODY_ORDERS = (3, 4, 8, 13, 16, 20, 32)
+ONE_BODY_BATCH = 37   # a multiple of no groups-per-workgroup count (4 ... 32): the last workgroup holds empty groups
+
+
+@pytest.mark.parametrize("pivoting", [True, False], ids=["pivot", "nopivot"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["fp32", "fp64"])
+def test_one_body_every_kernel_family_gives_the_same_bits(oracle, inv_res, inv_res_nopivot, dtype, pivoting):
+    """The kernels of mi32_resident.hip share one load, one step loop and one store: the inverse, the inverse beside
+    the determinant and A X = I must agree bit for bit, uniform and variable-size alike.  With K = n identity columns
+    the uniform solve runs at widths 6, 8, 16, 26, 32, 40 and 64: every lane class, both edges of a class, and a width
+    whose class is not the order's.  The variable-size calls take all seven orders interleaved in one plan, so groups
+    of different order share waves.  No tolerance; every status word must be 0.  The anchor against the CPU oracle
+    (order 13) keeps kernels that are all wrong alike from passing."""
+    inv = inv_res if pivoting else inv_res_nopivot
+    tdtype = torch.float32 if dtype == np.float32 else torch.float64
+    rng = np.random.default_rng(9100)
+    mats = {}
+    for n in ONE_BODY_ORDERS:
+        a = rng.uniform(-1, 1, (ONE_BODY_BATCH, n, n)) + n * np.eye(n)   # diagonally dominant: non-singular
+        if pivoting:
+            a = np.stack([m[rng.permutation(n)] for m in a])
+        mats[n] = a.astype(dtype)
+    kmax = max(ONE_BODY_ORDERS)
+    uniform = {}
+    for n in ONE_BODY_ORDERS:
+        a = torch.from_numpy(mats[n]).cuda()
+        x, st = inv.inv(a)
+        xd, std, mant, exp = inv.inv_det(a)
+        xs, sts = inv.solve(a, torch.eye(n, dtype=tdtype, device="cuda").repeat(ONE_BODY_BATCH, 1, 1))
+        assert not st.any() and not std.any() and not sts.any(), n
+        assert torch.equal(xd, x), n
+        assert torch.equal(xs, x), n
+        uniform[n] = (x.cpu(), mant.cpu(), exp.cpu())
+    # the anchor
+    fn = (oracle.matrix_inv_32 if dtype == np.float32 else oracle.matrix_inv_64) if pivoting \
+        else oracle.matrix_inversion_no_pivots
+    want, want_st = oracle_batch(fn, mats[13], 13)
+    assert not want_st.any()
+    assert_members_equal(uniform[13][0].numpy(), want, 13)
+    # one plan: [3, 32, 4, 20, 8, 16, 13] repeated, member b of order n is mats[n][b]
+    pattern = (3, 32, 4, 20, 8, 16, 13)
+    orders = np.tile(pattern, ONE_BODY_BATCH)
+    members = [mats[n][b] for b in range(ONE_BODY_BATCH) for n in pattern]
+    a_flat = torch.from_numpy(np.concatenate([m.reshape(-1) for m in members])).cuda()
+    # B: every member's identity, padded with zero columns to the widest order
+    rhs = torch.from_numpy(np.concatenate([np.eye(m.shape[0], kmax, dtype=dtype) for m in members])).cuda()
+    plan = inv.plan_ragged(orders)
+    try:
+        xr, str_ = inv.inv_ragged(plan, a_flat)
+        xrd, strd, (rmant, rexp) = inv.inv_ragged(plan, a_flat, det=True)
+        xrs, strs = inv.solve_ragged(plan, a_flat, rhs)
+        # the same B four columns wide: widths 7 ... 36, so that orders 3 / 4 and 13 / 16 / 20 share the waves of one
+        # solve launch and a finished group sits out the steps of its neighbours
+        xrn, strn = inv.solve_ragged(plan, a_flat, rhs[:, :4].contiguous())
+        torch.cuda.synchronize()
+    finally:
+        plan.close()
+    assert not str_.any() and not strd.any() and not strs.any() and not strn.any()
+    assert torch.equal(xrd, xr)
+    xr, xrs, xrn, rmant, rexp = xr.cpu(), xrs.cpu(), xrn.cpu(), rmant.cpu(), rexp.cpu()
+    at = row = 0
+    for i, n in enumerate(orders):
+        b = i // len(pattern)
+        x, mant, exp = uniform[n]
+        assert torch.equal(xr[at:at + n * n].view(n, n), x[b]), (i, n)
+        assert torch.equal(xrs[row:row + n, :n], x[b]), (i, n)
+        assert not xrs[row:row + n, n:].any(), (i, n)          # A X = 0 has the solution 0
+        k = min(n, 4)
+        assert torch.equal(xrn[row:row + n, :k], x[b][:, :k]), (i, n)
+        assert rmant[i] == mant[b] and rexp[i] == exp[b], (i, n)
+        at += n * n
+        row += n
+
+
 @pytest.mark.parametrize("n,batch", TIMED_SHAPES)
 def test_faster_than_the_path_auto_resolves_to(inv_res, n, batch):
     """Only the direction is asserted (no ratio was known before this path existed): for these three batches of

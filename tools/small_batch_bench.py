@@ -64,7 +64,7 @@ def timed(torch, inv, a, warmup, calls):
         if i >= warmup:
             ts.append((time.perf_counter() - t0) * 1e3)
     bad = int((st != 0).sum())
-    return statistics.median(ts), min(ts), out, bad
+    return statistics.median(ts), (min(ts), max(ts)), out, bad
 
 
 def leg(ms, n, batch, elem_bytes):
@@ -84,7 +84,8 @@ def measure(torch, n, batch, dtype, pivoting, with_parent, warmup, calls):
         ms, best, x_res, bad = timed(torch, res, a, warmup, calls)
     finally:
         res.close()
-    row["resident"] = dict(leg(ms, n, batch, elem), min_ms=round(best, 4), nonzero_status=bad,
+    row["resident"] = dict(leg(ms, n, batch, elem), min_ms=round(best[0], 4), max_ms=round(best[1], 4),
+                           nonzero_status=bad,
                            workspace_bytes=int(lib.mi32_workspace_bytes(n, batch, _lib.ALGO_RESIDENT)),
                            lanes_per_matrix=int(g_lanes(n, elem)))
     if not with_parent:
@@ -103,7 +104,8 @@ def measure(torch, n, batch, dtype, pivoting, with_parent, warmup, calls):
         ms_p, best_p, x_par, bad_p = timed(torch, auto, a, warmup, calls)
     finally:
         auto.close()
-    row["parent"] = dict(leg(ms_p, n, batch, elem), min_ms=round(best_p, 4), nonzero_status=bad_p,
+    row["parent"] = dict(leg(ms_p, n, batch, elem), min_ms=round(best_p[0], 4), max_ms=round(best_p[1], 4),
+                         nonzero_status=bad_p,
                          algo=ALGO_LABEL[algo], workspace_bytes=ws)
     row["speedup"] = round(ms_p / ms, 2)
     row["same_values"] = bool(torch.equal(x_res, x_par))

@@ -32,65 +32,6 @@ ALGO_NAMES = {"auto": ALGO_AUTO, "sweep": ALGO_SWEEP, "blocked": ALGO_BLOCKED, "
 VBATCH_CLASS_TOPS = (8, 16, 32, 64, 80, 96, 112, 128)
 KERNEL_CLASSES = ("init", "sweep_step", "panel", "update_in_block", "update_rank_bw", "finish", "panel_transpose")
 
-# every symbol include/mat_inv_32_c.h declares
-C_ABI_SYMBOLS = (
-    "mi32_matrix_inv_32",
-    "mi32_matrix_inv_32_batched",
-    "mi32_matrix_inv_32_batched_multi",
-    "mi32_shard_range",
-    "mi32_create",
-    "mi32_destroy",
-    "mi32_set_stream",
-    "mi32_set_algo",
-    "mi32_set_blocking",
-    "mi32_set_lookahead",
-    "mi32_workspace_bytes",
-    "mi32_reserve",
-    "mi32_inv_device",
-    "mi32_residual_device",
-    "mi32_set_profiling",
-    "mi32_get_profile",
-    "mi32_last_timing",
-    "mi32_bench_32",
-    "mi32_bench_64",
-    "mi32_matrix_multiply_64",
-    "mi32_resolve_algo",
-    "mi32_matrix_inv_64",
-    "mi32_matrix_inversion_no_pivots",
-    "mi32_set_pivoting",
-    "mi32_inv_device_f64",
-    "mi32_resolve_blocking_f64",
-    "mi32_resolve_blocking",
-    "mi32_resolve_panel_widths",
-    "mi32_resolve_route",
-    "mi32_resolve_resident",
-    "mi32_resolve_workgroup",
-    "mi32_resolve_wide",
-    "mi32_vbatch_bin",
-    "mi32_vbatch_create",
-    "mi32_vbatch_destroy",
-    "mi32_vbatch_info",
-    "mi32_inv_device_vbatched",
-    "mi32_inv_device_vbatched_f64",
-    "mi32_inv_det_device",
-    "mi32_inv_det_device_f64",
-    "mi32_inv_det_device_vbatched",
-    "mi32_inv_det_device_vbatched_f64",
-    "mi32_inv_det_any_device",
-    "mi32_inv_det_any_device_f64",
-    "mi32_solve_device",
-    "mi32_solve_device_f64",
-    "mi32_resolve_solve",
-    "mi32_solve_device_vbatched",
-    "mi32_solve_device_vbatched_f64",
-    "mi32_vbatch_solve_launches",
-    "mi32_apply_device_vbatched",
-    "mi32_apply_device_vbatched_f64",
-    "mi32_vbatch_apply_launches",
-    "mi32_dominant_kernel",
-    "mi32_last_error",
-    "mi32_version",
-)
 # the C++ drop-in of include/mat_inv_32.h (Itanium-mangled matrix_inv_32(std::vector<float>, int))
 CXX_DROPIN_SYMBOL = "_Z13matrix_inv_32St6vectorIfSaIfEEi"
 # the fp64 twin of include/mat_inv_64.h: matrix_inversion_FP64(std::vector<double>, int)
@@ -112,6 +53,63 @@ class Route(ctypes.Structure):
                 ("shared_panels", ctypes.c_int), ("lookahead", ctypes.c_int), ("parts", ctypes.c_int),
                 ("part_batch", ctypes.c_int * 2), ("part_strips_at_end", ctypes.c_int * 2),
                 ("first_fused_block", ctypes.c_int)]
+
+
+_I, _Z, _VP = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
+_IP, _FP, _DP = ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
+
+
+def _signatures(*rows):
+    """{symbol: (restype, argtypes)} from rows of ("name [name ...]", restype, argtypes): the names of one row (an
+    entry point and its twins) share the signature."""
+    return {name: (restype, argtypes) for names, restype, argtypes in rows for name in names.split()}
+
+
+# every symbol include/mat_inv_32_c.h declares, in the header's parameter order, and the two debug hooks load() binds
+SIGNATURES = _signatures(
+    ("mi32_matrix_inv_32", _I, [_FP, _Z, _I, _FP]),
+    ("mi32_matrix_inv_32_batched", _I, [_FP, _I, _I, _FP, _IP]),
+    ("mi32_matrix_inv_32_batched_multi", _I, [_FP, _I, _I, _FP, _IP, _I]),
+    ("mi32_shard_range", _I, [_I, _I, _I, _IP, _IP]),
+    ("mi32_create", _I, [ctypes.POINTER(_VP), _I]),
+    ("mi32_destroy mi32_vbatch_destroy", _I, [_VP]),
+    ("mi32_set_stream", _I, [_VP, _VP]),
+    ("mi32_set_algo mi32_set_lookahead mi32_set_profiling mi32_set_pivoting", _I, [_VP, _I]),
+    ("mi32_set_blocking mi32_reserve mi32_resolve_algo", _I, [_VP, _I, _I]),
+    ("mi32_workspace_bytes", _Z, [_I, _I, _I]),
+    ("mi32_inv_device mi32_inv_device_f64", _I, [_VP, _VP, _I, _I, _VP, _VP]),
+    ("mi32_residual_device", _I, [_VP, _VP, _VP, _I, _I, _VP]),
+    ("mi32_get_profile", _I, [_VP, _DP, ctypes.POINTER(ctypes.c_longlong), _I]),
+    ("mi32_last_timing", _I, [_DP, _DP]),
+    ("mi32_bench_32", _I, [_FP, _Z, _I, _FP, _DP]),
+    ("mi32_bench_64", _I, [_DP, _Z, _I, _DP, _DP, _I]),
+    ("mi32_matrix_multiply_64", _I, [_DP, _DP, _Z, _DP]),
+    ("mi32_matrix_inv_64 mi32_matrix_inversion_no_pivots", _I, [_DP, _Z, _I, _DP]),
+    ("mi32_resolve_blocking_f64", _I, [_VP, _I, _IP]),
+    ("mi32_resolve_blocking mi32_resolve_resident", _I, [_VP, _I, _I, _IP, _IP]),
+    ("mi32_resolve_workgroup mi32_resolve_wide", _I, [_VP, _I, _I, _IP, _IP, _IP]),
+    ("mi32_resolve_panel_widths", _I, [_VP, _I, _I, _IP, _I, _IP]),
+    ("mi32_resolve_route", _I, [_VP, _I, _I, ctypes.POINTER(Route), _IP, _I]),
+    ("mi32_vbatch_bin", _I, [_IP, _I, _IP, _IP]),
+    ("mi32_vbatch_create", _I, [_VP, _IP, _I, ctypes.POINTER(_VP)]),
+    ("mi32_vbatch_info", _I, [_VP, _IP, _IP]),
+    ("mi32_inv_device_vbatched mi32_inv_device_vbatched_f64", _I, [_VP] * 7),
+    ("mi32_inv_det_device mi32_inv_det_device_f64 mi32_inv_det_any_device mi32_inv_det_any_device_f64", _I,
+     [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    ("mi32_inv_det_device_vbatched mi32_inv_det_device_vbatched_f64", _I, [_VP] * 9),
+    ("mi32_solve_device mi32_solve_device_f64", _I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
+    ("mi32_resolve_solve", _I, [_VP, _I, _I, _I, _IP, _IP, _IP, _IP]),
+    ("mi32_solve_device_vbatched mi32_solve_device_vbatched_f64", _I, [_VP] * 6 + [_I] + [_VP] * 3),
+    ("mi32_vbatch_solve_launches", _I, [_IP, _I, _I, _IP, _I, _IP]),
+    ("mi32_apply_device_vbatched mi32_apply_device_vbatched_f64", _I, [_VP] * 6 + [_I] + [_VP] * 2),
+    ("mi32_vbatch_apply_launches", _I, [_IP, _I, _I, _I, _IP, _I, _IP]),
+    ("mi32_dominant_kernel", ctypes.c_char_p, [_I]),
+    ("mi32_last_error", ctypes.c_char_p, []),
+    ("mi32_version", _I, []),
+    ("mi32_debug_drop_panel_group", _I, [_I]),
+    ("mi32_debug_dpp_selftest", _I, [_VP, _VP, _I, _VP]),
+)
+C_ABI_SYMBOLS = tuple(name for name in SIGNATURES if not name.startswith("mi32_debug_"))
 
 
 def build_library(force: bool = False) -> str:
@@ -145,120 +143,11 @@ def load() -> ctypes.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the pure ctypes/numpy path
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    fp = ctypes.POINTER(ctypes.c_float)
-    ip = ctypes.POINTER(ctypes.c_int)
-    vp = ctypes.c_void_p
-    lib.mi32_matrix_inv_32.restype = ctypes.c_int
-    lib.mi32_matrix_inv_32.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp]
-    lib.mi32_matrix_inv_32_batched.restype = ctypes.c_int
-    lib.mi32_matrix_inv_32_batched.argtypes = [fp, ctypes.c_int, ctypes.c_int, fp, ip]
-    lib.mi32_shard_range.restype = ctypes.c_int
-    lib.mi32_shard_range.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip]
-    lib.mi32_debug_drop_panel_group.restype = ctypes.c_int
-    lib.mi32_debug_drop_panel_group.argtypes = [ctypes.c_int]
-    if hasattr(lib, "mi32_debug_dpp_selftest"):  # (tools/ab_bench.py also loads builds older than the self-test)
-        lib.mi32_debug_dpp_selftest.restype = ctypes.c_int
-        lib.mi32_debug_dpp_selftest.argtypes = [vp, vp, ctypes.c_int, vp]
-    lib.mi32_matrix_inv_32_batched_multi.restype = ctypes.c_int
-    lib.mi32_matrix_inv_32_batched_multi.argtypes = [fp, ctypes.c_int, ctypes.c_int, fp, ip, ctypes.c_int]
-    lib.mi32_create.restype = ctypes.c_int
-    lib.mi32_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-    lib.mi32_destroy.restype = ctypes.c_int
-    lib.mi32_destroy.argtypes = [vp]
-    lib.mi32_set_stream.restype = ctypes.c_int
-    lib.mi32_set_stream.argtypes = [vp, vp]
-    lib.mi32_set_algo.restype = ctypes.c_int
-    lib.mi32_set_algo.argtypes = [vp, ctypes.c_int]
-    lib.mi32_set_blocking.restype = ctypes.c_int
-    lib.mi32_set_blocking.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.mi32_set_lookahead.restype = ctypes.c_int
-    lib.mi32_set_lookahead.argtypes = [vp, ctypes.c_int]
-    lib.mi32_workspace_bytes.restype = ctypes.c_size_t
-    lib.mi32_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.mi32_reserve.restype = ctypes.c_int
-    lib.mi32_reserve.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.mi32_inv_device.restype = ctypes.c_int
-    lib.mi32_inv_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
-    lib.mi32_residual_device.restype = ctypes.c_int
-    lib.mi32_residual_device.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]
-    lib.mi32_set_profiling.restype = ctypes.c_int
-    lib.mi32_set_profiling.argtypes = [vp, ctypes.c_int]
-    lib.mi32_get_profile.restype = ctypes.c_int
-    lib.mi32_get_profile.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
-    lib.mi32_bench_32.restype = ctypes.c_int
-    lib.mi32_bench_32.argtypes = [fp, ctypes.c_size_t, ctypes.c_int, fp, ctypes.POINTER(ctypes.c_double)]
-    lib.mi32_bench_64.restype = ctypes.c_int
-    lib.mi32_bench_64.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_size_t, ctypes.c_int,
-                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int]
-    lib.mi32_matrix_multiply_64.restype = ctypes.c_int
-    lib.mi32_matrix_multiply_64.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_size_t,
-                                            ctypes.POINTER(ctypes.c_double)]
-    lib.mi32_last_timing.restype = ctypes.c_int
-    lib.mi32_last_timing.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    lib.mi32_resolve_algo.restype = ctypes.c_int
-    lib.mi32_resolve_algo.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.mi32_resolve_blocking.restype = ctypes.c_int
-    lib.mi32_resolve_blocking.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
-    dp = ctypes.POINTER(ctypes.c_double)
-    lib.mi32_matrix_inv_64.restype = ctypes.c_int
-    lib.mi32_matrix_inv_64.argtypes = [dp, ctypes.c_size_t, ctypes.c_int, dp]
-    lib.mi32_matrix_inversion_no_pivots.restype = ctypes.c_int
-    lib.mi32_matrix_inversion_no_pivots.argtypes = [dp, ctypes.c_size_t, ctypes.c_int, dp]
-    lib.mi32_set_pivoting.restype = ctypes.c_int
-    lib.mi32_set_pivoting.argtypes = [vp, ctypes.c_int]
-    lib.mi32_inv_device_f64.restype = ctypes.c_int
-    lib.mi32_inv_device_f64.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
-    lib.mi32_resolve_blocking_f64.restype = ctypes.c_int
-    lib.mi32_resolve_blocking_f64.argtypes = [vp, ctypes.c_int, ip]
-    lib.mi32_resolve_panel_widths.restype = ctypes.c_int
-    lib.mi32_resolve_panel_widths.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
-    lib.mi32_resolve_route.restype = ctypes.c_int
-    lib.mi32_resolve_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Route), ip, ctypes.c_int]
-    lib.mi32_resolve_resident.restype = ctypes.c_int
-    lib.mi32_resolve_resident.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip]
-    lib.mi32_resolve_workgroup.restype = ctypes.c_int
-    lib.mi32_resolve_workgroup.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
-    lib.mi32_resolve_wide.restype = ctypes.c_int
-    lib.mi32_resolve_wide.argtypes = [vp, ctypes.c_int, ctypes.c_int, ip, ip, ip]
-    lib.mi32_vbatch_bin.restype = ctypes.c_int
-    lib.mi32_vbatch_bin.argtypes = [ip, ctypes.c_int, ip, ip]
-    lib.mi32_vbatch_create.restype = ctypes.c_int
-    lib.mi32_vbatch_create.argtypes = [vp, ip, ctypes.c_int, ctypes.POINTER(vp)]
-    lib.mi32_vbatch_destroy.restype = ctypes.c_int
-    lib.mi32_vbatch_destroy.argtypes = [vp]
-    lib.mi32_vbatch_info.restype = ctypes.c_int
-    lib.mi32_vbatch_info.argtypes = [vp, ip, ip]
-    for fn in (lib.mi32_inv_device_vbatched, lib.mi32_inv_device_vbatched_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    for fn in (lib.mi32_inv_det_device, lib.mi32_inv_det_device_f64, lib.mi32_inv_det_any_device,
-               lib.mi32_inv_det_any_device_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
-    for fn in (lib.mi32_inv_det_device_vbatched, lib.mi32_inv_det_device_vbatched_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    for fn in (lib.mi32_solve_device, lib.mi32_solve_device_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp]
-    lib.mi32_resolve_solve.restype = ctypes.c_int
-    lib.mi32_resolve_solve.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip, ip, ip]
-    for fn in (lib.mi32_solve_device_vbatched, lib.mi32_solve_device_vbatched_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp]
-    lib.mi32_vbatch_solve_launches.restype = ctypes.c_int
-    lib.mi32_vbatch_solve_launches.argtypes = [ip, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
-    for fn in (lib.mi32_apply_device_vbatched, lib.mi32_apply_device_vbatched_f64):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp]
-    lib.mi32_vbatch_apply_launches.restype = ctypes.c_int
-    lib.mi32_vbatch_apply_launches.argtypes = [ip, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip]
-    lib.mi32_dominant_kernel.restype = ctypes.c_char_p
-    lib.mi32_dominant_kernel.argtypes = [ctypes.c_int]
-    lib.mi32_last_error.restype = ctypes.c_char_p
-    lib.mi32_last_error.argtypes = []
-    lib.mi32_version.restype = ctypes.c_int
-    lib.mi32_version.argtypes = []
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name == "mi32_debug_dpp_selftest" and not hasattr(lib, name):
+            continue  # tools/ab_bench.py also loads builds older than the self-test
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

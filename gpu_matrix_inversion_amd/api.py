@@ -201,13 +201,26 @@ def det_from_frexp(mant, exp, dtype=None):
 def vbatch_bin(orders):
     """``(perm, class_begin)`` of ``mi32_vbatch_bin`` (host only): the member indices sorted by order (stable) and the
     nine boundaries of the eight kernel classes in that list."""
-    o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
-    perm = np.empty(o.size, np.int32)
+    o, count = _order_array(orders)
+    perm = np.empty(count, np.int32)
     begin = np.empty(9, np.int32)
-    ip = ctypes.POINTER(ctypes.c_int)
-    _lib.check(_lib.load().mi32_vbatch_bin(o.ctypes.data_as(ip), int(o.size), perm.ctypes.data_as(ip),
-                                           begin.ctypes.data_as(ip)), "mi32_vbatch_bin")
+    _lib.check(_lib.load().mi32_vbatch_bin(_int_ptr(o), count, _int_ptr(perm), _int_ptr(begin)), "mi32_vbatch_bin")
     return perm, begin
+
+
+def _order_array(orders):
+    """``(contiguous int32 array, its length)`` of ``orders``: what the host-only queries hand to the library."""
+    o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
+    return o, int(o.size)
+
+
+def _int_ptr(array):
+    return array.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def _ptr(t):
+    """The address of a tensor as the library takes it; None stays None (a NULL argument)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _check_tensor(t, device, dtype, what, numel=None):
@@ -303,6 +316,131 @@ def check_dense_args(device, a, out=None, status=None, *, b=None, want_inverse=T
     return squeeze, a3, rhs, out3, status
 
 
+# ---- the argument handling of the variable-size calls: pure torch like check_dense_args, no handle and no GPU.
+# ``device`` is the Inverter's; of ``plan`` only ``batch``, ``flat_size``, ``total_rows``, ``orders``, ``device`` and
+# whether ``_p`` is set are read, so any object with those attributes stands for a RaggedPlan.  Every refusal is a
+# ValueError, raised before an address is formed. ----
+def _check_float(dtype, what):
+    import torch
+
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: expected torch.float32 or torch.float64, not {dtype}")
+
+
+def check_ragged_call(device, plan, dtype, status=None, *, max_order=128, want_status=True):
+    """What every variable-size call checks first: ``plan`` is an open RaggedPlan of ``device`` whose largest order the
+    call takes (``max_order``: 128 for ``inv`` and ``apply``, 127 for ``solve``); ``dtype``, the members' element type,
+    is float32 or float64; ``status`` is None or a contiguous 1-D int32 tensor of ``plan.batch`` entries on ``device``.
+    Returns the status tensor, allocated where None (None itself with ``want_status=False``: ``apply`` has none)."""
+    import torch
+
+    if not getattr(plan, "_p", None):
+        raise ValueError("expected an open RaggedPlan")
+    if plan.device != device:
+        raise ValueError(f"the plan lives on {plan.device}, this Inverter on {device}")
+    if int(plan.orders.max()) > max_order:
+        raise ValueError(f"this call takes orders up to {max_order}: the plan holds an order-{int(plan.orders.max())} "
+                         "member")
+    _check_float(dtype, "dtype")
+    if status is not None:
+        _check_tensor(status, device, torch.int32, "status", plan.batch)
+    elif want_status:
+        status = torch.empty(plan.batch, dtype=torch.int32, device=device)
+    return status
+
+
+def check_pointer_args(device, plan, dtype, ptrs, lds, status=None, *, nrhs=1, **call):
+    """The argument handling of ``inv_pointers`` / ``solve_pointers`` / ``apply_pointers``: ``check_ragged_call`` (which
+    takes ``call``), then ``nrhs``, integral and at least 1; ``ptrs``, {name: tensor} of the member address arrays,
+    contiguous 1-D int64 tensors of ``plan.batch`` entries on ``device``; ``lds``, the same for the leading dimensions,
+    in int32 or None.  Returns the status tensor.  What the addresses point to cannot be checked, overlap included."""
+    import torch
+
+    status = check_ragged_call(device, plan, dtype, status, **call)
+    if int(nrhs) != nrhs or nrhs < 1:
+        raise ValueError("nrhs: at least one column")
+    for what, t in ptrs.items():
+        _check_tensor(t, device, torch.int64, what, plan.batch)
+    for what, t in lds.items():
+        if t is not None:
+            _check_tensor(t, device, torch.int32, what, plan.batch)
+    return status
+
+
+def check_packed_matrices(device, plan, flat, what, status=None, **call):
+    """The matrices of ``inv_ragged`` / ``solve_ragged`` / ``apply_ragged``: ``check_ragged_call`` (which takes
+    ``call``) for flat's dtype, then ``flat`` itself, which holds the plan's members in the packed layout: a contiguous
+    1-D tensor of ``plan.flat_size`` elements on ``device``.  Returns the status tensor."""
+    status = check_ragged_call(device, plan, flat.dtype, status, **call)
+    _check_tensor(flat, device, flat.dtype, what, plan.flat_size)
+    return status
+
+
+def check_diag_blocks(device, m, block_orders):
+    """The block orders of ``inv_diag_blocks`` / ``solve_diag_blocks`` / ``apply_diag_blocks`` as an array: a non-empty
+    1-D sequence that sums to the order of ``m``, a contiguous square float32 / float64 matrix on ``device``.
+    ``m=None``: the blocks are stored packed, the orders may sum to anything."""
+    orders = np.asarray(block_orders)
+    if orders.ndim != 1 or orders.size == 0:
+        raise ValueError("block_orders: a non-empty 1-D sequence of block orders")
+    if m is not None:
+        _check_float(m.dtype, "the matrix")
+        if m.device != device:
+            raise ValueError(f"the matrix is on {m.device}, expected {device}")
+        if m.dim() != 2 or m.shape[0] != m.shape[1] or not m.is_contiguous():
+            raise ValueError("expected a contiguous square matrix")
+        if int(orders.sum()) != m.shape[0]:
+            raise ValueError("block_orders must sum to the matrix order")
+    return orders
+
+
+def _check_out_alias(out, replaced, read=None):
+    """The aliasing rule of the packed and diagonal-block calls, on contiguous tensors of one dtype and device:
+    ``out`` may be the input it replaces -- the same address and the same extent, in place -- and otherwise meets it
+    nowhere; it never meets ``read``, the matrices a ``solve`` or an ``apply`` reads."""
+    if (out.data_ptr() != replaced.data_ptr() or out.numel() != replaced.numel()) and _overlap(out, replaced):
+        raise ValueError("out may be the input it replaces (in place), not a part of its memory")
+    if read is not None and _overlap(out, read):
+        raise ValueError("out must not alias the matrices")
+
+
+def check_inverse_out(src, out, shape, zero=False):
+    """The output of ``inv_ragged`` / ``inv_diag_blocks`` for the input ``src`` (the packed members, or the matrix):
+    ``out`` where given -- a contiguous tensor of ``shape`` and of src's dtype and device, ``src`` itself (in place) or
+    memory that meets src's nowhere --, else a new tensor (``zero``: of zeros)."""
+    import torch
+
+    if out is None:
+        return (torch.zeros if zero else torch.empty)(tuple(shape), dtype=src.dtype, device=src.device)
+    if out.shape != tuple(shape) or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous tensor of shape {tuple(shape)} and of the input's dtype and device")
+    _check_out_alias(out, src)
+    return out
+
+
+def check_packed_rhs(plan, mats, b, out, what):
+    """The right-hand side of ``solve_ragged`` / ``solve_diag_blocks`` / ``apply_ragged`` / ``apply_diag_blocks``:
+    ``b`` is ``(plan.total_rows,)`` or ``(plan.total_rows, K)``, K >= 1, of the dtype and device of ``mats`` (the checked
+    matrices of the call), member i's rows starting at ``sum_{k<i} n_k``; ``out`` is None, ``b`` itself or a contiguous
+    tensor of b's shape, dtype and device that meets neither b's memory nor that of ``mats``.  Returns
+    ``(rhs, out, nrhs)``: ``rhs`` contiguous (a copy of a non-contiguous ``b``), ``out`` allocated where None, and 1
+    column for a vector."""
+    import torch
+
+    if b.dtype != mats.dtype or b.device != mats.device:
+        raise ValueError(f"{what} is {b.dtype} on {b.device}, expected {mats.dtype} on {mats.device}")
+    if b.dim() not in (1, 2) or b.shape[0] != plan.total_rows or b.numel() == 0:
+        raise ValueError(f"{what}: expected ({plan.total_rows},) or ({plan.total_rows}, K)")
+    nrhs = 1 if b.dim() == 1 else int(b.shape[1])
+    if out is None:
+        return b.contiguous(), torch.empty(b.shape, dtype=b.dtype, device=b.device), nrhs
+    if out.shape != b.shape or out.dtype != b.dtype or out.device != b.device or not out.is_contiguous():
+        raise ValueError(f"out: {what} itself or a contiguous tensor of its shape, dtype and device")
+    rhs = out if out is b else b.contiguous()
+    _check_out_alias(out, rhs, mats)
+    return rhs, out, nrhs
+
+
 class RaggedPlan:
     """A batch of members of mixed orders 1 ... 128 (``Inverter.plan_ragged``): the orders, binned once into the eight
     kernel classes and uploaded to the device.  Immutable; usable any number of times and from any ``Inverter`` on
@@ -331,43 +469,45 @@ class RaggedPlan:
         self.flat_size = int(sq.sum())
         # element offset of every member in the packed layout: member b at sum_{i<b} n_i^2
         self._offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(sq)[:-1]))).to(self.device)
-        self._ptrs = {}  # (base address, dtype) -> int64 device tensor of member addresses in the packed layout
-        # the packed right-hand side of solve_ragged: member b's rows start at sum_{i<b} n_i
+        # the packed right-hand side of solve_ragged and apply_ragged: member b's rows start at sum_{i<b} n_i
         rows = self.orders.astype(np.int64)
         self.total_rows = int(rows.sum())
         self._row_offsets = torch.from_numpy(np.concatenate(([0], np.cumsum(rows)[:-1]))).to(self.device)
-        self._row_ptrs = {}  # (base address, dtype, nrhs) -> int64 device tensor of member addresses (row_pointers)
+        self._torch = torch
+        # (base address, dtype, nrhs or None, stream) -> int64 device tensor of member addresses.  The stream that
+        # computed an entry is the only one that reads it, so dropping one is safe under the allocator's stream order.
+        self._ptrs = {}
 
-    def packed_pointers(self, flat):
-        """int64 device tensor of the member addresses inside the packed tensor ``flat`` (cached per base and dtype)."""
-        key = (flat.data_ptr(), flat.dtype)
+    def _pointers(self, t, nrhs, stream=None):
+        """The cache behind ``packed_pointers`` (``nrhs=None``) and ``row_pointers``: at most 8 entries, cleared when
+        full.  ``stream``: the current stream of the plan's device where the caller has looked it up already."""
+        if stream is None:
+            stream = self._torch.cuda.current_stream(self.device).cuda_stream
+        key = (t.data_ptr(), t.dtype, nrhs, stream)
         ptrs = self._ptrs.get(key)
         if ptrs is None:
             if len(self._ptrs) >= 8:
                 self._ptrs.clear()
-            ptrs = self._offsets * flat.element_size() + flat.data_ptr()
-            self._ptrs[key] = ptrs
+            offsets, step = (self._offsets, 1) if nrhs is None else (self._row_offsets, nrhs)
+            ptrs = self._ptrs[key] = offsets * (step * t.element_size()) + t.data_ptr()
         return ptrs
+
+    def packed_pointers(self, flat):
+        """int64 device tensor of the member addresses inside the packed tensor ``flat`` (cached per base, dtype and
+        current stream)."""
+        return self._pointers(flat, None)
 
     def row_pointers(self, t, nrhs):
         """int64 device tensor of the member addresses inside ``t``, a packed right-hand side of ``nrhs`` columns
-        (member b's rows start at ``sum_{i<b} n_i``; cached per base, dtype and width: an iteration that applies the
-        same buffers again computes nothing)."""
-        key = (t.data_ptr(), t.dtype, int(nrhs))
-        ptrs = self._row_ptrs.get(key)
-        if ptrs is None:
-            if len(self._row_ptrs) >= 8:
-                self._row_ptrs.clear()
-            ptrs = self._row_offsets * (int(nrhs) * t.element_size()) + t.data_ptr()
-            self._row_ptrs[key] = ptrs
-        return ptrs
+        (member b's rows start at ``sum_{i<b} n_i``; cached per base, dtype, width and current stream: an iteration
+        that uses the same buffers again computes nothing)."""
+        return self._pointers(t, int(nrhs))
 
     def close(self):
         if getattr(self, "_p", None):
             self._lib.mi32_vbatch_destroy(self._p)
             self._p = None
             self._ptrs = {}
-            self._row_ptrs = {}
 
     def __del__(self):  # pragma: no cover
         try:
@@ -416,6 +556,11 @@ class Inverter:
     def _bind_stream(self):
         s = self._torch.cuda.current_stream(self.device)
         _lib.check(self._lib.mi32_set_stream(self._h, ctypes.c_void_p(s.cuda_stream)), "mi32_set_stream")
+        return s.cuda_stream
+
+    def _entry(self, stem, dtype):
+        """The C entry point ``stem`` for float32 members, ``stem + "_f64"`` for float64 ones."""
+        return getattr(self._lib, stem if dtype == self._torch.float32 else stem + "_f64")
 
     def resolved_algo(self, n: int, batch: int = 1) -> int:
         return self._lib.mi32_resolve_algo(self._h, int(n), int(batch))
@@ -501,16 +646,10 @@ class Inverter:
         squeeze, a3, _, out, status = check_dense_args(self.device, a, out, status, want_inverse=want_inverse,
                                                        max_order=max_order)
         b, n = a3.shape[0], a3.shape[1]
-        pair = ptrs = ()
-        if det:
-            pair = (torch.empty(b, dtype=torch.float64, device=a3.device),
-                    torch.empty(b, dtype=torch.int32, device=a3.device))
-            ptrs = (ctypes.c_void_p(pair[0].data_ptr()), ctypes.c_void_p(pair[1].data_ptr()))
+        pair = (torch.empty(b, dtype=torch.float64, device=a3.device),
+                torch.empty(b, dtype=torch.int32, device=a3.device)) if det else ()
         self._bind_stream()
-        fn = getattr(self._lib, stem if a.dtype == torch.float32 else stem + "_f64")
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, b,
-                      ctypes.c_void_p(out.data_ptr()) if out is not None else None, ctypes.c_void_p(status.data_ptr()),
-                      *ptrs), stem)
+        _lib.check(self._entry(stem, a.dtype)(self._h, _ptr(a3), n, b, _ptr(out), _ptr(status), *map(_ptr, pair)), stem)
         return ((None if out is None else out[0] if squeeze else out), status) + pair
 
     def inv_det(self, a, out=None, status=None, want_inverse=True):
@@ -559,28 +698,17 @@ class Inverter:
         ``b`` the identity, x is ``inv``'s result bit for bit.  More than ``resolved_solve(N, K)[0]`` columns take one
         launch per chunk, and every launch repeats the elimination of A.  Always runs on the register-resident or
         workgroup-resident kernels, whatever ``algo`` is.  Asynchronous on torch's current stream."""
-        torch = self._torch
         _, a3, rhs, out3, status = check_dense_args(self.device, a, out, status, b=b)
         bsz, n = a3.shape[0], a3.shape[1]
         self._bind_stream()
-        fn = self._lib.mi32_solve_device if a.dtype == torch.float32 else self._lib.mi32_solve_device_f64
-        _lib.check(fn(self._h, ctypes.c_void_p(a3.data_ptr()), n, bsz, ctypes.c_void_p(rhs.data_ptr()), rhs.shape[2],
-                      ctypes.c_void_p(out3.data_ptr()), ctypes.c_void_p(status.data_ptr())), "mi32_solve_device")
+        _lib.check(self._entry("mi32_solve_device", a.dtype)(self._h, _ptr(a3), n, bsz, _ptr(rhs), rhs.shape[2],
+                                                             _ptr(out3), _ptr(status)), "mi32_solve_device")
         return out3.view(b.shape), status
 
     # ---- variable-size batches: mixed orders 1 ... 128, each member at its own pointer and leading dimension ----
     def plan_ragged(self, orders) -> RaggedPlan:
         """Bin a batch of members of the given orders (a sequence or an int array, each 1 ... 128) once."""
         return RaggedPlan(self, orders)
-
-    def _check_plan(self, plan):
-        if not isinstance(plan, RaggedPlan) or not plan._p:
-            raise ValueError("expected an open RaggedPlan")
-        if plan.device != self.device:
-            raise ValueError(f"the plan lives on {plan.device}, this Inverter on {self.device}")
-
-    def _check_tensor(self, t, dtype, what, numel=None):
-        _check_tensor(t, self.device, dtype, what, numel)
 
     def inv_pointers(self, plan, a_ptrs, out_ptrs, dtype, lda=None, ldout=None, status=None, *, det=False):
         """The low-level form: ``a_ptrs`` / ``out_ptrs`` are int64 device tensors of ``plan.batch`` member addresses
@@ -590,55 +718,35 @@ class Inverter:
         Returns the status tensor (int32[batch], the caller's member order).  ``det=True``: the determinants come
         from the same launches and ``(status, (det_mant, det_exp))`` is returned (float64[batch] and int32[batch] in
         the caller's member order, the pair of ``inv_det``); ``out_ptrs=None`` is then the determinant-only form."""
-        torch = self._torch
-        self._check_plan(plan)
-        if dtype not in (torch.float32, torch.float64):
-            raise ValueError("dtype: torch.float32 or torch.float64")
-        self._check_tensor(a_ptrs, torch.int64, "a_ptrs", plan.batch)
         if out_ptrs is None and not det:
             raise ValueError("out_ptrs=None needs det=True (the determinant-only form)")
-        if out_ptrs is not None:
-            self._check_tensor(out_ptrs, torch.int64, "out_ptrs", plan.batch)
-        for ld, what in ((lda, "lda"), (ldout, "ldout")):
-            if ld is not None:
-                self._check_tensor(ld, torch.int32, what, plan.batch)
-        if status is None:
-            status = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
-        else:
-            self._check_tensor(status, torch.int32, "status", plan.batch)
+        ptrs = {"a_ptrs": a_ptrs} if out_ptrs is None else {"a_ptrs": a_ptrs, "out_ptrs": out_ptrs}
+        status = check_pointer_args(self.device, plan, dtype, ptrs, {"lda": lda, "ldout": ldout}, status)
         self._bind_stream()
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        if det:
-            det_mant = torch.empty(plan.batch, dtype=torch.float64, device=self.device)
-            det_exp = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
-            fn = (self._lib.mi32_inv_det_device_vbatched if dtype == torch.float32
-                  else self._lib.mi32_inv_det_device_vbatched_f64)
-            _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(out_ptrs), ptr(ldout), ptr(status), ptr(det_mant),
-                          ptr(det_exp)), "mi32_inv_det_device_vbatched")
-            return status, (det_mant, det_exp)
-        fn = self._lib.mi32_inv_device_vbatched if dtype == torch.float32 else self._lib.mi32_inv_device_vbatched_f64
-        _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(out_ptrs), ptr(ldout), ptr(status)),
-                   "mi32_inv_device_vbatched")
-        return status
+        return self._inv_vbatched(plan, dtype, a_ptrs, lda, out_ptrs, ldout, status, det)
+
+    def _inv_vbatched(self, plan, dtype, a_ptrs, lda, out_ptrs, ldout, status, det):
+        """The library call of the variable-size inversions, on the stream bound; ``status``, or with ``det``
+        ``(status, (det_mant, det_exp))``."""
+        torch = self._torch
+        pair = (torch.empty(plan.batch, dtype=torch.float64, device=self.device),
+                torch.empty(plan.batch, dtype=torch.int32, device=self.device)) if det else ()
+        stem = "mi32_inv_det_device_vbatched" if det else "mi32_inv_device_vbatched"
+        _lib.check(self._entry(stem, dtype)(self._h, plan._p, _ptr(a_ptrs), _ptr(lda), _ptr(out_ptrs), _ptr(ldout),
+                                            _ptr(status), *map(_ptr, pair)), stem)
+        return (status, pair) if det else status
 
     def inv_ragged(self, plan, a_flat, out=None, status=None, *, det=False):
         """The packed layout: ``a_flat`` is a 1-D float32 / float64 device tensor in which member b holds its
         ``n_b * n_b`` row-major elements at offset ``sum_{i<b} n_i^2``.  One call, at most eight launches.  ``out``
-        may be ``a_flat`` itself (in place).  Returns ``(out_flat, status)``; with ``det=True``
-        ``(out_flat, status, (det_mant, det_exp))``, the pair of ``inv_det`` in the caller's member order."""
-        torch = self._torch
-        self._check_plan(plan)
-        if a_flat.dtype not in (torch.float32, torch.float64):
-            raise ValueError("expected a float32 or float64 tensor")
-        self._check_tensor(a_flat, a_flat.dtype, "a_flat")
-        if a_flat.numel() != plan.flat_size:
-            raise ValueError(f"a_flat holds {a_flat.numel()} elements, the plan's members {plan.flat_size}")
-        if out is None:
-            out = torch.empty_like(a_flat)
-        else:
-            self._check_tensor(out, a_flat.dtype, "out", plan.flat_size)
-        r = self.inv_pointers(plan, plan.packed_pointers(a_flat), plan.packed_pointers(out), a_flat.dtype,
-                              status=status, det=det)
+        may be ``a_flat`` itself (in place) and otherwise meets its memory nowhere.  Returns ``(out_flat, status)``;
+        with ``det=True`` ``(out_flat, status, (det_mant, det_exp))``, the pair of ``inv_det`` in the caller's member
+        order."""
+        status = check_packed_matrices(self.device, plan, a_flat, "a_flat", status)
+        out = check_inverse_out(a_flat, out, a_flat.shape)
+        stream = self._bind_stream()
+        r = self._inv_vbatched(plan, a_flat.dtype, plan._pointers(a_flat, None, stream), None,
+                               plan._pointers(out, None, stream), None, status, det)
         return (out, r[0], r[1]) if det else (out, r)
 
     def resolved_solve_ragged(self, orders, nrhs: int):
@@ -648,15 +756,13 @@ class Inverter:
         names it (lanes per member, or 0 and the workgroup-resident kernel's rows per thread).  Every member runs as
         ``solve`` would run a uniform batch of its order; members whose chunks agree share their launches, so
         ``nrhs = 1`` takes at most eight.  An order outside 1 ... 127 or ``nrhs < 1`` raises ValueError."""
-        o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
-        ip = ctypes.POINTER(ctypes.c_int)
+        o, size = _order_array(orders)
         count = ctypes.c_int()
-        _lib.check(self._lib.mi32_vbatch_solve_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs), None, 0,
-                                                        ctypes.byref(count)), "mi32_vbatch_solve_launches")
-        out = np.empty((count.value, 6), np.int32)
-        _lib.check(self._lib.mi32_vbatch_solve_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs),
-                                                        out.ctypes.data_as(ip), count.value, ctypes.byref(count)),
+        _lib.check(self._lib.mi32_vbatch_solve_launches(_int_ptr(o), size, int(nrhs), None, 0, ctypes.byref(count)),
                    "mi32_vbatch_solve_launches")
+        out = np.empty((count.value, 6), np.int32)
+        _lib.check(self._lib.mi32_vbatch_solve_launches(_int_ptr(o), size, int(nrhs), _int_ptr(out), count.value,
+                                                        ctypes.byref(count)), "mi32_vbatch_solve_launches")
         return [tuple(int(v) for v in row) for row in out]
 
     def solve_pointers(self, plan, a_ptrs, b_ptrs, x_ptrs, dtype, nrhs, lda=None, ldb=None, ldx=None, status=None):
@@ -668,81 +774,46 @@ class Inverter:
         undefined.  ``nrhs < 1`` or a plan that holds an order-128 member raises ValueError.  Every member is
         ``solve``'s result for its order bit for bit; ``resolved_solve_ragged`` lists the launches.  Asynchronous on
         torch's current stream.  Returns the status tensor (int32[batch], the caller's member order)."""
-        torch = self._torch
-        self._check_plan(plan)
-        if dtype not in (torch.float32, torch.float64):
-            raise ValueError("dtype: torch.float32 or torch.float64")
-        if int(nrhs) != nrhs or nrhs < 1:
-            raise ValueError("nrhs: at least one column")
-        if int(plan.orders.max()) > 127:
-            raise ValueError("solve takes orders up to 127: the plan holds an order-128 member")
-        for t, what in ((a_ptrs, "a_ptrs"), (b_ptrs, "b_ptrs"), (x_ptrs, "x_ptrs")):
-            self._check_tensor(t, torch.int64, what, plan.batch)
-        for ld, what in ((lda, "lda"), (ldb, "ldb"), (ldx, "ldx")):
-            if ld is not None:
-                self._check_tensor(ld, torch.int32, what, plan.batch)
-        if status is None:
-            status = torch.empty(plan.batch, dtype=torch.int32, device=self.device)
-        else:
-            self._check_tensor(status, torch.int32, "status", plan.batch)
+        status = check_pointer_args(self.device, plan, dtype, {"a_ptrs": a_ptrs, "b_ptrs": b_ptrs, "x_ptrs": x_ptrs},
+                                    {"lda": lda, "ldb": ldb, "ldx": ldx}, status, nrhs=nrhs, max_order=127)
         self._bind_stream()
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        fn = self._lib.mi32_solve_device_vbatched if dtype == torch.float32 else self._lib.mi32_solve_device_vbatched_f64
-        _lib.check(fn(self._h, plan._p, ptr(a_ptrs), ptr(lda), ptr(b_ptrs), ptr(ldb), int(nrhs), ptr(x_ptrs), ptr(ldx),
-                      ptr(status)), "mi32_solve_device_vbatched")
-        return status
+        return self._solve_vbatched(plan, dtype, nrhs, a_ptrs, lda, b_ptrs, ldb, x_ptrs, ldx, status)
 
-    def _packed_rhs(self, plan, a_dtype, a_device, b, out, what):
-        """The right-hand side handling ``solve_ragged`` and ``solve_diag_blocks`` share: ``b`` is (plan.total_rows,)
-        or (plan.total_rows, K), member i's rows starting at ``sum_{k<i} n_k``.  Returns ``(rhs, out, nrhs)`` with
-        ``rhs`` contiguous and ``out`` a contiguous tensor of b's shape (``b`` itself for the in-place form)."""
-        torch = self._torch
-        if b.dtype != a_dtype or b.device != a_device:
-            raise ValueError(f"{what} is {b.dtype} on {b.device}, expected {a_dtype} on {a_device}")
-        if b.dim() not in (1, 2) or b.shape[0] != plan.total_rows or b.numel() == 0:
-            raise ValueError(f"{what}: expected ({plan.total_rows},) or ({plan.total_rows}, K)")
-        nrhs = 1 if b.dim() == 1 else int(b.shape[1])
-        if out is None:
-            return b.contiguous(), torch.empty(b.shape, dtype=b.dtype, device=b.device), nrhs
-        if out.shape != b.shape or out.dtype != b.dtype or out.device != b.device or not out.is_contiguous():
-            raise ValueError(f"out: {what} itself or a contiguous tensor of its shape, dtype and device")
-        return (out if out is b else b.contiguous()), out, nrhs
+    def _solve_vbatched(self, plan, dtype, nrhs, a_ptrs, lda, b_ptrs, ldb, x_ptrs, ldx, status):
+        """The library call of the variable-size solves, on the stream bound; returns ``status``."""
+        _lib.check(self._entry("mi32_solve_device_vbatched", dtype)(
+            self._h, plan._p, _ptr(a_ptrs), _ptr(lda), _ptr(b_ptrs), _ptr(ldb), int(nrhs), _ptr(x_ptrs), _ptr(ldx),
+            _ptr(status)), "mi32_solve_device_vbatched")
+        return status
 
     def solve_ragged(self, plan, a_flat, b, out=None, status=None):
         """A X = B for members of mixed orders 1 ... 127 in one call.  ``a_flat`` is the packed layout of
         ``inv_ragged``; ``b`` is a contiguous ``(plan.total_rows,)`` or ``(plan.total_rows, K)`` tensor of a_flat's
         dtype and device in which member i's rows start at ``sum_{k<i} n_k`` (a vector keeps its shape).  ``out`` may
-        be ``b`` itself (in place) or a contiguous tensor of its shape; it must not be ``a_flat``.  Returns
+        be ``b`` itself (in place) or a contiguous tensor of its shape that meets b's memory nowhere; it never meets
+        that of ``a_flat``.  Returns
         ``(x, status)``; x of a member whose status is not 0 is unspecified.  A plan that holds an order-128 member
         raises ValueError."""
-        torch = self._torch
-        self._check_plan(plan)
-        if a_flat.dtype not in (torch.float32, torch.float64):
-            raise ValueError("expected a float32 or float64 tensor")
-        self._check_tensor(a_flat, a_flat.dtype, "a_flat")
-        if a_flat.numel() != plan.flat_size:
-            raise ValueError(f"a_flat holds {a_flat.numel()} elements, the plan's members {plan.flat_size}")
-        if out is a_flat or (out is not None and out.data_ptr() == a_flat.data_ptr()):
-            raise ValueError("out must not alias a_flat")
-        rhs, out, nrhs = self._packed_rhs(plan, a_flat.dtype, a_flat.device, b, out, "b")
-        step = nrhs * rhs.element_size()
-        st = self.solve_pointers(plan, plan.packed_pointers(a_flat), plan._row_offsets * step + rhs.data_ptr(),
-                                 plan._row_offsets * step + out.data_ptr(), a_flat.dtype, nrhs, status=status)
-        return out, st
+        status = check_packed_matrices(self.device, plan, a_flat, "a_flat", status, max_order=127)
+        rhs, out, nrhs = check_packed_rhs(plan, a_flat, b, out, "b")
+        stream = self._bind_stream()
+        return out, self._solve_vbatched(plan, a_flat.dtype, nrhs, plan._pointers(a_flat, None, stream), None,
+                                         plan._pointers(rhs, nrhs, stream), None, plan._pointers(out, nrhs, stream),
+                                         None, status)
 
     def solve_diag_blocks(self, m, block_orders, r, out=None):
         """``z = blockdiag(m)^-1 r``, the application of a block-Jacobi preconditioner, in one call: the consecutive
         diagonal blocks of the square device matrix ``m`` have the orders ``block_orders`` (each 1 ... 127, summing to
         ``m.shape[0]``), ``r`` is ``(N,)`` or ``(N, K)`` of m's dtype and device.  Only the block entries of ``m`` are
-        read and no inverse is formed.  ``out`` may be ``r`` itself.  Returns ``(z, status)`` with one status word per
-        block.  The plan of the last block structure is kept (shared with ``inv_diag_blocks``)."""
+        read and no inverse is formed.  ``out`` as in ``solve_ragged``, with ``m`` for ``a_flat``.  Returns ``(z, status)``
+        with one status word per block.  The plan of the last block structure is kept (shared with ``inv_diag_blocks``)."""
         plan, elem_off, lds = self._diag_blocks_plan(m, block_orders)
-        rhs, out, nrhs = self._packed_rhs(plan, m.dtype, m.device, r, out, "r")
-        step = nrhs * rhs.element_size()
-        st = self.solve_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
-                                 plan._row_offsets * step + rhs.data_ptr(), plan._row_offsets * step + out.data_ptr(),
-                                 m.dtype, nrhs, lda=lds)
-        return out, st
+        status = check_ragged_call(self.device, plan, m.dtype, max_order=127)
+        rhs, out, nrhs = check_packed_rhs(plan, m, r, out, "r")
+        stream = self._bind_stream()
+        return out, self._solve_vbatched(plan, m.dtype, nrhs, elem_off * m.element_size() + m.data_ptr(), lds,
+                                         plan._pointers(rhs, nrhs, stream), None, plan._pointers(out, nrhs, stream),
+                                         None, status)
 
     # ---- Z = X R: applying stored inverses ----
     def resolved_apply_ragged(self, orders, nrhs: int, elem_bytes: int = 4):
@@ -752,13 +823,11 @@ class Inverter:
         workgroup of 128 threads per member) and the columns the kernel holds at a time.  One launch per lane class
         that has members, at most five whatever ``nrhs`` is.  An order outside 1 ... 128, ``nrhs < 1`` or an
         ``elem_bytes`` other than 4 or 8 raises ValueError."""
-        o = np.ascontiguousarray(np.asarray(orders).reshape(-1), dtype=np.int32)
-        ip = ctypes.POINTER(ctypes.c_int)
+        o, size = _order_array(orders)
         count = ctypes.c_int()
         out = np.empty((5, 4), np.int32)
-        _lib.check(self._lib.mi32_vbatch_apply_launches(o.ctypes.data_as(ip), int(o.size), int(nrhs), int(elem_bytes),
-                                                        out.ctypes.data_as(ip), 5, ctypes.byref(count)),
-                   "mi32_vbatch_apply_launches")
+        _lib.check(self._lib.mi32_vbatch_apply_launches(_int_ptr(o), size, int(nrhs), int(elem_bytes), _int_ptr(out), 5,
+                                                        ctypes.byref(count)), "mi32_vbatch_apply_launches")
         return [tuple(int(v) for v in row) for row in out[:count.value]]
 
     def apply_pointers(self, plan, x_ptrs, r_ptrs, z_ptrs, dtype, nrhs, ldx=None, ldr=None, ldz=None):
@@ -769,24 +838,16 @@ class Inverter:
         one chain of fused multiply-adds over j ascending from +0, so the result is reproducible bit for bit; there
         is no status.  A member may be applied in place (the same address and leading dimension for R and Z); Z over
         X, or members that overlap otherwise, are undefined.  Asynchronous on torch's current stream."""
-        torch = self._torch
-        self._check_plan(plan)
-        if dtype not in (torch.float32, torch.float64):
-            raise ValueError("dtype: torch.float32 or torch.float64")
-        if int(nrhs) != nrhs or nrhs < 1:
-            raise ValueError("nrhs: at least one column")
-        for t, what in ((x_ptrs, "x_ptrs"), (r_ptrs, "r_ptrs"), (z_ptrs, "z_ptrs")):
-            self._check_tensor(t, torch.int64, what, plan.batch)
-        for ld, what in ((ldx, "ldx"), (ldr, "ldr"), (ldz, "ldz")):
-            if ld is not None:
-                self._check_tensor(ld, torch.int32, what, plan.batch)
+        check_pointer_args(self.device, plan, dtype, {"x_ptrs": x_ptrs, "r_ptrs": r_ptrs, "z_ptrs": z_ptrs},
+                           {"ldx": ldx, "ldr": ldr, "ldz": ldz}, nrhs=nrhs, want_status=False)
         self._bind_stream()
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        fn = self._lib.mi32_apply_device_vbatched if dtype == torch.float32 else self._lib.mi32_apply_device_vbatched_f64
-        _lib.check(fn(self._h, plan._p, ptr(x_ptrs), ptr(ldx), ptr(r_ptrs), ptr(ldr), int(nrhs), ptr(z_ptrs), ptr(ldz)),
-                   "mi32_apply_device_vbatched")
+        self._apply_vbatched(plan, dtype, nrhs, x_ptrs, ldx, r_ptrs, ldr, z_ptrs, ldz)
 
-    _overlap = staticmethod(_overlap)
+    def _apply_vbatched(self, plan, dtype, nrhs, x_ptrs, ldx, r_ptrs, ldr, z_ptrs, ldz):
+        """The library call of the variable-size applications, on the stream bound."""
+        _lib.check(self._entry("mi32_apply_device_vbatched", dtype)(
+            self._h, plan._p, _ptr(x_ptrs), _ptr(ldx), _ptr(r_ptrs), _ptr(ldr), int(nrhs), _ptr(z_ptrs), _ptr(ldz)),
+            "mi32_apply_device_vbatched")
 
     def apply_ragged(self, plan, x_flat, r, out=None):
         """``z = blockdiag(X) r`` for members of mixed orders 1 ... 128 in one call: with ``x_flat`` the inverses
@@ -794,64 +855,36 @@ class Inverter:
         ``x_flat`` is the packed layout of ``inv_ragged``; ``r`` is a contiguous ``(plan.total_rows,)`` or
         ``(plan.total_rows, K)`` tensor of x_flat's dtype and device in which member i's rows start at
         ``sum_{k<i} n_k`` (a vector keeps its shape).  ``out`` may be ``r`` itself (in place) or a contiguous tensor
-        of its shape; it must not alias ``x_flat``.  Returns z."""
-        torch = self._torch
-        self._check_plan(plan)
-        if x_flat.dtype not in (torch.float32, torch.float64):
-            raise ValueError("expected a float32 or float64 tensor")
-        self._check_tensor(x_flat, x_flat.dtype, "x_flat")
-        if x_flat.numel() != plan.flat_size:
-            raise ValueError(f"x_flat holds {x_flat.numel()} elements, the plan's members {plan.flat_size}")
-        rhs, out, nrhs = self._packed_rhs(plan, x_flat.dtype, x_flat.device, r, out, "r")
-        if self._overlap(out, x_flat):
-            raise ValueError("out must not alias x_flat")
-        self.apply_pointers(plan, plan.packed_pointers(x_flat), plan.row_pointers(rhs, nrhs),
-                            plan.row_pointers(out, nrhs), x_flat.dtype, nrhs)
+        of its shape that meets r's memory nowhere; it never meets that of ``x_flat``.  Returns z."""
+        check_packed_matrices(self.device, plan, x_flat, "x_flat", want_status=False)
+        rhs, out, nrhs = check_packed_rhs(plan, x_flat, r, out, "r")
+        stream = self._bind_stream()
+        self._apply_vbatched(plan, x_flat.dtype, nrhs, plan._pointers(x_flat, None, stream), None,
+                             plan._pointers(rhs, nrhs, stream), None, plan._pointers(out, nrhs, stream), None)
         return out
 
     def apply_diag_blocks(self, x, block_orders, r, out=None):
         """``z = blockdiag(x) r`` in one call: ``x`` holds the consecutive diagonal blocks of the orders
         ``block_orders`` (each 1 ... 128, summing to N) either as the dense square N x N matrix ``inv_diag_blocks``
         returns, of which only the block entries are read, or as a 1-D packed tensor (``inv_diag_blocks(...,
-        packed=True)``).  ``r`` is ``(N,)`` or ``(N, K)`` of x's dtype and device; ``out`` may be ``r`` itself.
+        packed=True)``).  ``r`` is ``(N,)`` or ``(N, K)`` of x's dtype and device; ``out`` as in ``apply_ragged``.
         Returns z.  The plan of the last block structure is kept (shared with ``inv_diag_blocks``)."""
         if x.dim() == 1:
-            plan = self._diag_blocks_structure(block_orders, x.device, None)[0]
-            if x.numel() != plan.flat_size:
-                raise ValueError(f"the packed x holds {x.numel()} elements, blocks of these orders {plan.flat_size} "
-                                 "(the sum of their squares)")
-            return self.apply_ragged(plan, x, r, out)
+            return self.apply_ragged(self._diag_blocks_plan(None, block_orders)[0], x, r, out)
         plan, elem_off, lds = self._diag_blocks_plan(x, block_orders)
-        rhs, out, nrhs = self._packed_rhs(plan, x.dtype, x.device, r, out, "r")
-        if self._overlap(out, x):
-            raise ValueError("out must not alias x")
-        self.apply_pointers(plan, elem_off * x.element_size() + x.data_ptr(), plan.row_pointers(rhs, nrhs),
-                            plan.row_pointers(out, nrhs), x.dtype, nrhs, ldx=lds)
+        check_ragged_call(self.device, plan, x.dtype, want_status=False)
+        rhs, out, nrhs = check_packed_rhs(plan, x, r, out, "r")
+        stream = self._bind_stream()
+        self._apply_vbatched(plan, x.dtype, nrhs, elem_off * x.element_size() + x.data_ptr(), lds,
+                             plan._pointers(rhs, nrhs, stream), None, plan._pointers(out, nrhs, stream), None)
         return out
 
     def _diag_blocks_plan(self, m, block_orders):
-        """``(plan, element offsets of the blocks in m, leading dimensions)`` for the diagonal blocks of ``m``, from
-        the one-entry cache ``_diag_plan`` where the block structure is that of the last call."""
+        """``(plan, element offsets of the blocks in m, leading dimensions)`` for the diagonal blocks of ``m``
+        (``check_diag_blocks``; None: the packed form), from the one-entry cache ``_diag_plan`` where the block
+        structure is that of the last call."""
         torch = self._torch
-        if m.dtype not in (torch.float32, torch.float64):
-            raise ValueError("expected a float32 or float64 matrix")
-        if m.device != self.device:
-            raise ValueError(f"m is on {m.device}, expected {self.device}")
-        if m.dim() != 2 or m.shape[0] != m.shape[1] or not m.is_contiguous():
-            raise ValueError("expected a contiguous square matrix")
-        return self._diag_blocks_structure(block_orders, m.device, m.shape[0])
-
-    def _diag_blocks_structure(self, block_orders, device, total):
-        """The cache behind ``_diag_blocks_plan``; ``total``: what the orders must sum to (None: anything, the packed
-        form)."""
-        torch = self._torch
-        if device != self.device:
-            raise ValueError(f"the blocks are on {device}, expected {self.device}")
-        orders = np.asarray(block_orders)
-        if orders.ndim != 1 or orders.size == 0:
-            raise ValueError("block_orders: a non-empty 1-D sequence of block orders")
-        if total is not None and int(orders.sum()) != total:
-            raise ValueError("block_orders must sum to the matrix order")
+        orders = check_diag_blocks(self.device, m, block_orders)
         ld = int(orders.sum())
         key = orders.astype(np.int32).tobytes()
         if self._diag_plan is None or self._diag_plan[0] != key:
@@ -867,27 +900,22 @@ class Inverter:
     def inv_diag_blocks(self, m, block_orders, out=None, *, det=False, packed=False):
         """Invert the consecutive diagonal blocks of the square device matrix ``m`` (the block-Jacobi case): their
         orders (each 1 ... 128) must sum to ``m.shape[0]``.  Only the block entries of ``out`` (same shape, zeros by
-        default) are written, and only the block entries of ``m`` are read.  Returns ``(out, status)``; with
-        ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block (the determinant of the block-diagonal
-        matrix is their product: add the logarithms of ``slogdet_from_frexp``).  ``packed=True``: ``out`` is the packed
-        layout of ``inv_ragged`` instead -- a 1-D tensor of ``sum n_b^2`` elements, block b at offset
-        ``sum_{i<b} n_i^2``, what ``apply_diag_blocks`` takes -- and no N x N buffer is touched."""
-        torch = self._torch
+        default; ``m`` itself, or memory that meets m's nowhere) are written, and only the block entries of ``m`` are
+        read.  Returns ``(out, status)``; with ``det=True`` ``(out, status, (det_mant, det_exp))``, one pair per block
+        (the determinant of the block-diagonal matrix is their product: add the logarithms of ``slogdet_from_frexp``).
+        ``packed=True``: ``out`` is the packed layout of ``inv_ragged`` instead -- a 1-D tensor of ``sum n_b^2``
+        elements, block b at offset ``sum_{i<b} n_i^2``, what ``apply_diag_blocks`` takes -- and no N x N buffer is
+        touched."""
         plan, elem_off, lds = self._diag_blocks_plan(m, block_orders)
+        status = check_ragged_call(self.device, plan, m.dtype)
+        out = check_inverse_out(m, out, (plan.flat_size,) if packed else m.shape, zero=not packed)
+        stream = self._bind_stream()
         if packed:
-            if out is None:
-                out = torch.empty(plan.flat_size, dtype=m.dtype, device=m.device)
-            else:
-                self._check_tensor(out, m.dtype, "out", plan.flat_size)
-            r = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(), plan.packed_pointers(out), m.dtype,
-                                  lda=lds, det=det)
-            return (out, r[0], r[1]) if det else (out, r)
-        if out is None:
-            out = torch.zeros_like(m)
-        elif out.shape != m.shape or out.dtype != m.dtype or out.device != m.device or not out.is_contiguous():
-            raise ValueError("out: a contiguous matrix of m's shape, dtype and device")
-        r = self.inv_pointers(plan, elem_off * m.element_size() + m.data_ptr(),
-                              elem_off * out.element_size() + out.data_ptr(), m.dtype, lda=lds, ldout=lds, det=det)
+            out_ptrs, ldout = plan._pointers(out, None, stream), None
+        else:
+            out_ptrs, ldout = elem_off * out.element_size() + out.data_ptr(), lds
+        r = self._inv_vbatched(plan, m.dtype, elem_off * m.element_size() + m.data_ptr(), lds, out_ptrs, ldout, status,
+                               det)
         return (out, r[0], r[1]) if det else (out, r)
 
     def set_lookahead(self, enable: bool):

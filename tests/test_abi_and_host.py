@@ -70,6 +70,25 @@ def test_every_declared_symbol_is_exported():
                      r"std::vector<float> inversa32;\s*\};", hb)
 
 
+def test_every_binding_has_the_headers_signature():
+    """For every function include/mat_inv_32_c.h declares, the bound ctypes function takes the header's number of
+    parameters and returns the header's type: ``size_t``, ``const char *`` or ``int``."""
+    hdr = open(os.path.join(ROOT, "include", "mat_inv_32_c.h")).read()
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)\b(mi32_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)
+    assert len(protos) == len({name for _, name, _ in protos}) == len(_lib.C_ABI_SYMBOLS) == 56
+    lib = _lib.load()
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        count = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == count, (name, fn.argtypes, params)
+        ret = " ".join(ret.replace("*", " * ").split())
+        want = {"size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "int": ctypes.c_int}[ret]
+        assert fn.restype is want, (name, ret, fn.restype)
+    assert {name for _, name, _ in protos if getattr(lib, name).restype is not ctypes.c_int} == \
+        {"mi32_workspace_bytes", "mi32_dominant_kernel", "mi32_last_error"}
+
+
 def test_dropin_header_matches_reference_declaration():
     """include/mat_inv_32.h keeps the reference's declaration verbatim (Matlab/mat_inv_32.h:4)."""
     hdr = open(os.path.join(ROOT, "include", "mat_inv_32.h")).read()

@@ -246,6 +246,31 @@ def test_plan_reuse_streams_and_null_status(inv):
         inv.inv_ragged(plan, a0)                                # a closed plan
 
 
+def test_pointer_cache_by_stream(inv):
+    """The member addresses are cached per buffer and per stream: the tensor a stream reads is one that stream wrote."""
+    orders = [3, 40, 70, 100]
+    plan = inv.plan_ragged(orders)
+    try:
+        a = torch.zeros(plan.flat_size, device="cuda")
+        r = torch.zeros(plan.total_rows, 3, device="cuda")
+        for base, get, offsets, step in (
+                (a.data_ptr(), lambda: plan.packed_pointers(a), np.cumsum([0] + [n * n for n in orders])[:-1], 4),
+                (r.data_ptr(), lambda: plan.row_pointers(r, 3), np.cumsum([0] + orders)[:-1], 3 * 4)):
+            first = get()
+            assert get() is first
+            s = torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                other = get()
+                assert get() is other
+            s.synchronize()
+            torch.cuda.synchronize()
+            assert other is not first and torch.equal(other, first)
+            assert first.dtype == torch.int64 and first.tolist() == [base + int(o) * step for o in offsets]
+            assert get() is first
+    finally:
+        plan.close()
+
+
 def test_host_side_checks(inv):
     plan = inv.plan_ragged([3, 70, 5])
     try:
@@ -260,6 +285,9 @@ def test_host_side_checks(inv):
             inv.inv_ragged(plan, a.cpu())                                    # a tensor on another device
         with pytest.raises(ValueError):
             inv.inv_ragged(plan, a.to(torch.float16))
+        buf = torch.zeros(size + 2, dtype=torch.float32, device="cuda")
+        with pytest.raises(ValueError):
+            inv.inv_ragged(plan, buf[:size], out=buf[2:])                    # out over a part of the input
         ptrs = torch.zeros(3, dtype=torch.int64, device="cuda")
         with pytest.raises(ValueError):
             inv.inv_pointers(plan, ptrs, ptrs.to(torch.int32), torch.float32)

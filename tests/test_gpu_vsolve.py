@@ -267,6 +267,45 @@ def test_many_workgroup_members(dll, inv):
     assert torch.equal(x, tile(torch.from_numpy(want_x).cuda(), int(r_off[rest])))   # each value against its mirror
 
 
+@pytest.mark.parametrize("k", [1, 3])
+def test_cached_addresses_equal_computed_ones(inv, k):
+    """``solve_ragged`` takes the member addresses of B and X from the plan's cache: X and the status must equal, bit
+    for bit, those of ``solve_pointers`` on addresses computed here -- on the first call, on a second with the same
+    buffers (a cache hit), after ten calls with ten other outputs (the cache of eight has been cleared), and in
+    place.  Orders on the lane kernels and on the workgroup kernel."""
+    orders = [3, 40, 70, 100]
+    mats = [gate_matrix(n, 9500 + n) for n in orders]
+    ta = torch.from_numpy(pack(mats)[1]).cuda()
+    tb = torch.from_numpy(packed_rhs(orders, k, 9600 + k)).cuda()
+    a_off = np.concatenate(([0], np.cumsum([n * n for n in orders])[:-1]))
+    r_off = row_offsets(orders)[:-1]
+    dev = lambda v: torch.tensor(np.asarray(v), dtype=torch.int64, device="cuda")  # noqa: E731
+    plan = inv.plan_ragged(orders)
+    want = torch.full_like(tb, float("nan"))
+    want_st = inv.solve_pointers(plan, dev(a_off * 4 + ta.data_ptr()), dev(r_off * k * 4 + tb.data_ptr()),
+                                 dev(r_off * k * 4 + want.data_ptr()), torch.float32, k)
+    torch.cuda.synchronize()
+    assert want_st.tolist() == [0] * 4 and not torch.isnan(want).any()
+
+    def same(out, b=tb):
+        x, st = inv.solve_ragged(plan, ta, b, out=out)
+        torch.cuda.synchronize()
+        return x is out and torch.equal(x, want) and torch.equal(st, want_st)
+
+    out = torch.full_like(tb, float("nan"))
+    assert same(out)
+    out.fill_(float("nan"))
+    assert same(out)                                             # the same buffers: a cache hit
+    others = [torch.full_like(tb, float("nan")) for _ in range(10)]
+    assert len({o.data_ptr() for o in others}) == 10
+    assert all(same(o) for o in others)                          # more keys than the cache holds
+    out.fill_(float("nan"))
+    assert same(out)                                             # after the eviction
+    in_place = tb.clone()
+    assert same(in_place, in_place)                              # out is b
+    plan.close()
+
+
 def test_argument_errors(inv):
     orders = [4, 9, 70]
     mats = [np.eye(n, dtype=np.float32) for n in orders]
@@ -291,6 +330,8 @@ def test_argument_errors(inv):
         inv.solve_ragged(plan, flat, b.cpu())                                 # wrong device
     with pytest.raises(ValueError):
         inv.solve_ragged(plan, flat, flat[:166].view(83, 2), out=flat)        # out is a_flat
+    with pytest.raises(ValueError):
+        inv.solve_ragged(plan, flat, b[:, 0].contiguous(), out=flat[2:85])    # out inside a_flat, past its start
     with pytest.raises(ValueError):
         inv.solve_diag_blocks(torch.eye(83, device="cuda"), [4, 9, 69], b)    # orders do not sum to N
     closed = inv.plan_ragged(orders)

@@ -12,9 +12,8 @@ warm-up rounds, then the median of 7, min ... max recorded):
 
 * ``apply``       -- the one call on the stored inverses: ``apply_ragged`` on the packed layout, or
   ``apply_diag_blocks`` on the packed inverses of ``inv_diag_blocks(packed=True)``
-  (the member addresses of r and z come from ``RaggedPlan.row_pointers``, cached after the first call; the solve leg
-  below computes its addresses on the device at every call, two small launches per pointer array, so the host share of
-  the two legs is not like for like -- the kernel times are)
+  (the member addresses of r and z come from ``RaggedPlan.row_pointers``, cached after the first call, as those of
+  the solve leg below do)
 * ``solve``       -- ``solve_ragged`` / ``solve_diag_blocks`` on the matrices themselves, per application: the way until now
 * ``bmm``         -- one ``torch.bmm`` per distinct order on inverses already grouped by order (the sort and the gather
   are done once, outside the timed region)

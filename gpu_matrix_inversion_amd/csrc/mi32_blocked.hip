@@ -114,10 +114,16 @@ struct BlockedWs {
     size_t tstride;     // floats per matrix in pt/gt
     size_t mtstride;    // floats per matrix in mt
     int mtld;           // row stride of mt: every register row of a panel workgroup has a slot (rows >= np too)
-    size_t pt_bstride;  // floats between pt[i] and pt[i + 1]
+    size_t pt_bstride;  // floats between pt[i] and pt[i + 1]: the kernels address the three as one array (PanelExport)
+    size_t ibytes;      // bytes of each index map (submap ... invp)
 };
-static size_t blocked_carve(const BlockedRoute &p, int batch, void *base, BlockedWs &o)
+static size_t blocked_carve(const BlockedRoute &p, int batch, void *base, BlockedWs &o, WsRegions *regions = nullptr)
 {
+    static const char *const kPt[] = {"pt0", "pt1", "pt2"}, *const kGt[] = {"gt0", "gt1"}, *const kMt[] = {"mt0", "mt1"},
+                             *const kAux[] = {"aux0", "aux1"}, *const kUb[] = {"ub0", "ub1"}, *const kXs[] = {"xs0", "xs1"},
+                             *const kMf[] = {"mf0", "mf1"}, *const kSubmap[] = {"submap0", "submap1"},
+                             *const kInvsub[] = {"invsub0", "invsub1"},
+                             *const kRowsrc[] = {"rowsrc0", "rowsrc1", "rowsrc2", "rowsrc3"};
     const size_t mbytes = align256((size_t)p.np * p.ld * sizeof(float));
     const size_t tbytes = align256((size_t)kMaxW * p.np * sizeof(float));
     const size_t ibytes = align256((size_t)p.np * sizeof(int) * batch);
@@ -128,34 +134,40 @@ static size_t blocked_carve(const BlockedRoute &p, int batch, void *base, Blocke
     const size_t mfbytes = align256((size_t)p.np * p.bw * sizeof(float));
     o.mstride = mbytes / sizeof(float);
     o.tstride = tbytes / sizeof(float);
-    o.pt_bstride = tbytes * batch / sizeof(float);
     o.mtstride = mtbytes / sizeof(float);
     o.mtld = mtld;
     o.gkstride = gkbytes / sizeof(float);
     o.mfstride = mfbytes / sizeof(float);
-    WsCarver c(base);
-    o.m0 = c.take<float>(mbytes * batch);
-    o.m1 = c.take<float>(mbytes * batch);
-    for (auto &r : o.pt) r = c.take<float>(tbytes * batch);
-    for (auto &r : o.gt) r = c.take<float>(tbytes * batch);
-    for (auto &r : o.mt) r = c.take<float>(mtbytes * batch);
-    for (auto &r : o.aux) r = c.take<float>(abytes);
-    o.xch = c.take<unsigned long long>(align256((size_t)kXchGranules * sizeof(unsigned long long) * batch));
-    o.gk = c.take<float>(gkbytes * batch);
+    o.ibytes = ibytes;
+    WsCarver c(base, regions);
+    o.m0 = c.take<float>(mbytes * batch, WS_VALUES, "m0");
+    o.m1 = c.take<float>(mbytes * batch, WS_VALUES, "m1");
+    for (int i = 0; i < 3; ++i) o.pt[i] = c.take<float>(tbytes * batch, WS_VALUES, kPt[i]);
+    // what lies between two of them, a red zone of the guard mode included: the carver's own step
+    o.pt_bstride = (tbytes * batch + c.guard) / sizeof(float);
+    for (int i = 0; i < 2; ++i) o.gt[i] = c.take<float>(tbytes * batch, WS_VALUES, kGt[i]);
+    for (int i = 0; i < 2; ++i) o.mt[i] = c.take<float>(mtbytes * batch, WS_VALUES, kMt[i]);
+    for (int i = 0; i < 2; ++i) o.aux[i] = c.take<float>(abytes, WS_VALUES, kAux[i]);
+    o.xch = c.take<unsigned long long>(align256((size_t)kXchGranules * sizeof(unsigned long long) * batch), WS_RECORDS, "xch");
+    o.gk = c.take<float>(gkbytes * batch, WS_VALUES, "gk");
     for (int i = 0; i < 2; ++i) {
-        o.ub[i] = c.take<float>(gkbytes * batch);
-        o.xs[i] = c.take<float>(gkbytes * batch);
+        o.ub[i] = c.take<float>(gkbytes * batch, WS_VALUES, kUb[i]);
+        o.xs[i] = c.take<float>(gkbytes * batch, WS_VALUES, kXs[i]);
     }
-    o.xst = c.take<float>(gkbytes * batch);
-    for (auto &r : o.mf) r = c.take<float>(mfbytes * batch);
-    for (auto &r : o.submap) r = c.take<int>(ibytes);
-    for (auto &r : o.invsub) r = c.take<int>(ibytes);
-    for (auto &r : o.rowsrc) r = c.take<int>(ibytes);
-    o.orig = c.take<int>(ibytes);
-    o.invp = c.take<int>(ibytes);
+    o.xst = c.take<float>(gkbytes * batch, WS_VALUES, "xst");
+    for (int i = 0; i < 2; ++i) o.mf[i] = c.take<float>(mfbytes * batch, WS_VALUES, kMf[i]);
+    for (int i = 0; i < 2; ++i) o.submap[i] = c.take<int>(ibytes, WS_INDICES, kSubmap[i]);
+    for (int i = 0; i < 2; ++i) o.invsub[i] = c.take<int>(ibytes, WS_INDICES, kInvsub[i]);
+    for (int i = 0; i < 4; ++i) o.rowsrc[i] = c.take<int>(ibytes, WS_INDICES, kRowsrc[i]);
+    o.orig = c.take<int>(ibytes, WS_INDICES, "orig");
+    o.invp = c.take<int>(ibytes, WS_INDICES, "invp");
     return c.off;
 }
-size_t blocked_workspace_bytes(const BlockedRoute &r, int batch) { BlockedWs ws; return blocked_carve(r, batch, nullptr, ws); }
+size_t blocked_workspace_bytes(const BlockedRoute &r, int batch, WsRegions *regions)
+{
+    BlockedWs ws;
+    return blocked_carve(r, batch, nullptr, ws, regions);
+}
 
 // ---- init: A -> diag(I, A) in the first working copy (makeAugmentedMatrix counterpart,
 //      mat_inv_32.cpp:177-192) + the compact copies of the first two sub-panels' columns ------
@@ -279,9 +291,15 @@ hipError_t blocked_invert(const BlockedRoute &p, int part, const float *d_a, flo
         // but where the strip(t) tiles ride in the panel launches they still run for it (ostrip_body: the 256-thread
         // groups of a workgroup share its barriers; computed, not stored) and address its rows THROUGH submap and
         // rowsrc.  Whatever an earlier call or another owner left in the workspace must not reach them: 0 is a valid
-        // position.  (submap, invsub and rowsrc are carved in one run, in front of orig, which the init kernel wrote.)
-        if ((e = hipMemsetAsync(ws.submap[0], 0, (size_t)((char *)ws.orig - (char *)ws.submap[0]), stream)) != hipSuccess)
-            return e;
+        // position.  The eight maps, ws.ibytes each (orig is the init kernel's): one memset per run of maps that lie side
+        // by side -- all eight as they are carved, one each with the guard mode's red zones between them.
+        int *const maps[] = {ws.submap[0], ws.submap[1], ws.invsub[0], ws.invsub[1],
+                             ws.rowsrc[0], ws.rowsrc[1], ws.rowsrc[2], ws.rowsrc[3]};
+        const size_t nmaps = sizeof(maps) / sizeof(maps[0]);
+        for (size_t i = 0, j; i < nmaps; i = j) {
+            for (j = i + 1; j < nmaps && (char *)maps[j] == (char *)maps[j - 1] + ws.ibytes; ++j) {}
+            if ((e = hipMemsetAsync(maps[i], 0, ws.ibytes * (j - i), stream)) != hipSuccess) return e;
+        }
     }
     const bool strips_at_end = p.part_strips_at_end[part];  // else the strip(t) tiles ride in the panel launches
     // what every sub-panel launch shares

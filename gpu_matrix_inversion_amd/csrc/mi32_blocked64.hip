@@ -56,23 +56,27 @@ struct B64Ws {
     int *orig, *invp, *rowmap;
     size_t wstride;
 };
-static size_t b64_carve(const Blocked64Plan &p, int batch, void *base, B64Ws &o)
+static size_t b64_carve(const Blocked64Plan &p, int batch, void *base, B64Ws &o, WsRegions *regions = nullptr)
 {
     const size_t wbytes = align256((size_t)p.np * p.ld * sizeof(double));
     const size_t kbytes = align256((size_t)p.row_tiles * sizeof(PivotRec<double>) * batch);
     const size_t ibytes = align256((size_t)p.np * sizeof(int) * batch);
-    WsCarver c(base);
+    WsCarver c(base, regions);
     o.wstride = wbytes / sizeof(double);
-    o.w0 = c.take<double>(wbytes * batch);
-    o.w1 = c.take<double>(wbytes * batch);
-    o.k0 = c.take<PivotRec<double>>(kbytes);
-    o.k1 = c.take<PivotRec<double>>(kbytes);
-    o.orig = c.take<int>(ibytes);
-    o.invp = c.take<int>(ibytes);
-    o.rowmap = c.take<int>(ibytes);
+    o.w0 = c.take<double>(wbytes * batch, WS_VALUES, "w0");
+    o.w1 = c.take<double>(wbytes * batch, WS_VALUES, "w1");
+    o.k0 = c.take<PivotRec<double>>(kbytes, WS_RECORDS, "k0");
+    o.k1 = c.take<PivotRec<double>>(kbytes, WS_RECORDS, "k1");
+    o.orig = c.take<int>(ibytes, WS_INDICES, "orig");
+    o.invp = c.take<int>(ibytes, WS_INDICES, "invp");
+    o.rowmap = c.take<int>(ibytes, WS_INDICES, "rowmap");
     return c.off;
 }
-size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch) { B64Ws ws; return b64_carve(p, batch, nullptr, ws); }
+size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch, WsRegions *regions)
+{
+    B64Ws ws;
+    return b64_carve(p, batch, nullptr, ws, regions);
+}
 
 // ---- makeAugmented counterpart: A -> diag(A, I) in the first working copy --------------------
 // pad: where the matrix starts in the working copy -- 0 here (the padding lies behind it), np - n on the no-pivot path

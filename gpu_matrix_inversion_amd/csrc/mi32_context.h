@@ -61,6 +61,44 @@ struct DeviceBuffer {
 
 void host_copier_destroy(HostCopier *c);
 
+// ---- the diagnostic guard mode of the workspace (off unless a test called mi32_debug_ws_guard) -------------------------
+// One carve a call makes: whose it is, where it starts in its buffer, and its regions in order (offsets from `base`).
+struct WsCarve {
+    enum Owner { INVERSE = 0, DET = 1, RESIDUAL = 2 };
+    int owner;
+    int part;     // 0 / 1 for the halves of a split batch
+    size_t base;  // bytes into the buffer: the workspace, or (DET) the det memory
+    size_t bytes;
+    mi32::WsRegions regions;
+};
+// A red zone armed by the last guarded call on a context: bytes [off, off + bytes) of its buffer hold `pattern` in
+// every 32-bit word.  region: index into the carve's regions of the region in front of the zone, -1 for the leading one
+// (which is named after the first region).
+struct WsZone {
+    int owner, part, region;
+    const char *name;
+    size_t off, bytes;
+    uint32_t pattern;
+};
+// the poison of the value regions and of the zones behind them: a quiet NaN as a float, and two of it as a double
+static constexpr uint32_t kWsPoison = 0x7FF8DEADu;
+// What the tests-only entry points mi32_debug_ws_layout and mi32_debug_ws_check fill (like mi32_debug_dense_route they
+// are not part of include/mat_inv_32_c.h; tests/workspace_cases.py mirrors the two structs).
+struct mi32_debug_ws_region {
+    int owner, part, kind, reserved;  // WsCarve::Owner, 0 / 1, mi32::WsKind
+    size_t offset, bytes;             // offset: from the start of the buffer (the det memory for owner 1, else the workspace)
+    char name[16];
+};
+struct mi32_debug_ws_report {
+    int checked, damaged;  // zones compared with their pattern / that differ from it
+    // the first damaged zone (all zero and an empty name while damaged == 0): its index among the zones of the call, its
+    // carve, the region it lies behind (the first region for a leading zone)
+    int zone, owner, part, reserved;
+    long long offset;      // of the first changed byte from that region's end; from its start, negative, in a leading zone
+    size_t bytes;          // changed bytes in that zone
+    char name[16];
+};
+
 struct mi32_context {
     int device = 0;
     Settings set;
@@ -81,6 +119,7 @@ struct mi32_context {
     DeviceBuffer d_istatus;
     // det calls above order 128 (mi32_inv_det_any_device*): the recorded pivots, the parity and input-flag words
     DeviceBuffer det;
+    std::vector<WsZone> zones;  // guard mode: what the last call armed (mi32_debug_ws_check)
     std::mutex mu;
 };
 inline Settings settings_of(const mi32_context *h) { return h ? h->set : Settings(); }
@@ -114,8 +153,8 @@ struct DenseRoute {
         mi32::Blocked64Plan blocked64;
         mi32::NoPivot64Plan nopivot64;
     };
-    // The path's *_workspace_bytes of the plan above.  fp32: at least the residual check's share; BLOCKED32: the larger
-    // of the whole batch and the two halves of a split, reserved whether or not this call splits.
+    // The path's *_workspace_bytes of the plan above.  fp32: at least the residual check's share; BLOCKED32: the whole
+    // batch, or the two halves of a split one (the same number of bytes unless the guard mode adds red zones).
     size_t ws_bytes;
     int det_steps;  // entries of a member's pivot list: the padded step count (0: the one-launch kernels keep no list)
     int det_first;  // the first real step: BLOCKED32 and NOPIVOT64 pad in front of the matrix, BLOCKED64 behind it
@@ -124,6 +163,14 @@ struct DenseRoute {
 // h: the streams a context offers (null: a fresh context's); they reach no field but the blocked fp32 route's look-ahead
 // and parts
 DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batch, size_t elem_bytes);
+// The carves a call on this route makes, by the size-only passes of the carves themselves: the path's (both parts of a
+// split batch; none on the one-launch paths) and, with det, the det memory's.
+std::vector<WsCarve> dense_carves(const DenseRoute &d, int batch, size_t elem_bytes, bool det);
+WsCarve residual_carve_of(int n, int batch);
+// Guard mode only (g_ws_guard != 0), after the buffers were ensured: waits for the context's streams, fills every value
+// region and every zone behind one with kWsPoison and every other zone with zero, on the main stream, waits for that,
+// and remembers the zones.  The index and record regions are left as they are.
+int guard_arm(mi32_context *h, const std::vector<WsCarve> &carves);
 void lookahead_geometry(int cus, int n, int *workgroups, bool *exclusive);
 
 // An instance of the one-launch kernels: register-resident with `lanes` per member (8 ... 64), or workgroup-resident

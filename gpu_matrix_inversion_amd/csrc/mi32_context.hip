@@ -5,6 +5,7 @@
 // queue, six JIT-built programs and four buffers on every call (:238-290, 1.44 s
 // of its 4.37 s at N=4096) and tears them down again (:388), this keeps one
 // AOT-compiled code object, one stream and one grow-only workspace per context.
+#include <cstring>
 #include <new>
 #include <vector>
 
@@ -119,6 +120,40 @@ int zeroed_status_buffer(mi32_context *h, int *d_status, int batch, int **out)
 {
     MI32_TRY(status_buffer(h, d_status, batch, out));
     MI32_HIP(hipMemsetAsync(*out, 0, sizeof(int) * (size_t)batch, h->stream));  // MI32_OK
+    return MI32_OK;
+}
+
+// ---- the diagnostic guard mode ------------------------------------------------------------------------------------------
+static DeviceBuffer &zone_buffer(mi32_context *h, int owner) { return owner == WsCarve::DET ? h->det : h->ws; }
+
+int guard_arm(mi32_context *h, const std::vector<WsCarve> &carves)
+{
+    const size_t G = g_ws_guard.load();
+    h->zones.clear();
+    if (G == 0) return MI32_OK;
+    MI32_TRY(sync_all_streams(h));  // whatever an earlier call still does in the workspace
+    const auto fill = [&](char *p, size_t bytes, uint32_t pattern) {
+        return hip_status(hipMemsetD32Async((hipDeviceptr_t)p, (int)pattern, bytes / sizeof(uint32_t), h->stream), "guard fill");
+    };
+    const auto pattern_of = [](const WsRegion &r) { return r.kind == WS_VALUES ? kWsPoison : 0u; };
+    for (const WsCarve &c : carves) {
+        DeviceBuffer &buf = zone_buffer(h, c.owner);
+        if (c.regions.empty() || c.base + c.bytes > buf.bytes) {
+            g_last_error = "guard mode: a carve does not fit its buffer";
+            return MI32_RUNTIME_ERROR;
+        }
+        char *base = (char *)buf.ptr + c.base;
+        const WsRegion &first = c.regions.front();
+        MI32_TRY(fill(base + first.off - G, G, pattern_of(first)));
+        h->zones.push_back(WsZone{c.owner, c.part, -1, first.name, c.base + first.off - G, G, pattern_of(first)});
+        for (size_t i = 0; i < c.regions.size(); ++i) {
+            const WsRegion &r = c.regions[i];
+            if (r.kind == WS_VALUES) MI32_TRY(fill(base + r.off, r.bytes, kWsPoison));
+            MI32_TRY(fill(base + r.off + r.bytes, G, pattern_of(r)));
+            h->zones.push_back(WsZone{c.owner, c.part, (int)i, r.name, c.base + r.off + r.bytes, G, pattern_of(r)});
+        }
+    }
+    MI32_HIP(hipStreamSynchronize(h->stream));  // the route's other streams start behind the fills too
     return MI32_OK;
 }
 
@@ -252,6 +287,62 @@ int mi32_reserve(mi32_handle_t h, int n, int batch)
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     return h->ws.ensure(h, dense_route(h, h->set, n, batch, sizeof(float)).ws_bytes);
+}
+
+// tests only: waits for the context's streams, then compares every red zone the LAST call on h armed with its pattern
+// (one copy per zone, of the zone alone).  A call made with the guard off, or on a one-launch route, armed none.
+int mi32_debug_ws_check(mi32_handle_t h, mi32_debug_ws_report *report)
+{
+    if (!h || !report) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    MI32_TRY(sync_all_streams(h));
+    *report = mi32_debug_ws_report{};
+    std::vector<uint32_t> host;
+    for (size_t z = 0; z < h->zones.size(); ++z) {
+        const WsZone &zn = h->zones[z];
+        const DeviceBuffer &buf = zone_buffer(h, zn.owner);
+        if (zn.off + zn.bytes > buf.bytes) return MI32_BAD_SHAPE;  // the buffer was grown since: the zones are gone
+        host.resize(zn.bytes / sizeof(uint32_t));
+        MI32_HIP(hipMemcpy(host.data(), (const char *)buf.ptr + zn.off, zn.bytes, hipMemcpyDeviceToHost));
+        ++report->checked;
+        size_t changed = 0, first = zn.bytes;
+        const unsigned char *got = reinterpret_cast<const unsigned char *>(host.data());
+        const unsigned char *want = reinterpret_cast<const unsigned char *>(&zn.pattern);
+        for (size_t i = 0; i < zn.bytes; ++i)
+            if (got[i] != want[i % sizeof(uint32_t)]) {
+                if (changed++ == 0) first = i;
+            }
+        if (changed == 0) continue;
+        if (report->damaged++ == 0) {
+            report->zone = (int)z;
+            report->owner = zn.owner;
+            report->part = zn.part;
+            report->offset = zn.region < 0 ? (long long)first - (long long)zn.bytes : (long long)first;
+            report->bytes = changed;
+            std::strncpy(report->name, zn.name, sizeof(report->name) - 1);
+        }
+    }
+    return MI32_OK;
+}
+
+// tests only: stores one 32-bit word `byte_offset` bytes into red zone `zone` of the last call, so that the checker can
+// be shown to notice damage.  Any offset that is not a whole word inside that zone is refused.
+int mi32_debug_ws_poke(mi32_handle_t h, int zone, long long byte_offset, unsigned value)
+{
+    if (!h) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (zone < 0 || (size_t)zone >= h->zones.size()) return MI32_BAD_SHAPE;
+    const WsZone &zn = h->zones[(size_t)zone];
+    const DeviceBuffer &buf = zone_buffer(h, zn.owner);
+    if (byte_offset < 0 || byte_offset % 4 != 0 || (unsigned long long)byte_offset + sizeof(uint32_t) > zn.bytes ||
+        zn.off + zn.bytes > buf.bytes)
+        return MI32_BAD_SHAPE;
+    MI32_HIP(hipSetDevice(h->device));
+    MI32_TRY(sync_all_streams(h));
+    const uint32_t word = value;
+    MI32_HIP(hipMemcpy((char *)buf.ptr + zn.off + (size_t)byte_offset, &word, sizeof(word), hipMemcpyHostToDevice));
+    return MI32_OK;
 }
 
 int mi32_set_profiling(mi32_handle_t h, int enable)

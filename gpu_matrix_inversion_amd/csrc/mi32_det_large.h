@@ -36,13 +36,16 @@ template <typename T>
 void launch_det_finish(const T *piv, size_t pstride, int first, int n, const int *parity, const int *flag,
                        const int *status, bool pivoting, DetOut det, int batch, hipStream_t stream);
 
-// bytes of the context's det memory for `batch` lists of `np` elements: [flag][parity][piv]
-size_t det_bytes(int np, int batch, size_t elem_bytes);
+// The context's det memory for `batch` lists of `np` elements: [flag][parity][piv], carved like a workspace (WsCarver).
 struct DetMem {
     int *flag, *parity;
     void *piv;
     size_t pstride;
+    size_t wbytes;  // bytes of flag and of parity, each
+    size_t bytes;   // of the whole carve
 };
-DetMem det_carve(void *base, int np, int batch, size_t elem_bytes);
+DetMem det_carve(void *base, int np, int batch, size_t elem_bytes, WsRegions *regions = nullptr);
+// the size-only pass of det_carve
+size_t det_bytes(int np, int batch, size_t elem_bytes, WsRegions *regions = nullptr);
 
 }  // namespace mi32

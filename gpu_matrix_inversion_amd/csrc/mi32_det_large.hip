@@ -5,20 +5,22 @@
 
 namespace mi32 {
 
-size_t det_bytes(int np, int batch, size_t elem_bytes)
+DetMem det_carve(void *base, int np, int batch, size_t elem_bytes, WsRegions *regions)
 {
-    return 2 * align256(sizeof(int) * (size_t)batch) + align256((size_t)np * elem_bytes) * batch;
-}
-DetMem det_carve(void *base, int np, int batch, size_t elem_bytes)
-{
-    WsCarver c(base);
+    WsCarver c(base, regions);
     DetMem m;
-    m.flag = c.take<int>(align256(sizeof(int) * (size_t)batch));
-    m.parity = c.take<int>(align256(sizeof(int) * (size_t)batch));
+    m.wbytes = align256(sizeof(int) * (size_t)batch);
+    m.flag = c.take<int>(m.wbytes, WS_RECORDS, "flag");
+    m.parity = c.take<int>(m.wbytes, WS_RECORDS, "parity");
     const size_t pbytes = align256((size_t)np * elem_bytes);
-    m.piv = c.take<void>(pbytes * batch);
+    m.piv = c.take<void>(pbytes * batch, WS_VALUES, "piv");
     m.pstride = pbytes / elem_bytes;
+    m.bytes = c.off;
     return m;
+}
+size_t det_bytes(int np, int batch, size_t elem_bytes, WsRegions *regions)
+{
+    return det_carve(nullptr, np, batch, elem_bytes, regions).bytes;
 }
 
 // ---- a non-finite input entry --------------------------------------------------------------------------------------

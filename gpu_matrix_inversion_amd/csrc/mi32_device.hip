@@ -77,7 +77,14 @@ static int det_begin(mi32_context *h, const T *d_a, int n, int np, int batch, De
 {
     MI32_TRY(h->det.ensure(h, det_bytes(np, batch, sizeof(T))));
     *dm = det_carve(h->det.ptr, np, batch, sizeof(T));
-    MI32_HIP(hipMemsetAsync(dm->flag, 0, (size_t)((char *)dm->piv - (char *)dm->flag), h->stream));
+    // the flag and the parity words: one memset while the two regions lie side by side, one each with the guard mode's
+    // red zone between them
+    if ((char *)dm->parity == (char *)dm->flag + dm->wbytes) {
+        MI32_HIP(hipMemsetAsync(dm->flag, 0, 2 * dm->wbytes, h->stream));
+    } else {
+        MI32_HIP(hipMemsetAsync(dm->flag, 0, dm->wbytes, h->stream));
+        MI32_HIP(hipMemsetAsync(dm->parity, 0, dm->wbytes, h->stream));
+    }
     ProfScope ps(h->prof, KC_FINISH, h->stream);
     launch_det_scan(d_a, n, batch, dm->flag, h->stream);
     *rec = DetRec{dm->piv, dm->pstride, dm->parity};
@@ -102,6 +109,12 @@ int inv_device(mi32_context *h, Settings s, const T *d_a, int n, int batch, T *d
     MI32_HIP(hipSetDevice(h->device));
     const DenseRoute dr = dense_route(h, s, n, batch, sizeof(T));
     MI32_TRY(h->ws.ensure(h, dr.ws_bytes));
+    if (g_ws_guard.load(std::memory_order_relaxed) != 0 || !h->zones.empty()) {
+        // the diagnostic guard mode: poison and red zones for every carve of this call, before its first launch (a
+        // one-launch call carves nothing: it only forgets the zones of the call before)
+        if (!det.empty() && !dr.one_launch()) MI32_TRY(h->det.ensure(h, det_bytes(dr.det_steps, batch, sizeof(T))));
+        MI32_TRY(guard_arm(h, dense_carves(dr, batch, sizeof(T), !det.empty())));
+    }
     if (dr.one_launch()) return one_launch_device(h, s.pivoting, d_a, n, batch, d_inv, d_status, det);
     MI32_TRY(status_buffer(h, d_status, batch, &d_status));
     DetMem dm;
@@ -411,6 +424,8 @@ int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, in
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     MI32_TRY(h->ws.ensure(h, dense_route(h, h->set, n, batch, sizeof(float)).ws_bytes));
+    if (g_ws_guard.load(std::memory_order_relaxed) != 0 || !h->zones.empty())  // the diagnostic guard mode
+        MI32_TRY(guard_arm(h, {residual_carve_of(n, batch)}));
     return hip_status(residual_launch(d_a, d_x, n, batch, d_out, h->ws.ptr, h->stream), "residual launch");
 }
 

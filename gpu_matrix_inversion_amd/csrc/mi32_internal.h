@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <type_traits>
+#include <vector>
 
 #include "mat_inv_32_c.h"
 
@@ -75,17 +77,39 @@ struct ProfScope {
 // ---- workspace carving ----------------------------------------------------------
 // Every workspace region starts on a 256-byte boundary.
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// What a region holds.  The diagnostic guard mode ("Ordering and workspace contract") poisons the VALUES
+// regions and leaves the other two as they are: a poisoned index would turn a stale-map read into a wild address.
+enum WsKind {
+    WS_VALUES = 0,   // float or double working data
+    WS_INDICES = 1,  // row maps (int)
+    WS_RECORDS = 2   // arg-max records, exchange granules, flags, parity
+};
+struct WsRegion {
+    const char *name;  // a string literal
+    size_t off, bytes;
+    int kind;
+};
+typedef std::vector<WsRegion> WsRegions;
+// The guard size G in bytes, a multiple of 256; 0: the mode is off (always, unless a test called mi32_debug_ws_guard).
+// Process-wide, and read by WsCarver alone: the size-only pass and the address pass of a carve cannot disagree.
+extern std::atomic<size_t> g_ws_guard;  // mi32_plan.hip
 // Bump allocator over one workspace.  Without a base pointer it only adds up the region sizes (the
-// *_workspace_bytes functions); with one it also hands out each region's address.
+// *_workspace_bytes functions); with one it also hands out each region's address.  With a guard size G, one red zone
+// of G bytes lies in front of the first region and one behind every region.  `log` (may be null) takes the regions in
+// carve order.
 struct WsCarver {
     char *base;
-    size_t off = 0;
-    explicit WsCarver(void *b) : base((char *)b) {}
+    size_t guard;
+    size_t off;
+    WsRegions *log;
+    explicit WsCarver(void *b, WsRegions *l = nullptr)
+        : base((char *)b), guard(g_ws_guard.load(std::memory_order_relaxed)), off(guard), log(l) {}
     template <typename P>
-    P *take(size_t bytes)
+    P *take(size_t bytes, WsKind kind, const char *name)
     {
         P *p = base ? (P *)(base + off) : nullptr;
-        off += bytes;
+        if (log) log->push_back(WsRegion{name, off, bytes, (int)kind});
+        off += bytes + guard;
         return p;
     }
 };
@@ -212,8 +236,10 @@ struct DetRec {
 
 SweepPlan make_sweep_plan(int n);
 
-size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes);
-size_t blocked_workspace_bytes(const BlockedRoute &r, int batch);  // of `batch` members (a whole call, or one part)
+// The size-only pass of each path's carve; regions (may be null) takes the carve's regions in order.
+size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes, WsRegions *regions = nullptr);
+// of `batch` members (a whole call, or one part)
+size_t blocked_workspace_bytes(const BlockedRoute &r, int batch, WsRegions *regions = nullptr);
 
 // Enqueue a whole inversion on `stream`.  ws: workspace of at least the size
 // reported above, 256-byte aligned.
@@ -230,7 +256,7 @@ struct Blocked64Plan {
     int row_tiles;  // workgroups per step launch = arg-max records per column
 };
 Blocked64Plan make_blocked64_plan(int n, int bw);
-size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch);
+size_t blocked64_workspace_bytes(const Blocked64Plan &p, int batch, WsRegions *regions = nullptr);
 hipError_t blocked64_invert(const Blocked64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
                             hipStream_t stream, Profiler *prof, const DetRec &det = DetRec());
 // makeAugmented counterpart of the fp64 blocked paths: w0 <- diag(A, I) with pad = 0 (the pivoted path) or diag(I, A)
@@ -246,7 +272,7 @@ struct NoPivot64Plan {
     int bw;         // block width: 64 (default) or 128
 };
 NoPivot64Plan make_nopivot64_plan(int n, int bw);
-size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch);
+size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch, WsRegions *regions = nullptr);
 hipError_t nopivot64_invert(const NoPivot64Plan &p, const double *d_a, double *d_inv, int batch, int *d_status, void *ws,
                             hipStream_t stream, Profiler *prof, const DetRec &det = DetRec());
 
@@ -468,7 +494,7 @@ void launch_unpermute(const T *w, int ld, size_t wstride, const int *orig, int *
                       hipStream_t stream);
 hipError_t residual_launch(const float *d_a, const float *d_x, int n, int batch, double *d_out, void *ws,
                            hipStream_t stream);
-size_t residual_workspace_bytes(int n, int batch);
+size_t residual_workspace_bytes(int n, int batch, WsRegions *regions = nullptr);
 hipError_t frobenius_launch_f64(const double *d_a, const double *d_b, int n, double *d_out, void *ws, hipStream_t stream);
 
 }  // namespace mi32

@@ -54,23 +54,27 @@ struct NP64Ws {
     int *orig, *invp;
     size_t wstride, fstride;
 };
-static size_t np64_carve(const NoPivot64Plan &p, int batch, void *base, NP64Ws &o)
+static size_t np64_carve(const NoPivot64Plan &p, int batch, void *base, NP64Ws &o, WsRegions *regions = nullptr)
 {
     const size_t wbytes = align256((size_t)p.np * p.ld * sizeof(double));
     const size_t fbytes = align256((size_t)p.bw * p.np * sizeof(double));
     const size_t ibytes = align256((size_t)p.np * sizeof(int) * batch);
-    WsCarver c(base);
+    WsCarver c(base, regions);
     o.wstride = wbytes / sizeof(double);
     o.fstride = fbytes / sizeof(double);
-    o.w = c.take<double>(wbytes * batch);
-    o.ft = c.take<double>(fbytes * batch);   // -f_m[i], [m][i] (k-major): A operand of the rank-bw update
-    o.ub = c.take<double>(fbytes * batch);   // U[m][j], [m][j]: B operand
-    o.piv = c.take<double>(align256((size_t)p.bw * sizeof(double) * batch));
-    o.orig = c.take<int>(ibytes);
-    o.invp = c.take<int>(ibytes);
+    o.w = c.take<double>(wbytes * batch, WS_VALUES, "w");
+    o.ft = c.take<double>(fbytes * batch, WS_VALUES, "ft");   // -f_m[i], [m][i] (k-major): A operand of the rank-bw update
+    o.ub = c.take<double>(fbytes * batch, WS_VALUES, "ub");   // U[m][j], [m][j]: B operand
+    o.piv = c.take<double>(align256((size_t)p.bw * sizeof(double) * batch), WS_VALUES, "piv");
+    o.orig = c.take<int>(ibytes, WS_INDICES, "orig");
+    o.invp = c.take<int>(ibytes, WS_INDICES, "invp");
     return c.off;
 }
-size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch) { NP64Ws ws; return np64_carve(p, batch, nullptr, ws); }
+size_t nopivot64_workspace_bytes(const NoPivot64Plan &p, int batch, WsRegions *regions)
+{
+    NP64Ws ws;
+    return np64_carve(p, batch, nullptr, ws, regions);
+}
 
 __device__ __forceinline__ double np64_readlane(double v, int lane)
 {

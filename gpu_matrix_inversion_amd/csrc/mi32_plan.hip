@@ -3,8 +3,11 @@
 // shape, no HIP runtime call and no context -- the mi32_resolve_* entry points answer with what a call would do.
 // A dense call is planned once: dense_route composes the rules below into the DenseRoute (mi32_context.h) that the
 // device entry, the workspace queries and mi32_resolve_blocking_f64 all read.
+#include <cstring>
+
 #include "mi32_apply.h"
 #include "mi32_context.h"
+#include "mi32_det_large.h"
 
 using namespace mi32;
 
@@ -163,9 +166,11 @@ DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batc
         // blocked_carve reads np, ld and bw only, and plan_route derives none of the three from the streams offered
         // (those reach `lookahead` and the parts): the route the call runs also sizes the workspace of any context
         const BlockedRoute &r = d.blocked = route_of(h, s, n, batch);
-        // a batch that may be split in two halves carves one workspace per half -- reserved whether or not this call splits
-        const size_t halves = blocked_workspace_bytes(r, (batch + 1) / 2) + blocked_workspace_bytes(r, batch - (batch + 1) / 2);
+        // A split batch carves one workspace per half, the second where the first ends.  Every region is a whole number
+        // of 256-byte units per member, so the two halves need exactly what the whole batch needs -- a context that
+        // never splits reserves the same -- until the guard mode gives each carve its own red zones.
         const size_t whole = blocked_workspace_bytes(r, batch);
+        const size_t halves = r.parts == 2 ? blocked_workspace_bytes(r, r.part_batch[0]) + blocked_workspace_bytes(r, r.part_batch[1]) : 0;
         d.ws_bytes = whole > halves ? whole : halves;
         d.det_steps = r.np;
         d.det_first = r.np - n;  // the identity padding comes first on this path: its steps are skipped by index
@@ -186,6 +191,47 @@ DenseRoute dense_route(const mi32_context *h, const Settings &s, int n, int batc
         if (res > d.ws_bytes) d.ws_bytes = res;
     }
     return d;
+}
+
+// ---- the workspace layout, for the diagnostic guard mode ------------------------------------------------------------------
+std::atomic<size_t> mi32::g_ws_guard{0};
+
+std::vector<WsCarve> dense_carves(const DenseRoute &d, int batch, size_t elem_bytes, bool det)
+{
+    std::vector<WsCarve> out;
+    const auto add = [&](int owner, int part, size_t base, auto size_pass) {
+        out.push_back(WsCarve{owner, part, base, 0, {}});
+        out.back().bytes = size_pass(&out.back().regions);
+    };
+    switch (d.path) {
+        case DenseRoute::SWEEP:
+            add(WsCarve::INVERSE, 0, 0, [&](WsRegions *r) { return sweep_workspace_bytes(d.sweep, batch, elem_bytes, r); });
+            break;
+        case DenseRoute::BLOCKED32:
+            // the second part's carve starts where the first part's ends (blocked_invert_split, mi32_device.hip)
+            for (int part = 0; part < d.blocked.parts; ++part)
+                add(WsCarve::INVERSE, part, part ? out[0].bytes : 0,
+                    [&](WsRegions *r) { return blocked_workspace_bytes(d.blocked, d.blocked.part_batch[part], r); });
+            break;
+        case DenseRoute::BLOCKED64:
+            add(WsCarve::INVERSE, 0, 0, [&](WsRegions *r) { return blocked64_workspace_bytes(d.blocked64, batch, r); });
+            break;
+        case DenseRoute::NOPIVOT64:
+            add(WsCarve::INVERSE, 0, 0, [&](WsRegions *r) { return nopivot64_workspace_bytes(d.nopivot64, batch, r); });
+            break;
+        case DenseRoute::RESIDENT:
+        case DenseRoute::WORKGROUP:
+        case DenseRoute::WIDE: return out;  // the one-launch kernels carve nothing and keep no pivot list
+    }
+    if (det) add(WsCarve::DET, 0, 0, [&](WsRegions *r) { return det_bytes(d.det_steps, batch, elem_bytes, r); });
+    return out;
+}
+
+WsCarve residual_carve_of(int n, int batch)
+{
+    WsCarve c{WsCarve::RESIDUAL, 0, 0, 0, {}};
+    c.bytes = residual_workspace_bytes(n, batch, &c.regions);
+    return c;
 }
 
 // The look-ahead half of a single large matrix (blocked_invert): how many CUs it runs on and whether it shares them.
@@ -426,6 +472,41 @@ int mi32_debug_dense_route(mi32_handle_t h, int n, int batch, int elem_bytes, in
     out[4] = d.path == DenseRoute::BLOCKED32 ? d.blocked.bw : d.path == DenseRoute::BLOCKED64 ? d.blocked64.bw
              : d.path == DenseRoute::NOPIVOT64 ? d.nopivot64.bw : 0;
     if (ws_bytes) *ws_bytes = d.ws_bytes;
+    return MI32_OK;
+}
+
+// tests only: the guard size G of the workspace's diagnostic guard mode, rounded up to a multiple of 256; 0 switches
+// the mode off.  Process-wide: every size query and every carve from now on reads it.
+int mi32_debug_ws_guard(size_t bytes)
+{
+    g_ws_guard.store(align256(bytes));
+    return MI32_OK;
+}
+
+// tests only: the regions of the carves the dense calls of this shape make on this context (null: a fresh one's), in
+// carve order: the inversion's (owner 0; both parts of a split batch; none on the one-launch routes), the det memory's
+// of mi32_inv_det_any_device* (owner 1; none on the one-launch routes) and, for fp32, the residual verifier's (owner 2).
+// offset: bytes from the start of the buffer, which is the det memory for owner 1 and the workspace otherwise.  Up to
+// `capacity` entries are written; *count is the number there are.
+int mi32_debug_ws_layout(mi32_handle_t h, int n, int batch, int elem_bytes, mi32_debug_ws_region *regions, int capacity,
+                         int *count)
+{
+    if (n <= 0 || batch <= 0 || (elem_bytes != 4 && elem_bytes != 8) || !count || capacity < 0 || (capacity > 0 && !regions))
+        return MI32_BAD_SHAPE;
+    const DenseRoute d = dense_route(h, settings_of(h), n, batch, (size_t)elem_bytes);
+    std::vector<WsCarve> carves = dense_carves(d, batch, (size_t)elem_bytes, true);
+    if (elem_bytes == 4) carves.push_back(residual_carve_of(n, batch));
+    int total = 0;
+    for (const WsCarve &c : carves)
+        for (const WsRegion &r : c.regions) {
+            if (total < capacity) {
+                mi32_debug_ws_region &o = regions[total];
+                o = mi32_debug_ws_region{c.owner, c.part, r.kind, 0, c.base + r.off, r.bytes, {}};
+                std::strncpy(o.name, r.name, sizeof(o.name) - 1);
+            }
+            ++total;
+        }
+    *count = total;
     return MI32_OK;
 }
 

@@ -12,7 +12,17 @@
 namespace mi32 {
 
 // workspace: per matrix rowsum_right[n], rowsum_left[n], sumsq (doubles)
-size_t residual_workspace_bytes(int n, int batch) { return align256(((size_t)2 * n + 2) * sizeof(double) * batch); }
+static size_t residual_carve(int n, int batch, void *base, double **sums, WsRegions *regions = nullptr)
+{
+    WsCarver c(base, regions);
+    *sums = c.take<double>(align256(((size_t)2 * n + 2) * sizeof(double) * batch), WS_VALUES, "sums");
+    return c.off;
+}
+size_t residual_workspace_bytes(int n, int batch, WsRegions *regions)
+{
+    double *sums;
+    return residual_carve(n, batch, nullptr, &sums, regions);
+}
 
 // C = L * R (n x n) on the fp64 matrix cores: 64 x 64 tile per workgroup, 4 waves (2 x 2), each 32 x 32 = 2 x 2 tiles
 // of v_mfma_f64_16x16x4_f64 (A[i = lane & 15][k = lane >> 4], B[k][j = lane & 15], D[row = (lane >> 4) + 4 reg][col =
@@ -150,9 +160,11 @@ __global__ __launch_bounds__(256) void residual_finalize_kernel(const double *__
     }
 }
 
-hipError_t residual_launch(const float *d_a, const float *d_x, int n, int batch, double *d_out, void *ws,
+hipError_t residual_launch(const float *d_a, const float *d_x, int n, int batch, double *d_out, void *wsp,
                            hipStream_t stream)
 {
+    double *ws;
+    residual_carve(n, batch, wsp, &ws);
     hipError_t e = hipMemsetAsync(ws, 0, ((size_t)2 * n + 2) * sizeof(double) * batch, stream);
     if (e != hipSuccess) return e;
     // the member index is blockIdx.z, which the grid limits to 65535: the tile launches go in chunks of members

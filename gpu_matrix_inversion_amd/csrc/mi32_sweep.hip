@@ -61,25 +61,26 @@ struct SweepWs {
     int *orig, *invp;
     size_t wstride;  // elements per matrix
 };
-static size_t sweep_carve(const SweepPlan &p, int batch, void *base, SweepWs &o, size_t elem_bytes)
+static size_t sweep_carve(const SweepPlan &p, int batch, void *base, SweepWs &o, size_t elem_bytes,
+                          WsRegions *regions = nullptr)
 {
     const size_t wbytes = align256((size_t)p.n * p.ld * elem_bytes);
     const size_t kbytes = align256((size_t)p.row_tiles * 2 * sizeof(unsigned long long) * batch);
     const size_t ibytes = align256((size_t)p.n * sizeof(int) * batch);
-    WsCarver c(base);
+    WsCarver c(base, regions);
     o.wstride = wbytes / elem_bytes;
-    o.w0 = c.take<void>(wbytes * batch);
-    o.w1 = c.take<void>(wbytes * batch);
-    o.k0 = c.take<void>(kbytes);
-    o.k1 = c.take<void>(kbytes);
-    o.orig = c.take<int>(ibytes);
-    o.invp = c.take<int>(ibytes);
+    o.w0 = c.take<void>(wbytes * batch, WS_VALUES, "w0");
+    o.w1 = c.take<void>(wbytes * batch, WS_VALUES, "w1");
+    o.k0 = c.take<void>(kbytes, WS_RECORDS, "k0");
+    o.k1 = c.take<void>(kbytes, WS_RECORDS, "k1");
+    o.orig = c.take<int>(ibytes, WS_INDICES, "orig");
+    o.invp = c.take<int>(ibytes, WS_INDICES, "invp");
     return c.off;
 }
-size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes)
+size_t sweep_workspace_bytes(const SweepPlan &p, int batch, size_t elem_bytes, WsRegions *regions)
 {
     SweepWs ws;
-    return sweep_carve(p, batch, nullptr, ws, elem_bytes);
+    return sweep_carve(p, batch, nullptr, ws, elem_bytes, regions);
 }
 
 // ---- makeAugmentedMatrix counterpart (mat_inv_32.cpp:177-192) ---------------

@@ -110,6 +110,11 @@ SIGNATURES = _signatures(
     ("mi32_debug_dpp_selftest", _I, [_VP, _VP, _I, _VP]),
 )
 C_ABI_SYMBOLS = tuple(name for name in SIGNATURES if not name.startswith("mi32_debug_"))
+# the sparse set-up calls, declared in a header of their own (include/mat_inv_32_csr.h)
+CSR_SIGNATURES = _signatures(
+    ("mi32_csr_blocks_device mi32_csr_blocks_device_f64", _I, [_VP] * 4 + [_I] + [_VP] * 4),
+)
+CSR_ABI_SYMBOLS = tuple(CSR_SIGNATURES)
 
 
 def build_library(force: bool = False) -> str:
@@ -143,7 +148,7 @@ def load() -> ctypes.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the pure ctypes/numpy path
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES}.items():
         if name == "mi32_debug_dpp_selftest" and not hasattr(lib, name):
             continue  # tools/ab_bench.py also loads builds older than the self-test
         fn = getattr(lib, name)

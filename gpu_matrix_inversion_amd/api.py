@@ -441,6 +441,105 @@ def check_packed_rhs(plan, mats, b, out, what):
     return rhs, out, nrhs
 
 
+# ---- the sparse matrix of csr_diag_blocks / inv_csr_blocks: pure torch as above ----
+def csr_parts(a):
+    """``(crow, col, values)`` of the one argument form of the CSR calls: a 2-D square ``torch.sparse_csr`` tensor
+    (through ``crow_indices()``, ``col_indices()`` and ``values()``), or the triple itself.  A batched CSR tensor, a
+    tensor of another layout or a matrix that is not square is a ValueError."""
+    import torch
+
+    if isinstance(a, torch.Tensor):
+        if a.layout != torch.sparse_csr:
+            raise ValueError("expected a torch.sparse_csr tensor or a (crow, col, values) triple")
+        if a.dim() != 2:
+            raise ValueError("batched CSR tensors are not taken: expected a 2-D matrix")
+        if a.shape[0] != a.shape[1]:
+            raise ValueError(f"expected a square matrix, not {tuple(a.shape)}")
+        return a.crow_indices(), a.col_indices(), a.values()
+    if not isinstance(a, (tuple, list)) or len(a) != 3 or not all(isinstance(t, torch.Tensor) for t in a):
+        raise ValueError("expected a torch.sparse_csr tensor or a (crow, col, values) triple")
+    return tuple(a)
+
+
+def check_csr(device, crow, col, values):
+    """The CSR arrays of a square matrix: ``crow`` and ``col`` are contiguous 1-D tensors of ONE dtype, int32 or int64;
+    ``values`` is a contiguous 1-D float32 / float64 tensor with col's element count; all three are on ``device`` and
+    ``crow`` has at least 2 entries.  Returns ``N = crow.numel() - 1``.  What the arrays hold is not looked at (no
+    synchronisation): that is ``validate_csr``."""
+    import torch
+
+    if crow.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"crow is {crow.dtype}, expected torch.int32 or torch.int64")
+    if col.dtype != crow.dtype:
+        raise ValueError(f"col is {col.dtype}, crow {crow.dtype}: expected one index dtype")
+    _check_float(values.dtype, "values")
+    _check_tensor(crow, device, crow.dtype, "crow")
+    _check_tensor(col, device, col.dtype, "col")
+    _check_tensor(values, device, values.dtype, "values")
+    if values.numel() != col.numel():
+        raise ValueError(f"values holds {values.numel()} entries, col {col.numel()}")
+    if crow.numel() < 2:
+        raise ValueError("crow: at least 2 entries (one row)")
+    return crow.numel() - 1
+
+
+def check_csr_first_rows(first_rows, orders, n):
+    """The first row (and column) of every block as an int64 array, checked on the host: ``first_rows`` is a 1-D
+    integer sequence with one entry per block, ``0 <= first`` and ``first + order <= n``.  Blocks may overlap or skip
+    rows.  ``first_rows=None``: consecutive diagonal blocks, the orders must sum to ``n``."""
+    orders = np.asarray(orders, dtype=np.int64)
+    if first_rows is None:
+        if int(orders.sum()) != n:
+            raise ValueError(f"block_orders sum to {int(orders.sum())}, the matrix has {n} rows (or give first_rows)")
+        return np.concatenate(([0], np.cumsum(orders)[:-1]))
+    f = np.asarray(first_rows)
+    if f.ndim != 1 or f.size != orders.size or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"first_rows: a 1-D integer sequence of {orders.size} entries, one per block")
+    f = f.astype(np.int64)
+    if (f < 0).any() or (f + orders > n).any():
+        b = int(np.nonzero((f < 0) | (f + orders > n))[0][0])
+        raise ValueError(f"first_rows: block {b} (rows {int(f[b])} ... {int(f[b] + orders[b]) - 1}) leaves the matrix "
+                         f"of {n} rows")
+    return f
+
+
+def check_csr_out(values, out, flat_size):
+    """The packed output of ``csr_diag_blocks``: ``out`` where given -- a contiguous 1-D tensor of ``flat_size``
+    elements of values' dtype and device that meets the memory of ``values`` nowhere --, else a new tensor."""
+    import torch
+
+    if out is None:
+        return torch.empty(flat_size, dtype=values.dtype, device=values.device)
+    _check_tensor(out, values.device, values.dtype, "out", flat_size)
+    if _overlap(out, values):
+        raise ValueError("out must not alias values")
+    return out
+
+
+def validate_csr(crow, col, n):
+    """What ``validate=True`` adds to ``check_csr``, each a ValueError: ``crow[0] == 0``, ``crow[-1] == nnz``, ``crow``
+    non-decreasing, ``0 <= col < n``, no (row, column) pair twice.  Reads the arrays: synchronises."""
+    import torch
+
+    nnz = col.numel()
+    if int(crow[0]) != 0:
+        raise ValueError(f"crow[0] is {int(crow[0])}, expected 0")
+    if int(crow[-1]) != nnz:
+        raise ValueError(f"crow[-1] is {int(crow[-1])}, expected the {nnz} entries of col")
+    counts = crow[1:] - crow[:-1]
+    if bool((counts < 0).any()):
+        raise ValueError("crow decreases")
+    if nnz == 0:
+        return
+    if int(col.min()) < 0 or int(col.max()) >= n:
+        raise ValueError(f"col: expected 0 <= col < {n}")
+    rows = torch.repeat_interleave(torch.arange(n, device=col.device), counts.long())
+    key = torch.sort(rows * n + col.long()).values
+    if bool((key[1:] == key[:-1]).any()):
+        at = int(key[1:][key[1:] == key[:-1]][0])
+        raise ValueError(f"entry ({at // n}, {at % n}) is stored twice")
+
+
 class RaggedPlan:
     """A batch of members of mixed orders 1 ... 128 (``Inverter.plan_ragged``): the orders, binned once into the eight
     kernel classes and uploaded to the device.  Immutable; usable any number of times and from any ``Inverter`` on
@@ -917,6 +1016,45 @@ class Inverter:
         r = self._inv_vbatched(plan, m.dtype, elem_off * m.element_size() + m.data_ptr(), lds, out_ptrs, ldout, status,
                                det)
         return (out, r[0], r[1]) if det else (out, r)
+
+    # ---- from a sparse matrix: the blocks of a CSR matrix, gathered on the device ----
+    def csr_diag_blocks(self, a, block_orders, out=None, *, first_rows=None, validate=False):
+        """The square diagonal blocks of a sparse matrix in the packed layout of ``inv_ragged``, gathered on the device
+        in one call (at most five launches) without a dense N x N copy.  ``a`` is a 2-D square ``torch.sparse_csr``
+        tensor or a ``(crow, col, values)`` triple (``check_csr``: int32 or int64 indices, float32 or float64 values);
+        ``block_orders`` as in ``inv_diag_blocks``, each 1 ... 128.  Without ``first_rows`` the blocks are consecutive
+        and the orders sum to N; ``first_rows``, a host integer sequence with one entry per block, puts block b at
+        rows and columns ``first_rows[b] ... first_rows[b] + n_b - 1`` instead: blocks may overlap or skip rows.
+        Element (i, j) of a block is the stored value copied bit for bit, ``+0.0`` where none is stored; columns need
+        no order inside a row; a (row, column) pair stored twice is the caller's error.  ``out``: a contiguous 1-D
+        tensor of ``sum n_b^2`` elements of values' dtype and device that meets ``values`` nowhere.
+        ``validate=True`` adds the synchronising checks of ``validate_csr``; the default path does not synchronise.
+        Asynchronous on torch's current stream.  Returns the packed tensor; the plan of the last block structure is
+        kept (shared with ``inv_diag_blocks``)."""
+        crow, col, values = csr_parts(a)
+        n = check_csr(self.device, crow, col, values)
+        orders = check_diag_blocks(self.device, None, block_orders)
+        first = check_csr_first_rows(first_rows, orders, n)
+        plan = self._diag_blocks_plan(None, orders)[0]
+        check_ragged_call(self.device, plan, values.dtype, want_status=False)
+        out = check_csr_out(values, out, plan.flat_size)
+        if validate:
+            validate_csr(crow, col, n)
+        # the consecutive first rows are the plan's row offsets, already on the device
+        d_first = plan._row_offsets if first_rows is None else self._torch.from_numpy(first).to(self.device)
+        stream = self._bind_stream()
+        _lib.check(self._entry("mi32_csr_blocks_device", values.dtype)(
+            self._h, plan._p, _ptr(crow), _ptr(col), crow.element_size(), _ptr(values), _ptr(d_first),
+            _ptr(plan._pointers(out, None, stream)), None), "mi32_csr_blocks_device")
+        return out
+
+    def inv_csr_blocks(self, a, block_orders, *, first_rows=None, det=False, validate=False):
+        """Block-Jacobi set-up from the sparse matrix: ``csr_diag_blocks``, then ``inv_ragged`` in place on the same
+        stream.  Returns ``(x_packed, status)``, or ``(x_packed, status, (det_mant, det_exp))`` with ``det=True`` --
+        what ``inv_diag_blocks(dense, block_orders, packed=True)`` returns for the dense form of ``a``, and what
+        ``apply_diag_blocks(x_packed, block_orders, r)`` takes as it is."""
+        x = self.csr_diag_blocks(a, block_orders, first_rows=first_rows, validate=validate)
+        return self.inv_ragged(self._diag_blocks_plan(None, block_orders)[0], x, out=x, det=det)
 
     def set_lookahead(self, enable: bool):
         _lib.check(self._lib.mi32_set_lookahead(self._h, 1 if enable else 0), "mi32_set_lookahead")

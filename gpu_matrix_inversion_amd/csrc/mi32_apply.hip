@@ -43,19 +43,6 @@ struct ApplyGeom {
     static_assert(L % TJ == 0 && (kPitch & 1) == 1, "tile geometry");
 };
 
-// LDS written by one lane of the group is read by another
-template <int L>
-__device__ __forceinline__ void group_sync()
-{
-    if constexpr (L > 64) {
-        __syncthreads();
-    } else {  // the group lies inside one wave: program order, which the compiler must keep
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
-
 // what one group knows of its member
 template <typename T>
 struct ApplyMember {

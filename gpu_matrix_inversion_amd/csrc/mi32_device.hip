@@ -7,6 +7,7 @@
 
 #include "mi32_apply.h"
 #include "mi32_context.h"
+#include "mi32_csr_blocks.h"
 #include "mi32_det_large.h"
 
 using namespace mi32;
@@ -267,6 +268,26 @@ static int apply_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T 
     return hip_status(e, "kernel launch");
 }
 
+// The square blocks of a CSR matrix as the plan's members: the launches of apply_walk, no workspace, no memset, no
+// status (a copy cannot fail).  The arguments are checked before the context is touched.
+template <typename T>
+static int csr_blocks_device(mi32_context *h, const mi32_vbatch *p, const void *d_row_ptr, const void *d_col,
+                             int index_bytes, const T *d_val, const long long *d_first, T *const *d_out,
+                             const int *d_ldout)
+{
+    if (!h || !p || !d_row_ptr || !d_col || !d_val || !d_first || !d_out) return MI32_BAD_SHAPE;
+    if ((index_bytes != 4 && index_bytes != 8) || p->device != h->device) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const CsrBlocksArgs<T> a{p->d_orders, p->d_members, d_row_ptr, d_col, d_val, d_first, d_out, d_ldout, index_bytes};
+    hipError_t e = hipSuccess;
+    apply_walk(p->class_begin, sizeof(T), [&](const ApplyLaunch &l) {
+        e = csr_blocks_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+        return e == hipSuccess;
+    });
+    return hip_status(e, "kernel launch");
+}
+
 extern "C" {
 
 int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status)
@@ -416,6 +437,19 @@ int mi32_apply_device_vbatched_f64(mi32_handle_t h, mi32_vbatch_t p, const doubl
                                    const int *d_ldz)
 {
     return apply_device_vbatched(h, p, d_x, d_ldx, d_r, d_ldr, nrhs, d_z, d_ldz);
+}
+
+int mi32_csr_blocks_device(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col, int index_bytes,
+                           const float *d_val, const long long *d_first, float *const *d_out, const int *d_ldout)
+{
+    return csr_blocks_device(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_out, d_ldout);
+}
+
+int mi32_csr_blocks_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col,
+                               int index_bytes, const double *d_val, const long long *d_first, double *const *d_out,
+                               const int *d_ldout)
+{
+    return csr_blocks_device(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_out, d_ldout);
 }
 
 int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out)

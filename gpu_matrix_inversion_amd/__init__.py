@@ -18,7 +18,7 @@ from ._lib import (  # noqa: F401
     Mi32Error,
     build_library,
 )
-from .api import Inverter, RaggedPlan, vbatch_bin, slogdet_from_frexp, det_from_frexp, fp32_bench, fp64_bench, just_inv, matrix_multiply, last_timing, matrix_inv_32, matrix_inv_32_batched, matrix_inv_64, matrix_inversion_no_pivots  # noqa: F401
+from .api import STORAGE_FORMATS, StoredInverses, choose_storage, Inverter, RaggedPlan, vbatch_bin, slogdet_from_frexp, det_from_frexp, fp32_bench, fp64_bench, just_inv, matrix_multiply, last_timing, matrix_inv_32, matrix_inv_32_batched, matrix_inv_64, matrix_inversion_no_pivots  # noqa: F401
 from .sharding import invert_distributed, invert_sharded, shard_range  # noqa: F401
 
 __all__ = [
@@ -33,6 +33,9 @@ __all__ = [
     "last_timing",
     "Inverter",
     "RaggedPlan",
+    "StoredInverses",
+    "STORAGE_FORMATS",
+    "choose_storage",
     "vbatch_bin",
     "slogdet_from_frexp",
     "det_from_frexp",

@@ -115,6 +115,13 @@ CSR_SIGNATURES = _signatures(
     ("mi32_csr_blocks_device mi32_csr_blocks_device_f64", _I, [_VP] * 4 + [_I] + [_VP] * 4),
 )
 CSR_ABI_SYMBOLS = tuple(CSR_SIGNATURES)
+# block inverses stored in a per-member format, declared in a header of their own (include/mat_inv_32_stored.h)
+STORED_SIGNATURES = _signatures(
+    ("mi32_block_stats_device mi32_block_stats_device_f64", _I, [_VP] * 5),
+    ("mi32_store_inverses_device mi32_store_inverses_device_f64", _I, [_VP] * 7),
+    ("mi32_apply_stored_device mi32_apply_stored_device_f64", _I, [_VP] * 7 + [_I] + [_VP] * 2),
+)
+STORED_ABI_SYMBOLS = tuple(STORED_SIGNATURES)
 
 
 def build_library(force: bool = False) -> str:
@@ -148,7 +155,7 @@ def load() -> ctypes.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the pure ctypes/numpy path
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES, **STORED_SIGNATURES}.items():
         if name == "mi32_debug_dpp_selftest" and not hasattr(lib, name):
             continue  # tools/ab_bench.py also loads builds older than the self-test
         fn = getattr(lib, name)

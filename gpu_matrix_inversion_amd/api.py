@@ -540,6 +540,144 @@ def validate_csr(crow, col, n):
         raise ValueError(f"entry ({at // n}, {at % n}) is stored twice")
 
 
+# ---- block inverses stored in a per-member format (store_inverses / apply_stored): pure torch and NumPy as above ----
+class StorageFormat:
+    """One row of ``STORAGE_FORMATS``: ``name``, ``nbytes`` per element (None: the working type's), the unit roundoff
+    ``u``, the smallest normal and the largest finite magnitude (None for native, which always qualifies)."""
+
+    def __init__(self, name, nbytes, u, smallest_normal, largest_finite):
+        self.name, self.nbytes, self.u = name, nbytes, u
+        self.smallest_normal, self.largest_finite = smallest_normal, largest_finite
+
+    def __repr__(self):
+        return f"StorageFormat({self.name})"
+
+
+# the storage formats of include/mat_inv_32_stored.h by code
+STORAGE_FORMATS = {
+    0: StorageFormat("native", None, None, None, None),
+    1: StorageFormat("float32", 4, 2.0 ** -24, 2.0 ** -126, (2.0 - 2.0 ** -23) * 2.0 ** 127),
+    2: StorageFormat("float16", 2, 2.0 ** -11, 2.0 ** -14, 65504.0),
+    3: StorageFormat("bfloat16", 2, 2.0 ** -8, 2.0 ** -126, (2.0 - 2.0 ** -7) * 2.0 ** 127),
+}
+
+
+def storage_candidates(dtype):
+    """The format codes a member of ``dtype`` is tried in, narrowest first; native (0) is the fallback behind them."""
+    import torch
+
+    _check_float(dtype, "dtype")
+    return (2, 3, 1) if dtype == torch.float64 else (2, 3)
+
+
+def choose_storage(dtype, kappa, absmax, absmin, tol=0.1, status=None):
+    """The storage format of every member, ``int32[batch]`` on the inputs' device: the first of float16, bfloat16,
+    float32 (``dtype`` float64 only) for which ``kappa`` is finite, ``kappa * u_F <= tol``, ``absmax <=
+    largest_finite_F`` and ``absmin >= smallest_normal_F``; native (0) otherwise, and for a member whose ``status`` is
+    not 0.  ``kappa`` (``norm1(A) * norm1(X)`` as one float64 product), ``absmax`` and ``absmin`` (of X) are float64
+    1-D tensors of one length and device, ``status`` an integer tensor beside them or None; ``tol`` is a positive
+    number (0.1 is Ginkgo's).  Elementwise torch on float64, no kernel: CPU tensors pass."""
+    import torch
+
+    candidates = storage_candidates(dtype)
+    for what, t in (("kappa", kappa), ("absmax", absmax), ("absmin", absmin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 1:
+            raise ValueError(f"{what}: expected a 1-D float64 tensor")
+        if t.shape != kappa.shape or t.device != kappa.device:
+            raise ValueError(f"{what}: expected kappa's length and device")
+    if not (isinstance(tol, (int, float)) and tol > 0 and tol < float("inf")):
+        raise ValueError("tol: a positive finite number")
+    open_ = torch.isfinite(kappa)
+    if status is not None:
+        if (not isinstance(status, torch.Tensor) or status.dtype.is_floating_point or status.shape != kappa.shape
+                or status.device != kappa.device):
+            raise ValueError("status: an integer tensor of kappa's length and device")
+        open_ = open_ & (status == 0)
+    out = torch.zeros(kappa.shape, dtype=torch.int32, device=kappa.device)
+    for code in candidates:
+        f = STORAGE_FORMATS[code]
+        fits = open_ & (kappa * f.u <= tol) & (absmax <= f.largest_finite) & (absmin >= f.smallest_normal)
+        out = torch.where(fits, torch.full_like(out, code), out)
+        open_ = open_ & ~fits
+    return out
+
+
+def check_storage_formats(plan, dtype, formats):
+    """The format codes of ``store_inverses`` as a host int32 array, checked on the host: ``formats`` is a 1-D integer
+    sequence or an int32 tensor (a device tensor is downloaded: this synchronises) with one entry per member of
+    ``plan``, every code one of ``STORAGE_FORMATS``, code 1 (float32) for float64 members only."""
+    import torch
+
+    _check_float(dtype, "dtype")
+    if isinstance(formats, torch.Tensor):
+        if formats.dtype != torch.int32:
+            raise ValueError(f"formats is {formats.dtype}, expected torch.int32")
+        f = formats.detach().cpu().numpy()
+    else:
+        f = np.asarray(formats)
+    if f.ndim != 1 or f.size != plan.batch or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"formats: a 1-D integer sequence of {plan.batch} entries, one per member")
+    f = f.astype(np.int64)
+    bad = ~np.isin(f, list(STORAGE_FORMATS))
+    if dtype == torch.float32:
+        bad |= f == 1
+    if bad.any():
+        b = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"formats: member {b} has code {int(f[b])}, which {dtype} members do not take")
+    return f.astype(np.int32)
+
+
+def stored_layout(orders, formats, native_bytes):
+    """``(offsets, nbytes)`` of the store: member b starts at byte ``offsets[b]``, ``offsets[0] = 0`` and
+    ``offsets[b + 1] = round_up_8(offsets[b] + n_b^2 * bytes(F_b))``; ``nbytes`` is what follows the last member in
+    that way, the size of the buffer.  Host only: int64 arithmetic on the orders and the format codes."""
+    size = np.array([native_bytes, 4, 2, 2], np.int64)[np.asarray(formats, np.int64)]
+    span = (np.asarray(orders, np.int64) ** 2 * size + 7) // 8 * 8
+    end = np.cumsum(span)
+    return np.concatenate(([0], end[:-1])).astype(np.int64), int(end[-1])
+
+
+def check_store_data(device, data, nbytes, x_flat=None):
+    """A caller's buffer for the store: a contiguous 1-D uint8 tensor on ``device`` of at least ``nbytes`` bytes at an
+    address that is a multiple of 8, which meets the memory of ``x_flat`` nowhere."""
+    import torch
+
+    _check_tensor(data, device, torch.uint8, "data")
+    if data.numel() < nbytes or data.data_ptr() % 8:
+        raise ValueError(f"data: at least {nbytes} bytes at an address that is a multiple of 8")
+    if x_flat is not None and _overlap(data, x_flat):
+        raise ValueError("data must not alias x_flat")
+
+
+class _StoreSpan:
+    """The store's memory as ``check_packed_rhs`` looks at the matrices of a call: the members' dtype and device, and
+    the span of the byte buffer."""
+
+    def __init__(self, dtype, data):
+        self.dtype, self.device, self._data = dtype, data.device, data
+
+    def data_ptr(self):
+        return self._data.data_ptr()
+
+    def numel(self):
+        return self._data.numel()
+
+    def element_size(self):
+        return 1
+
+
+class StoredInverses:
+    """What ``Inverter.store_inverses`` returns and ``Inverter.apply_stored`` takes: the members of ``plan`` (a
+    RaggedPlan; it must stay open), of working type ``dtype``, each narrowed to its own storage format in one byte
+    buffer.  ``formats`` (int32) and ``offsets`` (int64, bytes) are device tensors in the caller's member order,
+    ``data`` the uint8 device buffer of ``nbytes`` bytes; ``native_nbytes`` is what the members take in ``dtype``,
+    ``counts[code]`` the members per format.  Immutable by convention."""
+
+    def __init__(self, plan, dtype, formats, offsets, data, nbytes, native_nbytes, counts):
+        self.plan, self.dtype, self.formats, self.offsets, self.data = plan, dtype, formats, offsets, data
+        self.nbytes, self.native_nbytes, self.counts = nbytes, native_nbytes, counts
+
+
 class RaggedPlan:
     """A batch of members of mixed orders 1 ... 128 (``Inverter.plan_ragged``): the orders, binned once into the eight
     kernel classes and uploaded to the device.  Immutable; usable any number of times and from any ``Inverter`` on
@@ -1055,6 +1193,130 @@ class Inverter:
         ``apply_diag_blocks(x_packed, block_orders, r)`` takes as it is."""
         x = self.csr_diag_blocks(a, block_orders, first_rows=first_rows, validate=validate)
         return self.inv_ragged(self._diag_blocks_plan(None, block_orders)[0], x, out=x, det=det)
+
+    # ---- block inverses stored in reduced precision per block, and applied from that store ----
+    def _block_stats(self, plan, dtype, ptrs, ld):
+        """The library call of the block statistics, on the stream bound."""
+        stats = self._torch.empty((plan.batch, 3), dtype=self._torch.float64, device=self.device)
+        _lib.check(self._entry("mi32_block_stats_device", dtype)(self._h, plan._p, _ptr(ptrs), _ptr(ld), _ptr(stats)),
+                   "mi32_block_stats_device")
+        return stats
+
+    def block_stats(self, plan, flat):
+        """``(norm1, absmax, absmin)`` of every member of the packed tensor ``flat`` (the layout of ``inv_ragged``) as
+        a float64 ``(plan.batch, 3)`` device tensor in the caller's member order: the 1-norm (column sums of magnitudes
+        added in float64, rows ascending), the largest magnitude and the smallest nonzero one (``+inf`` for an all-zero
+        member).  A member with a NaN entry gives three NaNs.  One call, at most five launches, asynchronous on
+        torch's current stream."""
+        check_packed_matrices(self.device, plan, flat, "flat", want_status=False)
+        stream = self._bind_stream()
+        return self._block_stats(plan, flat.dtype, plan._pointers(flat, None, stream), None)
+
+    def block_stats_pointers(self, plan, ptrs, dtype, ld=None):
+        """``block_stats`` in the low-level form: ``ptrs`` is an int64 device tensor of ``plan.batch`` member addresses
+        (row-major members of ``dtype``), ``ld`` an int32 device tensor of leading dimensions (None: the orders).
+        Padding behind a row is never read."""
+        check_pointer_args(self.device, plan, dtype, {"ptrs": ptrs}, {"ld": ld}, want_status=False)
+        self._bind_stream()
+        return self._block_stats(plan, dtype, ptrs, ld)
+
+    def _store(self, plan, dtype, x_ptrs, ldx, formats, layout, data):
+        """The library call of the store kernels, on the stream bound: ``formats`` is the checked host array,
+        ``layout`` its ``stored_layout``, ``data`` the checked buffer or None for a new one."""
+        torch = self._torch
+        offsets, nbytes = layout
+        if data is None:
+            data = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        d_formats = torch.from_numpy(formats).to(self.device)
+        d_offsets = torch.from_numpy(offsets).to(self.device)
+        _lib.check(self._entry("mi32_store_inverses_device", dtype)(
+            self._h, plan._p, _ptr(x_ptrs), _ptr(ldx), _ptr(d_formats), _ptr(d_offsets), _ptr(data)),
+            "mi32_store_inverses_device")
+        counts = tuple(int(c) for c in np.bincount(formats, minlength=len(STORAGE_FORMATS)))
+        native = torch.empty(0, dtype=dtype).element_size()
+        return StoredInverses(plan, dtype, d_formats, d_offsets, data, nbytes, plan.flat_size * native, counts)
+
+    def _store_layout(self, plan, dtype, formats, data, x_flat=None):
+        """``(checked host formats, stored_layout)`` of a store call, and the check of a caller's ``data``."""
+        f = check_storage_formats(plan, dtype, formats)
+        layout = stored_layout(plan.orders, f, self._torch.empty(0, dtype=dtype).element_size())
+        if data is not None:
+            check_store_data(self.device, data, layout[1], x_flat)
+        return f, layout
+
+    def store_inverses(self, plan, x_flat, formats, *, data=None):
+        """Narrow every member of the packed tensor ``x_flat`` (what ``inv_ragged`` returns) to its own storage format
+        and return the ``StoredInverses`` that ``apply_stored`` reads.  ``formats``: one code of ``STORAGE_FORMATS``
+        per member, a host integer sequence or a device int32 tensor (``choose_storage`` returns one); code 1 (float32)
+        is for float64 members only.  The codes are checked on the host and the buffer is sized from them: with a
+        device tensor this is the one synchronisation of the set-up.  Narrowing is round-to-nearest-even with IEEE
+        results, from float64 to a 16-bit format through float32.  ``data``: a uint8 device tensor to store into
+        instead of a new one (at least the store's size, 8-byte aligned, away from ``x_flat``); bytes between members
+        are never written.  ``x_flat`` is not kept.  One call, at most five launches."""
+        check_packed_matrices(self.device, plan, x_flat, "x_flat", want_status=False)
+        f, layout = self._store_layout(plan, x_flat.dtype, formats, data, x_flat)
+        stream = self._bind_stream()
+        return self._store(plan, x_flat.dtype, plan._pointers(x_flat, None, stream), None, f, layout, data)
+
+    def store_inverses_pointers(self, plan, x_ptrs, dtype, formats, ldx=None, *, data=None):
+        """``store_inverses`` in the low-level form: ``x_ptrs`` is an int64 device tensor of ``plan.batch`` member
+        addresses (row-major members of ``dtype``), ``ldx`` an int32 device tensor of leading dimensions (None: the
+        orders).  The store itself is always dense."""
+        check_pointer_args(self.device, plan, dtype, {"x_ptrs": x_ptrs}, {"ldx": ldx}, want_status=False)
+        f, layout = self._store_layout(plan, dtype, formats, data)
+        self._bind_stream()
+        return self._store(plan, dtype, x_ptrs, ldx, f, layout, data)
+
+    def _apply_stored(self, stored, nrhs, r_ptrs, ldr, z_ptrs, ldz):
+        """The library call of the applications from a store, on the stream bound."""
+        _lib.check(self._entry("mi32_apply_stored_device", stored.dtype)(
+            self._h, stored.plan._p, _ptr(stored.data), _ptr(stored.offsets), _ptr(stored.formats), _ptr(r_ptrs),
+            _ptr(ldr), int(nrhs), _ptr(z_ptrs), _ptr(ldz)), "mi32_apply_stored_device")
+
+    def apply_stored(self, stored, r, out=None):
+        """``z = blockdiag(widen(X)) r`` from a ``StoredInverses``: the call of ``apply_ragged`` with every member read
+        in its storage format (2, 4 or 8 bytes per element) and widened exactly on the way into the multiply-adds,
+        which are unchanged -- the result has the bits of ``apply_ragged`` on the widened members.  ``r`` and ``out``
+        as in ``apply_ragged`` (``out`` may be ``r``; it must not meet ``stored.data``).  Returns z."""
+        if not isinstance(stored, StoredInverses):
+            raise ValueError("expected the StoredInverses of store_inverses")
+        plan = stored.plan
+        check_ragged_call(self.device, plan, stored.dtype, want_status=False)
+        rhs, out, nrhs = check_packed_rhs(plan, _StoreSpan(stored.dtype, stored.data), r, out, "r")
+        stream = self._bind_stream()
+        self._apply_stored(stored, nrhs, plan._pointers(rhs, nrhs, stream), None, plan._pointers(out, nrhs, stream), None)
+        return out
+
+    def apply_stored_pointers(self, stored, r_ptrs, z_ptrs, nrhs, ldr=None, ldz=None):
+        """``apply_stored`` in the low-level form of ``apply_pointers``: ``r_ptrs`` / ``z_ptrs`` are int64 device
+        tensors of member addresses (R and Z are n x ``nrhs``, row-major in ``stored.dtype``), ``ldr`` / ``ldz`` int32
+        device tensors of leading dimensions (None: ``nrhs``).  A member may be applied in place; what the addresses
+        point to cannot be checked."""
+        if not isinstance(stored, StoredInverses):
+            raise ValueError("expected the StoredInverses of store_inverses")
+        check_pointer_args(self.device, stored.plan, stored.dtype, {"r_ptrs": r_ptrs, "z_ptrs": z_ptrs},
+                           {"ldr": ldr, "ldz": ldz}, nrhs=nrhs, want_status=False)
+        self._bind_stream()
+        self._apply_stored(stored, nrhs, r_ptrs, ldr, z_ptrs, ldz)
+
+    def inv_csr_blocks_adaptive(self, a, block_orders, *, tol=0.1, first_rows=None, validate=False):
+        """Adaptive-precision block-Jacobi set-up from the sparse matrix, on one stream: ``csr_diag_blocks``,
+        ``block_stats`` of the blocks, ``inv_ragged`` in place, ``block_stats`` of the inverses, ``choose_storage``
+        with ``kappa = norm1(A) * norm1(X)``, the inversion's status and ``tol``, and ``store_inverses``.  Returns
+        ``(stored, status, formats)``: the ``StoredInverses`` for ``apply_stored``, one status word per block and the
+        chosen format codes (int32, device).  A block whose status is not 0 is stored native, as the inversion left
+        it.  Synchronises once, to size the store.  The plan goes with the result (``stored.plan``): it is taken out of
+        the Inverter's one-entry cache."""
+        x = self.csr_diag_blocks(a, block_orders, first_rows=first_rows, validate=validate)
+        plan = self._diag_blocks_plan(None, block_orders)[0]
+        stats_a = self.block_stats(plan, x)
+        x, status = self.inv_ragged(plan, x, out=x)
+        stats_x = self.block_stats(plan, x)
+        formats = choose_storage(x.dtype, stats_a[:, 0] * stats_x[:, 0], stats_x[:, 1].contiguous(),
+                                 stats_x[:, 2].contiguous(), tol, status)
+        stored = self.store_inverses(plan, x, formats)
+        self._diag_plan = None  # the stored object owns the plan now
+        return stored, status, formats
 
     def set_lookahead(self, enable: bool):
         _lib.check(self._lib.mi32_set_lookahead(self._h, 1 if enable else 0), "mi32_set_lookahead")

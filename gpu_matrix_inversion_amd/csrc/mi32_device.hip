@@ -9,6 +9,7 @@
 #include "mi32_context.h"
 #include "mi32_csr_blocks.h"
 #include "mi32_det_large.h"
+#include "mi32_stored.h"
 
 using namespace mi32;
 
@@ -288,6 +289,58 @@ static int csr_blocks_device(mi32_context *h, const mi32_vbatch *p, const void *
     return hip_status(e, "kernel launch");
 }
 
+// Block inverses in a per-member storage format (mi32_stored.h): statistics, store and apply, each the launches of
+// apply_walk, no workspace, no memset, no status.  The arguments are checked before the context is touched.
+template <typename T, typename Launch>
+static int stored_walk(mi32_context *h, const mi32_vbatch *p, const Launch &launch)
+{
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    hipError_t e = hipSuccess;
+    apply_walk(p->class_begin, sizeof(T), [&](const ApplyLaunch &l) {
+        e = launch(l);
+        return e == hipSuccess;
+    });
+    return hip_status(e, "kernel launch");
+}
+
+template <typename T>
+static int block_stats_device(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda, double *d_stats)
+{
+    if (!h || !p || !d_a || !d_stats) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const BlockStatsArgs<T> a{p->d_orders, p->d_members, d_a, d_lda, d_stats};
+        return block_stats_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
+template <typename T>
+static int store_inverses_device(mi32_context *h, const mi32_vbatch *p, const T *const *d_x, const int *d_ldx,
+                                 const int *d_format, const long long *d_offset, void *d_store)
+{
+    if (!h || !p || !d_x || !d_format || !d_offset || !d_store) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const StoreArgs<T> a{p->d_orders, p->d_members, d_x, d_ldx, d_format, d_offset, static_cast<unsigned char *>(d_store)};
+        return store_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
+template <typename T>
+static int apply_stored_device(mi32_context *h, const mi32_vbatch *p, const void *d_store, const long long *d_offset,
+                               const int *d_format, const T *const *d_r, const int *d_ldr, int nrhs, T *const *d_z,
+                               const int *d_ldz)
+{
+    if (!h || !p || !d_store || !d_offset || !d_format || !d_r || !d_z || nrhs <= 0) return MI32_BAD_SHAPE;
+    if (p->device != h->device) return MI32_BAD_SHAPE;
+    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const StoredApplyArgs<T> a{p->d_orders, p->d_members, static_cast<const unsigned char *>(d_store), d_offset, d_format,
+                                   d_r, d_z, d_ldr, d_ldz, nrhs};
+        return apply_stored_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
 extern "C" {
 
 int mi32_inv_device(mi32_handle_t h, const float *d_a, int n, int batch, float *d_inv, int *d_status)
@@ -450,6 +503,43 @@ int mi32_csr_blocks_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_r
                                const int *d_ldout)
 {
     return csr_blocks_device(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_out, d_ldout);
+}
+
+int mi32_block_stats_device(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda, double *d_stats)
+{
+    return block_stats_device(h, p, d_a, d_lda, d_stats);
+}
+
+int mi32_block_stats_device_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_a, const int *d_lda,
+                                double *d_stats)
+{
+    return block_stats_device(h, p, d_a, d_lda, d_stats);
+}
+
+int mi32_store_inverses_device(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_x, const int *d_ldx,
+                               const int *d_format, const long long *d_offset, void *d_store)
+{
+    return store_inverses_device(h, p, d_x, d_ldx, d_format, d_offset, d_store);
+}
+
+int mi32_store_inverses_device_f64(mi32_handle_t h, mi32_vbatch_t p, const double *const *d_x, const int *d_ldx,
+                                   const int *d_format, const long long *d_offset, void *d_store)
+{
+    return store_inverses_device(h, p, d_x, d_ldx, d_format, d_offset, d_store);
+}
+
+int mi32_apply_stored_device(mi32_handle_t h, mi32_vbatch_t p, const void *d_store, const long long *d_offset,
+                             const int *d_format, const float *const *d_r, const int *d_ldr, int nrhs,
+                             float *const *d_z, const int *d_ldz)
+{
+    return apply_stored_device(h, p, d_store, d_offset, d_format, d_r, d_ldr, nrhs, d_z, d_ldz);
+}
+
+int mi32_apply_stored_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_store, const long long *d_offset,
+                                 const int *d_format, const double *const *d_r, const int *d_ldr, int nrhs,
+                                 double *const *d_z, const int *d_ldz)
+{
+    return apply_stored_device(h, p, d_store, d_offset, d_format, d_r, d_ldr, nrhs, d_z, d_ldz);
 }
 
 int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out)

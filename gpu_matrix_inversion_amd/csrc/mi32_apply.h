@@ -1,7 +1,8 @@
 // mi32_apply.h -- Z_b = X_b R_b for the members of a variable-size batch (mi32_apply_device_vbatched*): what
 // mi32_apply.hip (the kernels), mi32_plan.hip (the launch list) and mi32_device.hip (the entry points) share.  Included
-// by these three units and, through mi32_csr_blocks.h, by the CSR gather, which walks the same launch list: the
-// elimination kernels never see it.
+// by these three units and, through mi32_stored.h and mi32_csr_blocks.h, by the stored-inverse and CSR units, which walk
+// the same launch list: the elimination kernels never see it.  Host declarations only: what the kernels of that list
+// share is mi32_member_walk.h.
 #pragma once
 #include <functional>
 
@@ -45,19 +46,6 @@ using ApplyLaunchFn = std::function<bool(const ApplyLaunch &)>;  // false ends t
 // lane class that has members, whatever nrhs is.  The plan's classes 0 ... 3 are the lane classes 8 ... 64, its classes
 // 4 ... 7 together the 128-thread class.  The one place the rule lives (mi32_plan.hip).
 void apply_walk(const int *class_begin, size_t elem_bytes, const ApplyLaunchFn &f);
-
-// LDS written by one lane of a group of L lanes is read by another (shared with mi32_csr_blocks.hip)
-template <int L>
-__device__ __forceinline__ void group_sync()
-{
-    if constexpr (L > 64) {
-        __syncthreads();
-    } else {  // the group lies inside one wave: program order, which the compiler must keep
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
 
 // hipErrorInvalidValue for a lane class without an instance, an empty or negative range, no columns or a null pointer
 template <typename T>

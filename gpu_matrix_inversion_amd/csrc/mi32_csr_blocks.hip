@@ -24,14 +24,13 @@
 #include <cstdint>
 
 #include "mi32_csr_blocks.h"
+#include "mi32_member_walk.h"
 
 namespace mi32 {
 
-constexpr int csr_threads(int lanes) { return lanes > 64 ? lanes : 256; }
-
 template <typename T, int L>
 struct CsrGeom {
-    static constexpr int kThreads = csr_threads(L);
+    static constexpr int kThreads = walk_threads(L);
     static constexpr int kLanes = L > 64 ? 64 : L;        // of a group: it lies inside one wave
     static constexpr int kGroups = kThreads / kLanes;
     static constexpr int kShare = L > 64 ? kGroups : 1;   // the groups that share one member, row by row
@@ -39,24 +38,14 @@ struct CsrGeom {
     static constexpr int kRows = 4;                       // the rows a group has in flight
     // a group has at most ceil(L / kShare) <= kLanes rows, one range per lane, and takes them kRows at a time
     static_assert(L <= kShare * kLanes && kLanes % kRows == 0, "one lane per row of the group");
+    static_assert(kSlots == kThreads / L, "the grid of member_walk_launch");
 };
 
-// the largest value of a wave's groups, wave-uniform
-template <int GL>
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int off = GL; off < 64; off <<= 1) {
-        const int o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
 // Slot s of the launch takes member members[first + s] of the plan's sorted list; s is a 64-bit function of blockIdx.x
-// alone.  I: the index type of row_ptr and col.
+// alone.  The lookup is this kernel's own, not member_slot: in the 128 class two groups of 64 lanes share a slot, and
+// the member's order stays a per-lane value.  I: the index type of row_ptr and col.
 template <typename T, typename I, int L>
-__global__ __launch_bounds__(csr_threads(L)) void csr_blocks_vkernel(const CsrBlocksArgs<T> a, const int first,
+__global__ __launch_bounds__(walk_threads(L)) void csr_blocks_vkernel(const CsrBlocksArgs<T> a, const int first,
                                                                      const int count)
 {
     using G = CsrGeom<T, L>;
@@ -140,27 +129,6 @@ __global__ __launch_bounds__(csr_threads(L)) void csr_blocks_vkernel(const CsrBl
     }
 }
 
-template <typename T, typename I, int L>
-static void csr_blocks_launch_class(const CsrBlocksArgs<T> &a, int first, int count, hipStream_t stream)
-{
-    using G = CsrGeom<T, L>;
-    const dim3 grid((unsigned)(((long long)count + G::kSlots - 1) / G::kSlots));
-    hipLaunchKernelGGL((csr_blocks_vkernel<T, I, L>), grid, dim3(G::kThreads), 0, stream, a, first, count);
-}
-
-template <typename T, typename I>
-static bool csr_blocks_launch_lanes(int lanes, const CsrBlocksArgs<T> &a, int first, int count, hipStream_t stream)
-{
-    switch (lanes) {
-        case 8: csr_blocks_launch_class<T, I, 8>(a, first, count, stream); return true;
-        case 16: csr_blocks_launch_class<T, I, 16>(a, first, count, stream); return true;
-        case 32: csr_blocks_launch_class<T, I, 32>(a, first, count, stream); return true;
-        case 64: csr_blocks_launch_class<T, I, 64>(a, first, count, stream); return true;
-        case 128: csr_blocks_launch_class<T, I, 128>(a, first, count, stream); return true;
-        default: return false;
-    }
-}
-
 template <typename T>
 hipError_t csr_blocks_vlaunch(int lanes, const CsrBlocksArgs<T> &a, int first, int count, hipStream_t stream,
                               Profiler *prof)
@@ -168,10 +136,10 @@ hipError_t csr_blocks_vlaunch(int lanes, const CsrBlocksArgs<T> &a, int first, i
     if (count <= 0 || first < 0 || !a.orders || !a.members || !a.row_ptr || !a.col || !a.val || !a.first || !a.out)
         return hipErrorInvalidValue;
     if (a.index_bytes != 4 && a.index_bytes != 8) return hipErrorInvalidValue;
-    ProfScope ps(prof, KC_UPDATE_IN, stream);  // the class of the apply launches, whose members it prepares
-    const bool ok = a.index_bytes == 4 ? csr_blocks_launch_lanes<T, int32_t>(lanes, a, first, count, stream)
-                                       : csr_blocks_launch_lanes<T, int64_t>(lanes, a, first, count, stream);
-    return ok ? hipGetLastError() : hipErrorInvalidValue;
+    const auto k32 = [](auto l) { return csr_blocks_vkernel<T, int32_t, decltype(l)::value>; };
+    const auto k64 = [](auto l) { return csr_blocks_vkernel<T, int64_t, decltype(l)::value>; };
+    return a.index_bytes == 4 ? member_walk_launch(lanes, k32, a, first, count, stream, prof)
+                              : member_walk_launch(lanes, k64, a, first, count, stream, prof);
 }
 template hipError_t csr_blocks_vlaunch(int, const CsrBlocksArgs<float> &, int, int, hipStream_t, Profiler *);
 template hipError_t csr_blocks_vlaunch(int, const CsrBlocksArgs<double> &, int, int, hipStream_t, Profiler *);

@@ -250,50 +250,14 @@ static int solve_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T 
     return hip_status(e, "kernel launch");
 }
 
-// Z = X R for a variable-size batch: the launches of apply_walk, no workspace, no memset, no status (a product cannot
-// fail).  The arguments are checked before the context is touched.
-template <typename T>
-static int apply_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_x, const int *d_ldx,
-                                 const T *const *d_r, const int *d_ldr, int nrhs, T *const *d_z, const int *d_ldz)
-{
-    if (!h || !p || !d_x || !d_r || !d_z || nrhs <= 0) return MI32_BAD_SHAPE;
-    if (p->device != h->device) return MI32_BAD_SHAPE;
-    std::lock_guard<std::mutex> lk(h->mu);
-    MI32_HIP(hipSetDevice(h->device));
-    const ApplyArgs<T> a{p->d_orders, p->d_members, d_x, d_r, d_z, d_ldx, d_ldr, d_ldz, nrhs};
-    hipError_t e = hipSuccess;
-    apply_walk(p->class_begin, sizeof(T), [&](const ApplyLaunch &l) {
-        e = apply_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
-        return e == hipSuccess;
-    });
-    return hip_status(e, "kernel launch");
-}
-
-// The square blocks of a CSR matrix as the plan's members: the launches of apply_walk, no workspace, no memset, no
-// status (a copy cannot fail).  The arguments are checked before the context is touched.
-template <typename T>
-static int csr_blocks_device(mi32_context *h, const mi32_vbatch *p, const void *d_row_ptr, const void *d_col,
-                             int index_bytes, const T *d_val, const long long *d_first, T *const *d_out,
-                             const int *d_ldout)
-{
-    if (!h || !p || !d_row_ptr || !d_col || !d_val || !d_first || !d_out) return MI32_BAD_SHAPE;
-    if ((index_bytes != 4 && index_bytes != 8) || p->device != h->device) return MI32_BAD_SHAPE;
-    std::lock_guard<std::mutex> lk(h->mu);
-    MI32_HIP(hipSetDevice(h->device));
-    const CsrBlocksArgs<T> a{p->d_orders, p->d_members, d_row_ptr, d_col, d_val, d_first, d_out, d_ldout, index_bytes};
-    hipError_t e = hipSuccess;
-    apply_walk(p->class_begin, sizeof(T), [&](const ApplyLaunch &l) {
-        e = csr_blocks_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
-        return e == hipSuccess;
-    });
-    return hip_status(e, "kernel launch");
-}
-
-// Block inverses in a per-member storage format (mi32_stored.h): statistics, store and apply, each the launches of
-// apply_walk, no workspace, no memset, no status.  The arguments are checked before the context is touched.
+// The calls that walk a plan's members with the apply call's launch list (apply_walk: one launch per lane class that has
+// members): the product, the CSR gather, and the statistics, store and apply of block inverses in a per-member storage
+// format (mi32_stored.h).  No workspace, no memset, no status: a product or a copy cannot fail.  Each caller checks its
+// own arguments before the context is touched; a plan of another device is refused here, before the lock.
 template <typename T, typename Launch>
-static int stored_walk(mi32_context *h, const mi32_vbatch *p, const Launch &launch)
+static int member_walk(mi32_context *h, const mi32_vbatch *p, const Launch &launch)
 {
+    if (p->device != h->device) return MI32_BAD_SHAPE;
     std::lock_guard<std::mutex> lk(h->mu);
     MI32_HIP(hipSetDevice(h->device));
     hipError_t e = hipSuccess;
@@ -305,11 +269,34 @@ static int stored_walk(mi32_context *h, const mi32_vbatch *p, const Launch &laun
 }
 
 template <typename T>
+static int apply_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T *const *d_x, const int *d_ldx,
+                                 const T *const *d_r, const int *d_ldr, int nrhs, T *const *d_z, const int *d_ldz)
+{
+    if (!h || !p || !d_x || !d_r || !d_z || nrhs <= 0) return MI32_BAD_SHAPE;
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const ApplyArgs<T> a{p->d_orders, p->d_members, d_x, d_r, d_z, d_ldx, d_ldr, d_ldz, nrhs};
+        return apply_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
+template <typename T>
+static int csr_blocks_device(mi32_context *h, const mi32_vbatch *p, const void *d_row_ptr, const void *d_col,
+                             int index_bytes, const T *d_val, const long long *d_first, T *const *d_out,
+                             const int *d_ldout)
+{
+    if (!h || !p || !d_row_ptr || !d_col || !d_val || !d_first || !d_out) return MI32_BAD_SHAPE;
+    if (index_bytes != 4 && index_bytes != 8) return MI32_BAD_SHAPE;
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const CsrBlocksArgs<T> a{p->d_orders, p->d_members, d_row_ptr, d_col, d_val, d_first, d_out, d_ldout, index_bytes};
+        return csr_blocks_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
+template <typename T>
 static int block_stats_device(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda, double *d_stats)
 {
     if (!h || !p || !d_a || !d_stats) return MI32_BAD_SHAPE;
-    if (p->device != h->device) return MI32_BAD_SHAPE;
-    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
         const BlockStatsArgs<T> a{p->d_orders, p->d_members, d_a, d_lda, d_stats};
         return block_stats_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
     });
@@ -320,8 +307,7 @@ static int store_inverses_device(mi32_context *h, const mi32_vbatch *p, const T 
                                  const int *d_format, const long long *d_offset, void *d_store)
 {
     if (!h || !p || !d_x || !d_format || !d_offset || !d_store) return MI32_BAD_SHAPE;
-    if (p->device != h->device) return MI32_BAD_SHAPE;
-    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
         const StoreArgs<T> a{p->d_orders, p->d_members, d_x, d_ldx, d_format, d_offset, static_cast<unsigned char *>(d_store)};
         return store_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
     });
@@ -333,8 +319,7 @@ static int apply_stored_device(mi32_context *h, const mi32_vbatch *p, const void
                                const int *d_ldz)
 {
     if (!h || !p || !d_store || !d_offset || !d_format || !d_r || !d_z || nrhs <= 0) return MI32_BAD_SHAPE;
-    if (p->device != h->device) return MI32_BAD_SHAPE;
-    return stored_walk<T>(h, p, [&](const ApplyLaunch &l) {
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
         const StoredApplyArgs<T> a{p->d_orders, p->d_members, static_cast<const unsigned char *>(d_store), d_offset, d_format,
                                    d_r, d_z, d_ldr, d_ldz, nrhs};
         return apply_stored_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);

@@ -115,6 +115,18 @@ CSR_SIGNATURES = _signatures(
     ("mi32_csr_blocks_device mi32_csr_blocks_device_f64", _I, [_VP] * 4 + [_I] + [_VP] * 4),
 )
 CSR_ABI_SYMBOLS = tuple(CSR_SIGNATURES)
+# finding the blocks from the sparsity pattern, declared in a header of its own (include/mat_inv_32_csr_find.h), and the
+# hook that runs its stages one by one (tools/csr_find_blocks_bench.py)
+_LL = ctypes.c_longlong
+_FIND_ARGS = [_VP, _LL, _VP, _VP, _I, _I, _I, _VP, _VP, _Z]
+CSR_FIND_SIGNATURES = _signatures(
+    ("mi32_csr_find_blocks_work_bytes", _I, [_LL, ctypes.POINTER(_Z)]),
+    ("mi32_csr_find_blocks_device", _I, _FIND_ARGS),
+    ("mi32_csr_find_blocks_chunk_rows", _I, []),
+    ("mi32_debug_csr_find_stages", _I, _FIND_ARGS + [_I]),
+)
+CSR_FIND_ABI_SYMBOLS = tuple(name for name in CSR_FIND_SIGNATURES if not name.startswith("mi32_debug_"))
+CSR_FIND_MAX_ORDER = 128
 # block inverses stored in a per-member format, declared in a header of their own (include/mat_inv_32_stored.h)
 STORED_SIGNATURES = _signatures(
     ("mi32_block_stats_device mi32_block_stats_device_f64", _I, [_VP] * 5),
@@ -155,7 +167,7 @@ def load() -> ctypes.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the pure ctypes/numpy path
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES, **STORED_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES, **CSR_FIND_SIGNATURES, **STORED_SIGNATURES}.items():
         if name == "mi32_debug_dpp_selftest" and not hasattr(lib, name):
             continue  # tools/ab_bench.py also loads builds older than the self-test
         fn = getattr(lib, name)

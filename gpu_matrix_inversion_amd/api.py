@@ -516,6 +516,74 @@ def check_csr_out(values, out, flat_size):
     return out
 
 
+def csr_pattern_parts(a):
+    """``(crow, col)`` of the argument of the calls that read the sparsity pattern alone (``csr_block_starts`` /
+    ``csr_find_blocks``): what ``csr_parts`` takes, and a ``(crow, col, None)`` triple."""
+    import torch
+
+    if isinstance(a, (tuple, list)) and len(a) == 3 and a[2] is None:
+        if not all(isinstance(t, torch.Tensor) for t in a[:2]):
+            raise ValueError("expected a torch.sparse_csr tensor or a (crow, col, values) triple")
+        return a[0], a[1]
+    return csr_parts(a)[:2]
+
+
+def check_csr_pattern(device, crow, col):
+    """``check_csr`` without the values: ``crow`` and ``col`` are contiguous 1-D tensors of ONE dtype, int32 or int64,
+    on ``device``, and ``crow`` has at least 2 entries.  Returns ``N = crow.numel() - 1``.  No synchronisation."""
+    import torch
+
+    if crow.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"crow is {crow.dtype}, expected torch.int32 or torch.int64")
+    if col.dtype != crow.dtype:
+        raise ValueError(f"col is {col.dtype}, crow {crow.dtype}: expected one index dtype")
+    _check_tensor(crow, device, crow.dtype, "crow")
+    _check_tensor(col, device, col.dtype, "col")
+    if crow.numel() < 2:
+        raise ValueError("crow: at least 2 entries (one row)")
+    return crow.numel() - 1
+
+
+def check_find_blocks_args(max_order, agglomerate):
+    """``(max_order, agglomerate)`` as the library takes them: an integer 1 ... 128 (a bool or a float is refused) and
+    a bool."""
+    if isinstance(max_order, bool) or not isinstance(max_order, (int, np.integer)):
+        raise ValueError(f"max_order: expected an integer, not {type(max_order).__name__}")
+    if not 1 <= int(max_order) <= _lib.CSR_FIND_MAX_ORDER:
+        raise ValueError(f"max_order is {int(max_order)}, expected 1 ... {_lib.CSR_FIND_MAX_ORDER}")
+    if not isinstance(agglomerate, (bool, np.bool_)):
+        raise ValueError(f"agglomerate: expected a bool, not {type(agglomerate).__name__}")
+    return int(max_order), bool(agglomerate)
+
+
+def check_block_starts_out(crow, col, out, n):
+    """The output of ``csr_block_starts``: ``out`` where given -- a contiguous 1-D uint8 tensor of ``n`` entries on
+    crow's device that meets the memory of ``crow`` and ``col`` nowhere --, else a new tensor."""
+    import torch
+
+    if out is None:
+        return torch.empty(n, dtype=torch.uint8, device=crow.device)
+    if not isinstance(out, torch.Tensor):
+        raise ValueError("out: expected a tensor")
+    _check_tensor(out, crow.device, torch.uint8, "out", n)
+    if _overlap(out, crow) or _overlap(out, col):
+        raise ValueError("out must not alias crow or col")
+    return out
+
+
+def find_blocks_work_bytes(n):
+    """``mi32_csr_find_blocks_work_bytes``: the temporary memory a call on ``n`` rows needs (host only)."""
+    size = ctypes.c_size_t()
+    _lib.check(_lib.load().mi32_csr_find_blocks_work_bytes(int(n), ctypes.byref(size)), "mi32_csr_find_blocks_work_bytes")
+    return int(size.value)
+
+
+def find_blocks_chunk_rows():
+    """The rows of a chunk of ``csr_block_starts`` (host only): the orbit of row 0 is found chunk by chunk and chained,
+    so this is where the seams are."""
+    return int(_lib.load().mi32_csr_find_blocks_chunk_rows())
+
+
 def validate_csr(crow, col, n):
     """What ``validate=True`` adds to ``check_csr``, each a ValueError: ``crow[0] == 0``, ``crow[-1] == nnz``, ``crow``
     non-decreasing, ``0 <= col < n``, no (row, column) pair twice.  Reads the arrays: synchronises."""
@@ -1193,6 +1261,39 @@ class Inverter:
         ``apply_diag_blocks(x_packed, block_orders, r)`` takes as it is."""
         x = self.csr_diag_blocks(a, block_orders, first_rows=first_rows, validate=validate)
         return self.inv_ragged(self._diag_blocks_plan(None, block_orders)[0], x, out=x, det=det)
+
+    # ---- the block structure itself, from the sparsity pattern ----
+    def csr_block_starts(self, a, max_order=32, *, agglomerate=True, out=None):
+        """Where the block-Jacobi blocks of a sparse matrix begin, found on the device from its sparsity pattern by
+        supervariable agglomeration: a uint8 device tensor of N entries, 1 at the first row of every block.  ``a`` as in
+        ``csr_diag_blocks``, or a ``(crow, col, None)`` triple: the values are not read.  Consecutive rows with the same
+        column indices IN STORED ORDER form a supervariable, cut every ``max_order`` (1 ... 128) rows; with
+        ``agglomerate`` consecutive supervariables are merged while their rows sum to at most ``max_order``.  Rows
+        that hold the same set in a different order count as different: sort unsorted rows first (``torch``'s CSR
+        tensors are sorted).  ``out``: a contiguous uint8 tensor of N entries on the device that meets ``crow`` and
+        ``col`` nowhere.  The temporary memory (2.1 bytes per row) is a ``torch.empty`` of this call.  Asynchronous on
+        torch's current stream; no synchronisation."""
+        torch = self._torch
+        crow, col = csr_pattern_parts(a)
+        n = check_csr_pattern(self.device, crow, col)
+        max_order, agglomerate = check_find_blocks_args(max_order, agglomerate)
+        out = check_block_starts_out(crow, col, out, n)
+        nbytes = find_blocks_work_bytes(n)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._bind_stream()
+        # (a pattern without entries has no col to point at: every row is empty and no entry is read, crow stands in)
+        _lib.check(self._lib.mi32_csr_find_blocks_device(
+            self._h, n, _ptr(crow), _ptr(col if col.numel() else crow), crow.element_size(), max_order,
+            int(agglomerate), _ptr(out), _ptr(work), nbytes), "mi32_csr_find_blocks_device")
+        return out
+
+    def csr_find_blocks(self, a, max_order=32, *, agglomerate=True):
+        """The block orders of ``csr_block_starts`` as a host ``np.int32`` array, what every ``block_orders=`` argument
+        takes: they sum to N and each is in 1 ... ``max_order``.  One N-byte copy to the host (this synchronises);
+        plans are binned on the host, so the orders have to arrive there in any case."""
+        start = self.csr_block_starts(a, max_order, agglomerate=agglomerate).cpu().numpy()
+        first = np.flatnonzero(start)
+        return np.diff(first, append=start.size).astype(np.int32)
 
     # ---- block inverses stored in reduced precision per block, and applied from that store ----
     def _block_stats(self, plan, dtype, ptrs, ld):

@@ -8,6 +8,7 @@
 #include "mi32_apply.h"
 #include "mi32_context.h"
 #include "mi32_csr_blocks.h"
+#include "mi32_csr_find.h"
 #include "mi32_det_large.h"
 #include "mi32_stored.h"
 
@@ -292,6 +293,22 @@ static int csr_blocks_device(mi32_context *h, const mi32_vbatch *p, const void *
     });
 }
 
+// The blocks of a CSR pattern (mi32_csr_find.h): the caller's temporary memory, no plan.  stages: FIND_ALL but for the
+// measuring hook.
+static int csr_find_blocks_device(mi32_context *h, long long n, const void *d_row_ptr, const void *d_col, int index_bytes,
+                                  int max_order, int agglomerate, unsigned char *d_start, void *d_work, size_t work_bytes,
+                                  int stages)
+{
+    if (!h || !d_row_ptr || !d_col || !d_start || !d_work || n < 1) return MI32_BAD_SHAPE;
+    if (index_bytes != 4 && index_bytes != 8) return MI32_BAD_SHAPE;
+    if (max_order < 1 || max_order > kFindMaxOrder) return MI32_BAD_SHAPE;
+    if (work_bytes < find_layout(n).bytes || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0) return MI32_BAD_SHAPE;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MI32_HIP(hipSetDevice(h->device));
+    const FindArgs a{n, d_row_ptr, d_col, index_bytes, max_order, agglomerate != 0, d_start, d_work};
+    return hip_status(csr_find_launch(a, stages, h->stream, h->prof), "kernel launch");
+}
+
 template <typename T>
 static int block_stats_device(mi32_context *h, const mi32_vbatch *p, const T *const *d_a, const int *d_lda, double *d_stats)
 {
@@ -488,6 +505,32 @@ int mi32_csr_blocks_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_r
                                const int *d_ldout)
 {
     return csr_blocks_device(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_out, d_ldout);
+}
+
+int mi32_csr_find_blocks_work_bytes(long long n, size_t *bytes)
+{
+    if (n < 1 || !bytes) return MI32_BAD_SHAPE;
+    *bytes = find_layout(n).bytes;
+    return MI32_OK;
+}
+
+int mi32_csr_find_blocks_chunk_rows(void) { return kFindChunk; }
+
+int mi32_csr_find_blocks_device(mi32_handle_t h, long long n, const void *d_row_ptr, const void *d_col, int index_bytes,
+                                int max_order, int agglomerate, unsigned char *d_start, void *d_work, size_t work_bytes)
+{
+    return csr_find_blocks_device(h, n, d_row_ptr, d_col, index_bytes, max_order, agglomerate, d_start, d_work, work_bytes,
+                                  FIND_ALL);
+}
+
+// Not part of include/mat_inv_32_csr_find.h: the stages of `stages` (1 nat, 2 runs, 4 sv, 8 chain, 16 mark) alone, on the
+// temporary memory a whole call left, for tools/csr_find_blocks_bench.py to time them one by one.
+int mi32_debug_csr_find_stages(mi32_handle_t h, long long n, const void *d_row_ptr, const void *d_col, int index_bytes,
+                               int max_order, int agglomerate, unsigned char *d_start, void *d_work, size_t work_bytes,
+                               int stages)
+{
+    return csr_find_blocks_device(h, n, d_row_ptr, d_col, index_bytes, max_order, agglomerate, d_start, d_work, work_bytes,
+                                  stages & FIND_ALL);
 }
 
 int mi32_block_stats_device(mi32_handle_t h, mi32_vbatch_t p, const float *const *d_a, const int *d_lda, double *d_stats)

@@ -134,6 +134,14 @@ STORED_SIGNATURES = _signatures(
     ("mi32_apply_stored_device mi32_apply_stored_device_f64", _I, [_VP] * 7 + [_I] + [_VP] * 2),
 )
 STORED_ABI_SYMBOLS = tuple(STORED_SIGNATURES)
+# the block residual and the fused relaxation sweep, declared in a header of their own (include/mat_inv_32_relax.h);
+# omega is passed by value in the working type
+RELAX_SIGNATURES = _signatures(
+    ("mi32_csr_block_residual_device mi32_csr_block_residual_device_f64", _I, [_VP] * 4 + [_I] + [_VP] * 5),
+    ("mi32_csr_relax_stored_device", _I, [_VP] * 4 + [_I] + [_VP] * 7 + [ctypes.c_float, _VP]),
+    ("mi32_csr_relax_stored_device_f64", _I, [_VP] * 4 + [_I] + [_VP] * 7 + [ctypes.c_double, _VP]),
+)
+RELAX_ABI_SYMBOLS = tuple(RELAX_SIGNATURES)
 
 
 def build_library(force: bool = False) -> str:
@@ -167,7 +175,8 @@ def load() -> ctypes.CDLL:
     except Exception:  # pragma: no cover - torch is optional for the pure ctypes/numpy path
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES, **CSR_FIND_SIGNATURES, **STORED_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **CSR_SIGNATURES, **CSR_FIND_SIGNATURES, **STORED_SIGNATURES,
+                                       **RELAX_SIGNATURES}.items():
         if name == "mi32_debug_dpp_selftest" and not hasattr(lib, name):
             continue  # tools/ab_bench.py also loads builds older than the self-test
         fn = getattr(lib, name)

@@ -717,6 +717,58 @@ def check_store_data(device, data, nbytes, x_flat=None):
         raise ValueError("data must not alias x_flat")
 
 
+# ---- the vectors and blocks of csr_block_residual / relax_stored: pure torch and NumPy as above ----
+def check_relax_vectors(values, n, x, b):
+    """The iterate and the right-hand side of ``csr_block_residual`` / ``relax_stored``: ``x`` and ``b`` are contiguous
+    1-D tensors of ``n`` entries, of the dtype and device of ``values`` (the checked values of the CSR matrix)."""
+    import torch
+
+    for what, t in (("x", x), ("b", b)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: expected a tensor")
+        _check_tensor(t, values.device, values.dtype, what, n)
+
+
+def check_relax_out(values, out, numel, reads):
+    """The output of ``csr_block_residual`` / ``relax_stored``: ``out`` where given -- a contiguous 1-D tensor of
+    ``numel`` entries of values' dtype and device that meets none of ``reads``, {name: tensor or span} of everything
+    the call reads --, else None (the caller allocates)."""
+    import torch
+
+    if out is None:
+        return None
+    if not isinstance(out, torch.Tensor):
+        raise ValueError("out: expected a tensor")
+    _check_tensor(out, values.device, values.dtype, "out", numel)
+    for what, t in reads.items():
+        if _overlap(out, t):
+            raise ValueError(f"out must not alias {what}")
+    return out
+
+
+def check_blocks_disjoint(first, orders):
+    """ValueError unless the blocks ``first[b] ... first[b] + orders[b] - 1`` (host arrays, ``check_csr_first_rows``)
+    meet one another nowhere: a Jacobi sweep writes every row once."""
+    first, orders = np.asarray(first, np.int64), np.asarray(orders, np.int64)
+    by = np.argsort(first, kind="stable")
+    ends = (first + orders)[by]
+    clash = np.nonzero(ends[:-1] > first[by][1:])[0]
+    if clash.size:
+        a, b = int(by[clash[0]]), int(by[clash[0] + 1])
+        raise ValueError(f"blocks {a} (rows {int(first[a])} ... {int(first[a] + orders[a]) - 1}) and {b} (from row "
+                         f"{int(first[b])}) overlap: a relaxation sweep takes disjoint blocks")
+
+
+def check_sweeps(sweeps, omega):
+    """``(sweeps, omega)`` as the library takes them: an integer at least 1 (a bool or a float is refused) and a real
+    number."""
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)) or sweeps < 1:
+        raise ValueError("sweeps: an integer, at least 1")
+    if isinstance(omega, bool) or not isinstance(omega, (int, float, np.integer, np.floating)):
+        raise ValueError(f"omega: expected a real number, not {type(omega).__name__}")
+    return int(sweeps), float(omega)
+
+
 class _StoreSpan:
     """The store's memory as ``check_packed_rhs`` looks at the matrices of a call: the members' dtype and device, and
     the span of the byte buffer."""
@@ -1418,6 +1470,84 @@ class Inverter:
         stored = self.store_inverses(plan, x, formats)
         self._diag_plan = None  # the stored object owns the plan now
         return stored, status, formats
+
+    # ---- a solver-level use of the store: the residual of the block rows, and the fused block-Jacobi sweep ----
+    def csr_block_residual(self, a, plan, x, b, out=None, *, first_rows=None, validate=False):
+        """``r = (b - A x)`` at the rows of the blocks, in the packed layout that ``apply_stored`` and ``apply_ragged``
+        take (member i's rows start at ``sum_{k<i} n_k``), in one call (at most five launches).  ``a`` as in
+        ``csr_diag_blocks``; ``plan`` is the RaggedPlan of the block orders; ``first_rows`` as in ``csr_diag_blocks``
+        (None: consecutive blocks whose orders sum to N; blocks may overlap or skip rows).  ``x`` and ``b`` are
+        contiguous N-vectors of values' dtype and device.  The arithmetic is fixed bit for bit: per row eight partial
+        sums over the stored entries in stored order, ``p[e % 8] = fma(val_e, x[col_e], p[e % 8])``, a three-level
+        butterfly ``(p_s + p_{s^4}) + (.. s^2) + (.. s^1)`` and ``b - sum``, whatever the block order or the index
+        dtype.  ``out``: a contiguous 1-D tensor of ``plan.total_rows`` entries that meets neither ``x``, ``b`` nor
+        the CSR arrays.  ``validate=True`` adds the synchronising checks of ``validate_csr``.  Asynchronous on
+        torch's current stream.  Returns r."""
+        crow, col, values = csr_parts(a)
+        n = check_csr(self.device, crow, col, values)
+        check_ragged_call(self.device, plan, values.dtype, want_status=False)
+        first = check_csr_first_rows(first_rows, plan.orders, n)
+        check_relax_vectors(values, n, x, b)
+        out = check_relax_out(values, out, plan.total_rows, {"x": x, "b": b, "crow": crow, "col": col, "values": values})
+        if validate:
+            validate_csr(crow, col, n)
+        if out is None:
+            out = self._torch.empty(plan.total_rows, dtype=values.dtype, device=values.device)
+        d_first = plan._row_offsets if first_rows is None else self._torch.from_numpy(first).to(self.device)
+        stream = self._bind_stream()
+        _lib.check(self._entry("mi32_csr_block_residual_device", values.dtype)(
+            self._h, plan._p, _ptr(crow), _ptr(col), crow.element_size(), _ptr(values), _ptr(d_first), _ptr(x), _ptr(b),
+            _ptr(plan._pointers(out, 1, stream))), "mi32_csr_block_residual_device")
+        return out
+
+    def relax_stored(self, a, stored, x, b, omega=1.0, out=None, *, first_rows=None, sweeps=1, validate=False):
+        """Block-Jacobi relaxation from the sparse matrix and the stored block inverses, fused:
+        ``x' = x + omega * blockdiag(A)^-1 (b - A x)`` in one call per sweep (at most five launches; the residual
+        never goes to memory).  ``a`` as in ``csr_diag_blocks``; ``stored`` is the ``StoredInverses`` of the blocks
+        (``inv_csr_blocks_adaptive`` or ``store_inverses``), of the matrix's dtype; ``first_rows`` places its members
+        as in ``csr_diag_blocks``, and the blocks must not overlap one another.  Bit for bit,
+        ``x'[rows of block b] = fma(omega, z_b, x[rows of block b])`` with ``z_b`` what ``apply_stored`` returns on
+        ``csr_block_residual``'s r.  Rows in no block are not written: ``out=None`` gives a new tensor where the
+        blocks tile ``[0, N)`` and ``x.clone()`` otherwise.  ``out``: a contiguous N-vector that meets neither ``x``,
+        ``b``, the CSR arrays nor ``stored.data`` (every block reads the old x).  ``sweeps=k`` runs k sweeps on the
+        stream, ping-ponging between ``out`` and one temporary, with no host synchronisation; where the blocks do not
+        tile ``[0, N)``, the rows in no block are the fixed part of the iterate, and with ``k > 1`` a given ``out``
+        first receives them from ``x``.  Asynchronous on torch's current stream.  Returns x'."""
+        if not isinstance(stored, StoredInverses):
+            raise ValueError("expected the StoredInverses of store_inverses")
+        crow, col, values = csr_parts(a)
+        n = check_csr(self.device, crow, col, values)
+        if stored.dtype != values.dtype:
+            raise ValueError(f"stored holds {stored.dtype} members, the matrix is {values.dtype}")
+        plan = stored.plan
+        check_ragged_call(self.device, plan, stored.dtype, want_status=False)
+        sweeps, omega = check_sweeps(sweeps, omega)
+        first = check_csr_first_rows(first_rows, plan.orders, n)
+        check_blocks_disjoint(first, plan.orders)
+        check_relax_vectors(values, n, x, b)
+        out = check_relax_out(values, out, n, {"x": x, "b": b, "crow": crow, "col": col, "values": values,
+                                                 "stored.data": stored.data})
+        if validate:
+            validate_csr(crow, col, n)
+        tiles = plan.total_rows == n  # disjoint blocks inside the matrix: they cover it where their rows are all of it
+        if out is None:
+            out = self._torch.empty_like(x) if tiles else x.clone()
+        elif not tiles and sweeps > 1:
+            out.copy_(x)
+        tmp = None
+        if sweeps > 1:
+            tmp = self._torch.empty_like(x) if tiles else x.clone()
+        d_first = plan._row_offsets if first_rows is None else self._torch.from_numpy(first).to(self.device)
+        fn = self._entry("mi32_csr_relax_stored_device", values.dtype)
+        self._bind_stream()
+        src = x
+        for j in range(sweeps):
+            dst = out if (sweeps - 1 - j) % 2 == 0 else tmp
+            _lib.check(fn(self._h, plan._p, _ptr(crow), _ptr(col), crow.element_size(), _ptr(values), _ptr(d_first),
+                          _ptr(stored.data), _ptr(stored.offsets), _ptr(stored.formats), _ptr(src), _ptr(b), omega,
+                          _ptr(dst)), "mi32_csr_relax_stored_device")
+            src = dst
+        return out
 
     def set_lookahead(self, enable: bool):
         _lib.check(self._lib.mi32_set_lookahead(self._h, 1 if enable else 0), "mi32_set_lookahead")

@@ -183,7 +183,7 @@ static int create_streams(mi32_context *h)
 
 extern "C" {
 
-int mi32_version(void) { return 147; }
+int mi32_version(void) { return 148; }
 const char *mi32_last_error(void) { return g_last_error.c_str(); }
 
 int mi32_create(mi32_handle_t *out, int device)

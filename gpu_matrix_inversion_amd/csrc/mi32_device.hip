@@ -10,6 +10,7 @@
 #include "mi32_csr_blocks.h"
 #include "mi32_csr_find.h"
 #include "mi32_det_large.h"
+#include "mi32_relax.h"
 #include "mi32_stored.h"
 
 using namespace mi32;
@@ -252,8 +253,8 @@ static int solve_device_vbatched(mi32_context *h, const mi32_vbatch *p, const T 
 }
 
 // The calls that walk a plan's members with the apply call's launch list (apply_walk: one launch per lane class that has
-// members): the product, the CSR gather, and the statistics, store and apply of block inverses in a per-member storage
-// format (mi32_stored.h).  No workspace, no memset, no status: a product or a copy cannot fail.  Each caller checks its
+// members): the product, the CSR gather, the statistics, store and apply of block inverses in a per-member storage
+// format (mi32_stored.h), and the block residual and relaxation sweep on them (mi32_relax.h).  No workspace, no memset, no status: a product or a copy cannot fail.  Each caller checks its
 // own arguments before the context is touched; a plan of another device is refused here, before the lock.
 template <typename T, typename Launch>
 static int member_walk(mi32_context *h, const mi32_vbatch *p, const Launch &launch)
@@ -340,6 +341,23 @@ static int apply_stored_device(mi32_context *h, const mi32_vbatch *p, const void
         const StoredApplyArgs<T> a{p->d_orders, p->d_members, static_cast<const unsigned char *>(d_store), d_offset, d_format,
                                    d_r, d_z, d_ldr, d_ldz, nrhs};
         return apply_stored_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
+    });
+}
+
+// The residual of the block rows (d_r set) or the fused sweep (d_xnew set) of mi32_relax.h.
+template <typename T>
+static int relax_device(mi32_context *h, const mi32_vbatch *p, const void *d_row_ptr, const void *d_col, int index_bytes,
+                        const T *d_val, const long long *d_first, const void *d_store, const long long *d_offset,
+                        const int *d_format, const T *d_x, const T *d_b, T omega, T *d_xnew, T *const *d_r)
+{
+    if (!h || !p || !d_row_ptr || !d_col || !d_val || !d_first || !d_x || !d_b) return MI32_BAD_SHAPE;
+    if (d_xnew ? (!d_store || !d_offset || !d_format || d_r) : !d_r) return MI32_BAD_SHAPE;
+    if (index_bytes != 4 && index_bytes != 8) return MI32_BAD_SHAPE;
+    return member_walk<T>(h, p, [&](const ApplyLaunch &l) {
+        const RelaxArgs<T> a{p->d_orders, p->d_members, d_row_ptr, d_col, d_val, d_first,
+                             static_cast<const unsigned char *>(d_store), d_offset, d_format, d_x, d_b, d_xnew, d_r, omega,
+                             index_bytes};
+        return relax_vlaunch(l.lanes, a, l.first, l.count, h->stream, h->prof);
     });
 }
 
@@ -568,6 +586,42 @@ int mi32_apply_stored_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d
                                  double *const *d_z, const int *d_ldz)
 {
     return apply_stored_device(h, p, d_store, d_offset, d_format, d_r, d_ldr, nrhs, d_z, d_ldz);
+}
+
+int mi32_csr_block_residual_device(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col,
+                                   int index_bytes, const float *d_val, const long long *d_first, const float *d_x,
+                                   const float *d_b, float *const *d_r)
+{
+    return relax_device<float>(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, nullptr, nullptr, nullptr, d_x, d_b, 0.0f,
+                               nullptr, d_r);
+}
+
+int mi32_csr_block_residual_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col,
+                                       int index_bytes, const double *d_val, const long long *d_first, const double *d_x,
+                                       const double *d_b, double *const *d_r)
+{
+    return relax_device<double>(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, nullptr, nullptr, nullptr, d_x, d_b, 0.0,
+                                nullptr, d_r);
+}
+
+int mi32_csr_relax_stored_device(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col,
+                                 int index_bytes, const float *d_val, const long long *d_first, const void *d_store,
+                                 const long long *d_offset, const int *d_format, const float *d_x, const float *d_b,
+                                 float omega, float *d_xnew)
+{
+    if (!d_xnew) return MI32_BAD_SHAPE;
+    return relax_device<float>(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_store, d_offset, d_format, d_x, d_b,
+                               omega, d_xnew, nullptr);
+}
+
+int mi32_csr_relax_stored_device_f64(mi32_handle_t h, mi32_vbatch_t p, const void *d_row_ptr, const void *d_col,
+                                     int index_bytes, const double *d_val, const long long *d_first, const void *d_store,
+                                     const long long *d_offset, const int *d_format, const double *d_x, const double *d_b,
+                                     double omega, double *d_xnew)
+{
+    if (!d_xnew) return MI32_BAD_SHAPE;
+    return relax_device<double>(h, p, d_row_ptr, d_col, index_bytes, d_val, d_first, d_store, d_offset, d_format, d_x, d_b,
+                                omega, d_xnew, nullptr);
 }
 
 int mi32_residual_device(mi32_handle_t h, const float *d_a, const float *d_x, int n, int batch, double *d_out)

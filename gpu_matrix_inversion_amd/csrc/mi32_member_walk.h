@@ -1,6 +1,6 @@
 // mi32_member_walk.h -- what the kernels that walk a plan's sorted member list share, and their launchers: mi32_apply.hip,
-// mi32_stored.hip and mi32_csr_blocks.hip, one launch per lane class that has members (apply_walk).  Device code and its
-// launch layer: no host unit includes it.  First the layer every such kernel uses -- the threads rule, the fence inside a
+// mi32_stored.hip, mi32_csr_blocks.hip and mi32_relax.hip, one launch per lane class that has members (apply_walk).
+// Device code and its launch layer: no host unit includes it.  First the layer every such kernel uses -- the threads rule, the fence inside a
 // group, the group-to-member lookup, the wave-wide maximum, the lane-class dispatch and the launch --, then the body of
 // the product Z = X R around a loader (mi32_apply.hip, whose top explains the layout and the +0 / -0 padding rule).
 #pragma once
